@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the PPDE hot path: MCMC steps/sec on synthetic PABP_YEAST-shaped inputs (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline figure needs: it sets up, warms up, times exactly K steps, writes the outputs of
+the last step if --dump-outputs is given, and prints the result line (`value`, `ms_per_step`, ...). --full measures
+everything else as well (the other evaluation policy, roofline figures, the CPU baseline, the `also` configurations,
+the reference's protocol as a command) and times the headline as the median of 5 blocks of K steps.
 
 With --gpus N > 1 and no RANK in the environment this process only LAUNCHES the ranks (a child
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same arguments>`; the parent never
@@ -19,8 +24,8 @@ configs[3] (1024 chains over 8 GPUs) with the Potts expert alone; `--protein GFP
 the reference would run it (its energy evaluates the supervised CNN whatever lamda is; --lamda defaults to the README's 15). Inputs are synthetic (seeded couplings, all chains start at the wild
 type) and resident in HBM before the timed region. Rank 0 prints ONE JSON line.
 
-Timing: W warm-up steps, then `--repeats` blocks of EXACTLY K steps, each block bracketed by barrier +
-synchronize on both sides and reduced with MAX over ranks; `value` is computed from the MEDIAN block. Every
+Timing: W warm-up steps, then `--repeats` blocks (default 1; 5 with --full) of EXACTLY K steps, each block bracketed by
+barrier + synchronize on both sides and reduced with MAX over ranks; `value` is computed from the MEDIAN block. Every
 iteration of a block is replayed from hipGraphs captured by ppde_chains_init (never inside the timed region:
 `graph_captured_in_timed_region` comes from a counter in the library).
 """
@@ -47,7 +52,17 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=None, help="timed iterations per block (default: 2000; transformer workload: 20)")
     p.add_argument("--warmup", type=int, default=None, help="untimed iterations before the first block (default: 200; transformer workload: 3)")
-    p.add_argument("--repeats", type=int, default=5, help="timed blocks of --steps iterations; the median is reported")
+    p.add_argument("--repeats", type=int, default=None,
+                   help="timed blocks of --steps iterations, the median is reported (default: 1, i.e. exactly --steps timed "
+                        "iterations; with --full: 5)")
+    p.add_argument("--full", action="store_true",
+                   help="everything beyond the headline figure as well: the other evaluation policy, the Potts kernel's roofline "
+                        "(in situ, back to back, GFP size), the CPU baseline, the timed population gather of a multi-rank run, and "
+                        "on the default N = 1 workload the `also` configurations and the reference's protocol timed as a command; "
+                        "--no-cpu-baseline / --no-large / --no-also leave parts of it out")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the timed path computed in its last step as DIR/<name>.npy "
+                        "(float32 / float64; rank 0's chains)")
     p.add_argument("--chains", type=int, default=None, help="chains per GPU (default: 128; transformer workload: 256, BASELINE configs[4])")
     p.add_argument("--workload", default="potts", choices=["potts", "potts+cnn", "transformer"],
                    help="potts = BASELINE configs[1] (Potts-only PoE); potts+cnn = configs[2] (lamda=5); "
@@ -104,12 +119,38 @@ def resolve_defaults(args):
         args.warmup = 3 if tf else 200
     if args.chains is None:
         args.chains = 256 if tf else 128
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     return args
 
 
 def env_flag(name):
     """Knobs of this script are off unless set to something other than '' / '0' (as the library's atoi-style knobs)."""
     return os.environ.get(name, "0") not in ("", "0")
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def last_step_outputs(ch):
+    """What a caller of the timed path holds after its last step (Chains.peek + Chains.collect): the chains' current states,
+    energies, fitness values, accept bits and mutation counts, the best state of every chain with its energy, fitness and
+    step, and the energy / fitness history rows of the last step. Integers are converted exactly to float32 / float64."""
+    p, c = ch.peek(), ch.collect()
+    return {"state_idx": p["idx"].astype(np.float32), "energy": p["energy"], "fitness": p["fitness"],
+            "accepted": p["accepted"].astype(np.float32), "mutations": p["dist"].astype(np.float64),
+            "best_idx": c["best_idx"].astype(np.float32), "best_energy": c["best_energy"], "best_fitness": c["best_fitness"],
+            "best_step": c["best_step"].astype(np.float64),
+            "energy_history_last": c["energy_history"][-1], "fitness_history_last": c["fitness_history"][-1]}
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64, at most DUMP_LIMIT_BYTES in all."""
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values()), {k: a.dtype for k, a in arrays.items()}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_LIMIT_BYTES
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def build_model(workload, device, protein="PABP", lamda=5.0):
@@ -382,9 +423,10 @@ def main():
     backend = os.environ.get("PPDE_BENCH_BACKEND", "nccl")          # "gloo" + PPDE_BENCH_ONE_GPU=1: rehearse N ranks on one card
     if env_flag("PPDE_BENCH_ONE_GPU"):
         local = 0
+    on_timed = (lambda ch: dump_outputs(args.dump_outputs, last_step_outputs(ch))) if args.dump_outputs and rank == 0 else None
     if args.workload == "transformer":
         import bench_transformer
-        return bench_transformer.main(args, rank, world, local, backend)
+        return bench_transformer.main(args, rank, world, local, backend, on_timed=on_timed)
     # PPDE_BENCH_FORCE_DIST=1 (with PPDE_COLLECTIVES_AT_WORLD_1=1): a ONE-rank process group, so that a one-GPU box executes
     # the RCCL branch (init, barrier, all_reduce, the population gather) before an 8-GPU node ever sees it
     dist_on = world > 1 or env_flag("PPDE_BENCH_FORCE_DIST")
@@ -437,30 +479,33 @@ def main():
     ch, dts = timed_run(bool(args.reuse_grad), args.repeats)
     dt = float(np.median(dts))
     stats = ch.graph_stats()
-    ch_other, dts_other = timed_run(not bool(args.reuse_grad), min(args.repeats, 3))   # the other evaluation policy, for the record
-    dt_other = float(np.median(dts_other))
-    del ch_other
+    if on_timed:
+        on_timed(ch)
+    if args.full:
+        ch_other, dts_other = timed_run(not bool(args.reuse_grad), min(args.repeats, 3))   # the other evaluation policy, for the record
+        dt_other = float(np.median(dts_other))
+        del ch_other
 
-    # dominant kernel: potts_energy_grad, timed live IN SITU: every kernel of IN_SITU real, eagerly launched iterations carries
-    # a stop event bound to its dispatch (hipExtLaunchKernelGGL: the dispatch's end timestamp as the command processor records
-    # it -- the source rocprofv3's kernel trace reads), and a Potts launch is timed from its predecessor's end to its own end,
-    # which is how rocprofv3's per-kernel table accounts a dependent kernel: this is the figure profiles/ reproduces. Beside
-    # it, for the record: 500 launches back to back between one event pair (no dependent chain kernel in front of any of them).
-    if which == 1:
-        pk_situ_us, pk_launches, pk_disp_us = ch.time_potts_in_situ(IN_SITU)
-        pk_us = ch.time_potts_kernel(500)
-    else:       # (the in-situ hook times dispatch to dispatch and is defined for the Potts-only energy: the same kernel, its own chains)
-        chp = Chains(m, n, IN_SITU + 8, args.pas, args.nmut, False, i0, i0 + Lp - 1, 1, 1, reuse_grad=False, random_chain=0,
-                     use_graph=False, seed=1, chain_offset=rank * n)
-        chp.init(torch.as_tensor(np.tile(wt, (n, 1))).to(device))
-        pk_situ_us, pk_launches, pk_disp_us = chp.time_potts_in_situ(IN_SITU)
-        pk_us = chp.time_potts_kernel(500)
-        del chp
-    alg_bytes = potts_alg_bytes(n, L, Lp)
-    traffic, traffic_source = load_traffic(args.protein)
+        # dominant kernel: potts_energy_grad, timed live IN SITU: every kernel of IN_SITU real, eagerly launched iterations carries
+        # a stop event bound to its dispatch (hipExtLaunchKernelGGL: the dispatch's end timestamp as the command processor records
+        # it -- the source rocprofv3's kernel trace reads), and a Potts launch is timed from its predecessor's end to its own end,
+        # which is how rocprofv3's per-kernel table accounts a dependent kernel: this is the figure profiles/ reproduces. Beside
+        # it, for the record: 500 launches back to back between one event pair (no dependent chain kernel in front of any of them).
+        if which == 1:
+            pk_situ_us, pk_launches, pk_disp_us = ch.time_potts_in_situ(IN_SITU)
+            pk_us = ch.time_potts_kernel(500)
+        else:       # (the in-situ hook times dispatch to dispatch and is defined for the Potts-only energy: the same kernel, its own chains)
+            chp = Chains(m, n, IN_SITU + 8, args.pas, args.nmut, False, i0, i0 + Lp - 1, 1, 1, reuse_grad=False, random_chain=0,
+                         use_graph=False, seed=1, chain_offset=rank * n)
+            chp.init(torch.as_tensor(np.tile(wt, (n, 1))).to(device))
+            pk_situ_us, pk_launches, pk_disp_us = chp.time_potts_in_situ(IN_SITU)
+            pk_us = chp.time_potts_kernel(500)
+            del chp
+        alg_bytes = potts_alg_bytes(n, L, Lp)
+        traffic, traffic_source = load_traffic(args.protein)
 
-    tag = {("potts", "PABP"): "config2", ("potts+cnn", "PABP"): "config3", ("potts", "GFP"): "gfp", ("potts", "UBE4B"): "ube4b"}.get((args.workload, args.protein))
-    rocprof = committed_profile(tag, "potts_energy_grad_kernel", alg_bytes, HBM_PEAK_GBS * 1e9, pk_disp_us or pk_situ_us) if tag and n == 128 else None
+        tag = {("potts", "PABP"): "config2", ("potts+cnn", "PABP"): "config3", ("potts", "GFP"): "gfp", ("potts", "UBE4B"): "ube4b"}.get((args.workload, args.protein))
+        rocprof = committed_profile(tag, "potts_energy_grad_kernel", alg_bytes, HBM_PEAK_GBS * 1e9, pk_disp_us or pk_situ_us) if tag and n == 128 else None
 
     res = ch.collect()
     assert np.isfinite(res["energy_history"]).all()
@@ -468,7 +513,7 @@ def main():
     # final population collect: one all_gather of best states / energies / histories, outside the
     # timed region, timed on its own
     gather_ms, rccl_ranks = None, None
-    if dist_on:
+    if dist_on and args.full:
         ones = torch.ones(1, device=device if backend == "nccl" else "cpu")
         torch.distributed.all_reduce(ones)
         rccl_ranks = int(ones.item())
@@ -484,7 +529,7 @@ def main():
 
     # second roofline entry at the size where the HBM target is reachable: the GFP window (L' = 237, 90 MB of couplings)
     roofline_large = None
-    if rank == 0 and world == 1 and args.protein == "PABP" and not args.no_large:
+    if args.full and rank == 0 and world == 1 and args.protein == "PABP" and not args.no_large:
         del ch
         mg, wtg, _, _, i0g, Lpg, _ = build_model("potts", device, "GFP")
         chg = Chains(mg, n, 4, args.pas, 0, False, i0g, i0g + Lpg - 1, 1, 1, reuse_grad=False, random_chain=0,
@@ -525,19 +570,21 @@ def main():
             "timed_blocks": {"repeats": len(dts), "statistic": "median", "ms_per_block": [round(x * 1e3, 4) for x in dts]},
             "graph_captured_in_timed_region": bool(stats["captures_in_run"]),
             "graph": stats,
-            "roofline": potts_roofline(alg_bytes, pk_situ_us, pk_disp_us, pk_us, pk_launches, rocprof, traffic, traffic_source),
-            ("value_reuse_grad" if not args.reuse_grad else "value_reevaluate"): world * args.steps / dt_other,
         }
+        if args.full:
+            out["roofline"] = potts_roofline(alg_bytes, pk_situ_us, pk_disp_us, pk_us, pk_launches, rocprof, traffic, traffic_source)
+            out["value_reuse_grad" if not args.reuse_grad else "value_reevaluate"] = world * args.steps / dt_other
         if roofline_large:
             out["roofline_large"] = roofline_large
         if dist_on:
-            out["rccl_ranks"] = rccl_ranks
             out["backend"] = backend
-            out["population_gather_ms"] = gather_ms
-        if world == 1 and not args.no_cpu_baseline:
+            if args.full:
+                out["rccl_ranks"] = rccl_ranks
+                out["population_gather_ms"] = gather_ms
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, wt, J, h, i0, Lp, cnn, n)
         # BASELINE configs[2] and configs[4] under the same clock: a few short median-of-3 blocks each (N = 1 default workload only)
-        if world == 1 and not dist_on and args.workload == "potts" and args.protein == "PABP" and n == 128 and not args.no_also:
+        if args.full and world == 1 and not dist_on and args.workload == "potts" and args.protein == "PABP" and n == 128 and not args.no_also:
             out["value_torch_rng"] = torch_rng_value(args, m, wt, i0, Lp, n, which)
             t0 = time.perf_counter()
             from ppde_amd.noise import draw_chunk

@@ -3,7 +3,7 @@ shapes: 30 layers x 640, 20 heads, ffn 2560; synthetic seeded weights) + supervi
 README.md:70-72), 256 chains on one GPU. One step = one MCMC iteration = two energy+gradient evaluations of the
 transformer (forward and input gradient over 256 x 104 tokens) plus the chain kernels.
 
-Roofline entry: the GEMM kernel that carries ~95 % of the arithmetic, timed live at the fc1 shape against the dense
+Roofline entry (with --full): the GEMM kernel that carries ~95 % of the arithmetic, timed live at the fc1 shape against the dense
 fp16 MFMA peak; `eval_tflops` is the whole evaluation (all kernels) at its algorithmic GEMM + attention flops."""
 import ctypes as C
 import json
@@ -27,9 +27,10 @@ def eval_flops(n, L, layers, D, F):
     return layers * (2 * lin + att_f * 3.5) + 2 * head + 2.0 * M * 33 * D
 
 
-def measure(args, rank, world, local, backend, steps, warmup, repeats, with_cpu, other_policy=True):
+def measure(args, rank, world, local, backend, steps, warmup, repeats, with_cpu, other_policy=True, full=True, on_timed=None):
     """-> the bench dict of BASELINE configs[4] (`python bench.py --workload transformer` prints it; the default N = 1 run of
-    bench.py embeds a short version as `also.config5`)."""
+    bench.py --full embeds a short version as `also.config5`). full=False: the headline alone (no roofline, no evaluation
+    timing, no CPU baseline); on_timed(chains) is called right after the timed blocks of the measured policy."""
     import torch
     sys.path.insert(0, REPO)
     from ppde_amd import _hip, synthetic
@@ -64,7 +65,7 @@ def measure(args, rank, world, local, backend, steps, warmup, repeats, with_cpu,
     m.set_lamda(lam)
     T = warmup + repeats * steps + 4
 
-    def timed(reuse):
+    def timed(reuse, on_timed=None):
         ch = Chains(m, n, T, args.pas, args.nmut, False, 0, L - 1, 6, 1, reuse_grad=reuse, random_chain=0, use_graph=False, seed=1,
                     chain_offset=rank * n)
         ch.init(torch.as_tensor(np.tile(wt, (n, 1))).to(device))
@@ -85,37 +86,40 @@ def measure(args, rank, world, local, backend, steps, warmup, repeats, with_cpu,
                 torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
                 d = float(t.item())
             dts.append(d)
+        if on_timed:
+            on_timed(ch)
         res = ch.collect()
         assert np.isfinite(res["energy_history"]).all()
         return float(np.median(dts)), dts
 
-    dt, dts = timed(bool(args.reuse_grad))
+    dt, dts = timed(bool(args.reuse_grad), on_timed)
     dt_other = timed(not bool(args.reuse_grad))[0] if other_policy else None
-    # dominant kernel: the GEMM at the fc1 shape (bias + GELU epilogue; tf_gemm160, or tf_gemm_nt with PPDE_TF_160=0), timed IN SITU: a HIP event pair around every fc1
-    # launch of one real evaluation (what rocprofv3's per-kernel average of the same command sees). The same kernel on
-    # pseudo-random operands, launched back to back, is reported beside it: random fp16 data toggles more of the matrix
-    # pipe and runs at a lower clock than the activations of a real evaluation do.
-    M = (n * L + 127) // 128 * 128
-    x = torch.as_tensor(np.tile(wt, (n, 1))).to(device, torch.uint8).contiguous()
-    us, nl = C.c_float(), C.c_int()
-    _hip.check(_hip.load().ppde_transformer_time_fc1_in_situ(m.handle, _hip.ptr(x), n, C.byref(us), C.byref(nl)))
-    us_rand = C.c_float()
-    use160 = os.environ.get("PPDE_TF_160", "1") != "0" and F % 160 == 0         # (tf_host.h tf_pad_rows: 160 x 160 tiles, rows padded to 640;
-    big = os.environ.get("PPDE_TF_BIG", "0") not in ("", "0")                    #  1280 with the opt-in 256-row tiles)
-    pad = (1280 if big else 640) if use160 else (256 if big else 128)
-    M_launch = (n * L + pad - 1) // pad * pad
-    gemm_name = "tf_gemm160" if use160 else "tf_gemm_nt"
-    _hip.check(_hip.load().ppde_transformer_time_gemm(local, M_launch, F, D, 50, 3, C.byref(us_rand)))
-    gemm_tf = 2.0 * M * F * D / (us.value * 1e-6) / 1e12
-    # one evaluation on its own
-    m.energy_grad(x, 4)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for _ in range(3):
+    if full:
+        # dominant kernel: the GEMM at the fc1 shape (bias + GELU epilogue; tf_gemm160, or tf_gemm_nt with PPDE_TF_160=0), timed IN SITU: a HIP event pair around every fc1
+        # launch of one real evaluation (what rocprofv3's per-kernel average of the same command sees). The same kernel on
+        # pseudo-random operands, launched back to back, is reported beside it: random fp16 data toggles more of the matrix
+        # pipe and runs at a lower clock than the activations of a real evaluation do.
+        M = (n * L + 127) // 128 * 128
+        x = torch.as_tensor(np.tile(wt, (n, 1))).to(device, torch.uint8).contiguous()
+        us, nl = C.c_float(), C.c_int()
+        _hip.check(_hip.load().ppde_transformer_time_fc1_in_situ(m.handle, _hip.ptr(x), n, C.byref(us), C.byref(nl)))
+        us_rand = C.c_float()
+        use160 = os.environ.get("PPDE_TF_160", "1") != "0" and F % 160 == 0         # (tf_host.h tf_pad_rows: 160 x 160 tiles, rows padded to 640;
+        big = os.environ.get("PPDE_TF_BIG", "0") not in ("", "0")                    #  1280 with the opt-in 256-row tiles)
+        pad = (1280 if big else 640) if use160 else (256 if big else 128)
+        M_launch = (n * L + pad - 1) // pad * pad
+        gemm_name = "tf_gemm160" if use160 else "tf_gemm_nt"
+        _hip.check(_hip.load().ppde_transformer_time_gemm(local, M_launch, F, D, 50, 3, C.byref(us_rand)))
+        gemm_tf = 2.0 * M * F * D / (us.value * 1e-6) / 1e12
+        # one evaluation on its own
         m.energy_grad(x, 4)
-    torch.cuda.synchronize()
-    ev = (time.perf_counter() - t0) / 3
-    fl = eval_flops(n, L, layers, D, F)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(3):
+            m.energy_grad(x, 4)
+        torch.cuda.synchronize()
+        ev = (time.perf_counter() - t0) / 3
+        fl = eval_flops(n, L, layers, D, F)
 
     out = {
         "metric": f"MCMC steps/sec ({n} chains, UBE4B transformer PoE)",
@@ -132,21 +136,24 @@ def measure(args, rank, world, local, backend, steps, warmup, repeats, with_cpu,
         "chain_steps_per_s": world * n * steps / dt,
         "timed_blocks": {"repeats": len(dts), "statistic": "median", "ms_per_block": [round(x * 1e3, 3) for x in dts]},
         "graph_captured_in_timed_region": False,
-        "roofline": {"kernel": f"{gemm_name}<bias+GELU> (fc1 shape)", "bound": "mfma", "achieved": gemm_tf, "peak": MFMA_F16_PEAK_TF / 1.0,
-                     "unit": "TFLOP/s", "frac": gemm_tf / MFMA_F16_PEAK_TF, "traffic": None,
-                     "traffic_source": None, "algorithmic_flops_per_launch": 2.0 * M * F * D, "avg_launch_us": us.value,
-                     "launches_timed": nl.value, "shape": [M, F, D], "rows_launched": M_launch,
-                     "timing": "HIP event pair around every fc1 launch of one evaluation (in situ)",
-                     "avg_launch_us_random_operands_back_to_back": us_rand.value},
-        "evaluation": {"ms": ev * 1e3, "algorithmic_tflop": fl / 1e12, "tflops": fl / ev / 1e12,
-                       "note": "one transformer energy+gradient evaluation of all chains (forward + input gradient, every kernel)"},
     }
+    if full:
+        out.update({
+            "roofline": {"kernel": f"{gemm_name}<bias+GELU> (fc1 shape)", "bound": "mfma", "achieved": gemm_tf, "peak": MFMA_F16_PEAK_TF / 1.0,
+                         "unit": "TFLOP/s", "frac": gemm_tf / MFMA_F16_PEAK_TF, "traffic": None,
+                         "traffic_source": None, "algorithmic_flops_per_launch": 2.0 * M * F * D, "avg_launch_us": us.value,
+                         "launches_timed": nl.value, "shape": [M, F, D], "rows_launched": M_launch,
+                         "timing": "HIP event pair around every fc1 launch of one evaluation (in situ)",
+                         "avg_launch_us_random_operands_back_to_back": us_rand.value},
+            "evaluation": {"ms": ev * 1e3, "algorithmic_tflop": fl / 1e12, "tflops": fl / ev / 1e12,
+                           "note": "one transformer energy+gradient evaluation of all chains (forward + input gradient, every kernel)"},
+        })
+        stats = rocprof_frac("transformer", "tf_gemm160<3" if use160 else "tf_gemm_nt<3,", 2.0 * M * F * D, MFMA_F16_PEAK_TF * 1e12)   # <3 ...> = the bias + GELU epilogue (fc1; "<3>" in profiles before the touch-ahead variant, "<3, true>" since)
+        if stats:
+            stats["consistent_with_this_run"] = bool(abs(stats["avg_launch_us"] - us.value) <= 0.10 * us.value)
+            out["roofline"]["committed_profile"] = stats
     if dt_other:
         out["value_reuse_grad" if not args.reuse_grad else "value_reevaluate"] = world * steps / dt_other
-    stats = rocprof_frac("transformer", "tf_gemm160<3" if use160 else "tf_gemm_nt<3,", 2.0 * M * F * D, MFMA_F16_PEAK_TF * 1e12)   # <3 ...> = the bias + GELU epilogue (fc1; "<3>" in profiles before the touch-ahead variant, "<3, true>" since)
-    if stats:
-        stats["consistent_with_this_run"] = bool(abs(stats["avg_launch_us"] - us.value) <= 0.10 * us.value)
-        out["roofline"]["committed_profile"] = stats
     if world > 1:
         out["backend"] = backend
     if world == 1 and with_cpu:
@@ -190,9 +197,11 @@ def rocprof_frac(tag, kernel_substr, work_per_launch, peak=None):
     return out
 
 
-def main(args, rank, world, local, backend):
+def main(args, rank, world, local, backend, on_timed=None):
     import torch
-    out = measure(args, rank, world, local, backend, args.steps, args.warmup, min(args.repeats, 3), False if args.no_cpu_baseline else "minibatch")
+    out = measure(args, rank, world, local, backend, args.steps, args.warmup, min(args.repeats, 3),
+                  "minibatch" if args.full and not args.no_cpu_baseline else False, other_policy=args.full, full=args.full,
+                  on_timed=on_timed)
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -11,7 +11,7 @@ for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU
            "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_INSTS_SALU SQ_INSTS_VMEM" \
            "SQ_INST_CYCLES_VMEM SQ_WAIT_INST_ANY SQ_ACTIVE_INST_MISC SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_IDX_ACTIVE"; do
     i=$((i + 1))
-    rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$OUT/pmc_att_$i" -- python3 "$ROOT/bench.py" ${@:---workload transformer --steps 1 --warmup 1 --repeats 1} --no-cpu-baseline --no-large --no-also > "$OUT/pmc_att_$i.log" 2>&1 || echo "pass $i failed"
+    rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$OUT/pmc_att_$i" -- python3 "$ROOT/bench.py" --full ${@:---workload transformer --steps 1 --warmup 1 --repeats 1} --no-cpu-baseline --no-large --no-also > "$OUT/pmc_att_$i.log" 2>&1 || echo "pass $i failed"
     f=$(ls -t "$OUT"/pmc_att_$i/*/*counter_collection.csv 2>/dev/null | head -1)
     [ -n "$f" ] && python3 - "$f" <<'PY'
 import csv, sys, collections

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$ROOT/gpurun_out
 rm -rf "$OUT/prof_tfq"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_tfq" -- python3 "$ROOT/bench.py" --workload transformer --steps 4 --warmup 1 --repeats 1 --no-cpu-baseline > "$OUT/prof_tfq.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_tfq" -- python3 "$ROOT/bench.py" --full --workload transformer --steps 4 --warmup 1 --repeats 1 --no-cpu-baseline > "$OUT/prof_tfq.log" 2>&1
 python3 - "$(ls -t "$OUT"/prof_tfq/*/*kernel_stats.csv | head -1)" <<'PY'
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))

@@ -6,7 +6,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/qs_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-large --no-also "$@" > "$OUT.log" 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT" -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --no-large --no-also "$@" > "$OUT.log" 2>&1
 F=$(ls -t "$OUT"/*/*kernel_stats.csv | head -1)
 cp "$F" "$ROOT/gpurun_out/qs_${TAG}_kernel_stats.csv"
 head -12 "$F" | cut -d, -f1-4

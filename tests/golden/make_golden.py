@@ -289,6 +289,29 @@ def real_cnn_weights(protein, out):
     print("wrote", out, f"({os.path.getsize(out) / 1e3:.0f} kB)")
 
 
+def real_linear_weights(protein, out):
+    """The VALUES of the shipped ground-truth ridge models of one protein (weights/<protein>/results-...-seed={0..19}-linear.pkl,
+    data files: a dict of coef_, intercept_, reg_coef each) with the files' SHA-256, so that the loader test on the shipped
+    weights (test_oracle_golden.py::test_real_shipped_weights) runs from the repository alone."""
+    import pickle
+    import ppde
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(ppde.__file__))), "weights", protein)
+    payload, names = {}, []
+    for s in range(20):
+        name = f"results-predictor=ev+onehot-train=-1-seed={s}-linear.pkl"
+        with open(os.path.join(src, name), "rb") as fh:
+            d = pickle.load(fh)
+        assert sorted(d) == ["coef_", "intercept_", "reg_coef"], sorted(d)
+        payload[f"seed{s}.coef_"] = np.asarray(d["coef_"])
+        payload[f"seed{s}.intercept_"] = np.asarray(d["intercept_"])
+        payload[f"seed{s}.reg_coef"] = np.asarray(d["reg_coef"])
+        names.append(name)
+    payload["files"] = np.array(names)
+    payload["file_sha"] = np.array([file_sha(os.path.join(src, f)) for f in names])
+    np.savez_compressed(out, **payload)
+    print("wrote", out, f"({os.path.getsize(out) / 1e3:.0f} kB)")
+
+
 def run_case(root, protein, lamda, n, T, seed, pas, nmut, paper, out, store_q, unsup="potts"):
     """One reference sampler run with everything it drew recorded. unsup = 'transformer' / 'potts+transformer': the
     reference's energy.py:110-130 branch over the stand-in ESM-2 (see install_stubs)."""
@@ -474,6 +497,10 @@ def main():
         # chunked HIP kernels, and they are the supervised expert of BASELINE configs 5 and 4
         for protein in ("PABP_YEAST_Fields2013", "UBE4B_MOUSE_Klevit2013-nscor_log2_ratio", "GFP_AEQVI_Sarkisyan2016"):
             real_cnn_weights(protein, os.path.join(HERE, f"real_{protein.split('_')[0].lower()}_cnn.npz"))
+        return
+    if only and "reallinear" in only:
+        for protein in ("PABP_YEAST_Fields2013", "UBE4B_MOUSE_Klevit2013-nscor_log2_ratio", "GFP_AEQVI_Sarkisyan2016"):
+            real_linear_weights(protein, os.path.join(HERE, f"real_{protein.split('_')[0].lower()}_linear.npz"))
         return
     if only and "single" in only:
         with tempfile.TemporaryDirectory() as root:

@@ -241,6 +241,26 @@ def test_bench_launches_its_own_ranks(monkeypatch):
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stdout + r.stderr)
 
 
+
+def test_bench_plain_run_and_full_options(monkeypatch, tmp_path):
+    """A plain bench run times exactly --steps iterations (one block); --full restores the median of 5 blocks next to the
+    measurements it adds; --dump-outputs writes float32 / float64 arrays only, within 64 MB."""
+    import importlib
+    sys.path.insert(0, REPO)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "40", "--warmup", "4"])
+    a = bench.resolve_defaults(bench.parse())
+    assert (a.steps, a.warmup, a.repeats, a.full, a.dump_outputs) == (40, 4, 1, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "d")])
+    a = bench.resolve_defaults(bench.parse())
+    assert (a.steps, a.warmup, a.repeats, a.full, a.dump_outputs) == (2000, 200, 5, True, str(tmp_path / "d"))
+    bench.dump_outputs(a.dump_outputs, {"x": np.arange(6, dtype=np.float32), "y": np.ones((2, 3))})
+    assert np.array_equal(np.load(tmp_path / "d" / "x.npy"), np.arange(6)) and np.load(tmp_path / "d" / "y.npy").dtype == np.float64
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"idx": np.zeros(4, np.uint8)})
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"big": np.zeros((64 << 20) // 4 + 1, np.float32)})
+
 def test_host_layer_under_address_sanitizer():
     """The host side of the C ABI (no device code) against a mock HIP runtime under ASan + LSan: the whole call
     sequence with all three experts, then once more per fallible runtime call with that call failing, so that every

@@ -148,7 +148,7 @@ print("rccl one-rank ok")
 def test_rccl_path_executes_on_one_gpu():
     """A process group of ONE rank on the nccl (= RCCL) backend with the world-size-1 shortcut switched off: RCCL loads,
     builds a communicator and moves the population collect's buffers (host -> device staging -> all_gather / broadcast ->
-    host), and `bench.py --gpus 1` runs its nccl branch (init, barrier, all_reduce, timed gather). Every other multi-rank
+    host), and `bench.py --gpus 1 --full` runs its nccl branch (init, barrier, all_reduce, timed gather). Every other multi-rank
     test uses gloo; this is the only place the RCCL code path runs before an 8-GPU node sees it."""
     import json
     import subprocess
@@ -166,7 +166,40 @@ def test_rccl_path_executes_on_one_gpu():
         os.unlink(path)
     env.update(MASTER_PORT="29548", PPDE_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5", "--repeats", "2",
-                        "--no-cpu-baseline", "--no-large"], capture_output=True, text=True, timeout=420, env=env)
+                        "--full", "--no-cpu-baseline", "--no-large"], capture_output=True, text=True, timeout=420, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["backend"] == "nccl" and line["rccl_ranks"] == 1 and line["population_gather_ms"] > 0 and line["value"] > 0
+
+
+def test_bench_plain_run_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: one timed block of exactly K iterations (W + K in all, as
+    the graph counters show), the headline line without the --full measurements, and the last step's outputs as float32 /
+    float64 arrays that two runs with the same arguments write identically."""
+    import json
+    import subprocess
+    import sys
+    REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    K, W = 300, 30
+    for k in range(2):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                            "--dump-outputs", str(tmp_path / f"out{k}")], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == K and line["warmup"] == W and line["timed_blocks"]["repeats"] == 1
+        assert line["graph"]["replayed_steps"] + line["graph"]["eager_steps"] == W + K
+        assert line["ms_per_step"] == pytest.approx(line["timed_blocks"]["ms_per_block"][0] / K, rel=1e-3)
+        assert line["value"] == pytest.approx(1e3 / line["ms_per_step"])
+        assert line["higher_is_better"] is True and line["unit"] == "steps/s" and line["dtype"] == "f32"
+        assert not {"roofline", "roofline_large", "value_reuse_grad", "cpu_baseline", "also"} & set(line), sorted(line)
+    names = sorted(os.listdir(tmp_path / "out0"))
+    assert names == sorted(os.listdir(tmp_path / "out1")) and {"state_idx.npy", "energy.npy", "best_energy.npy"} <= set(names)
+    out = {}
+    for f in names:
+        a, b = np.load(tmp_path / "out0" / f), np.load(tmp_path / "out1" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+        out[f[:-len(".npy")]] = a
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    assert out["state_idx"].shape == (128, 96) and out["state_idx"].min() >= 0 and out["state_idx"].max() <= 19
+    assert np.array_equal(out["energy"], out["energy_history_last"]) and np.all(out["best_energy"] >= out["energy"])
+    assert np.all(out["best_step"] <= W + K) and np.isfinite(out["best_energy"]).all()

@@ -54,24 +54,38 @@ def test_ground_truth_model(name):
 
 REAL = [("real_pabp.npz", "PABP_YEAST_Fields2013"), ("real_ube4b.npz", "UBE4B_MOUSE_Klevit2013-nscor_log2_ratio"),
         ("real_gfp.npz", "GFP_AEQVI_Sarkisyan2016")]
-REF_WEIGHTS = "/root/reference/weights"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_WEIGHTS), reason="the shipped weight files exist in the build container only")
 @pytest.mark.parametrize("name,protein", REAL)
-def test_real_shipped_weights(name, protein):
-    """The REAL onehot_cnn_seed=*.pt / *-linear.pkl / wt.fasta files of all three proteins, read by the product's
-    loaders (ppde_amd/weights.py) and evaluated by the oracle, against what the reference itself computed from those
-    files (fixture: file hashes + outputs, no weight values; synthetic couplings, the real potts.pkl is a missing blob).
-    Reads DATA files only; the reference's code is not imported here."""
+def test_real_shipped_weights(name, protein, tmp_path):
+    """The shipped weights of all three proteins, written back in the reference's file formats (onehot_cnn_seed=*.pt,
+    *-linear.pkl, wt.fasta) from the values frozen in tests/golden/real_<tag>_cnn.npz / real_<tag>_linear.npz, read by the
+    product's loaders (ppde_amd/weights.py) and evaluated by the oracle, against what the reference itself computed from
+    those files (fixture: file hashes + outputs; synthetic couplings, the real potts.pkl is a missing blob). Every file of
+    the fixture is accounted for by hash: wt.fasta byte for byte, the checkpoints through the hashes recorded with their
+    values. Reads DATA files only; the reference's code is not imported here."""
     import hashlib
+    import pickle
+    from helpers import real_cnn_states
     from ppde_amd import synthetic
     from ppde_amd.weights import load_cnn_states, load_linear, load_wt
     fx = load(name)
-    d = os.path.join(REF_WEIGHTS, protein)
-    for f, want in zip(fx["files"], fx["file_sha"]):
-        with open(os.path.join(d, str(f)), "rb") as fh:
-            assert hashlib.sha256(fh.read()).hexdigest() == str(want), f"{f} is not the file the fixture was generated on"
+    tag = name[len("real_"):-len(".npz")]
+    want = {str(f): str(h) for f, h in zip(fx["files"], fx["file_sha"])}
+    d = synthetic.write_weights_dir(str(tmp_path), protein, potts_seed=int(fx["potts_seed"]), cnn_seeds=(), linear_seeds=())
+    with open(os.path.join(d, "wt.fasta"), "rb") as fh:
+        assert hashlib.sha256(fh.read()).hexdigest() == want["wt.fasta"], "wt.fasta is not the file the fixture was generated on"
+    cnn, cnn_sha = real_cnn_states(tag)
+    pt = [f"onehot_cnn_seed={k}.pt" for k in range(len(cnn))]
+    assert cnn_sha == [want[f] for f in pt], f"real_{tag}_cnn.npz holds other checkpoints than the fixture was generated on"
+    for f, sd in zip(pt, cnn):
+        torch.save({"model": {k: torch.from_numpy(v) for k, v in sd.items()}}, os.path.join(d, f))
+    lin = load(f"real_{tag}_linear.npz")
+    pkl = [str(f) for f in lin["files"]]
+    assert [str(h) for h in lin["file_sha"]] == [want[f] for f in pkl], f"real_{tag}_linear.npz holds other models than the fixture was generated on"
+    assert set(want) == {"wt.fasta", *pt, *pkl}
+    for s, f in enumerate(pkl):
+        with open(os.path.join(d, f), "wb") as fh:
+            pickle.dump({"coef_": lin[f"seed{s}.coef_"], "intercept_": lin[f"seed{s}.intercept_"][()],
+                         "reg_coef": lin[f"seed{s}.reg_coef"].item()}, fh)
     seqs, wt_idx = load_wt(d)
     assert np.array_equal(wt_idx[0], fx["wt_idx"])
     Lp, i0 = int(fx["Lp"]), int(fx["win_start"])
