@@ -8,6 +8,7 @@ SRC = os.path.join(HERE, "csrc", "ppde_api.hip")
 DEPS = sorted(os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc")) if f.endswith((".hip", ".h"))) + \
        [os.path.join(os.path.dirname(HERE), "include", "ppde_hip.h")]
 OUT = os.path.join(HERE, "libppde_hip.so")
+OUT_EXACT = os.path.join(HERE, "libppde_hip_exact.so")      # -DCNN_SPLIT=3: the CNN's products as three fp16 terms (exact fp32 products)
 
 
 def hipcc():
@@ -17,10 +18,11 @@ def hipcc():
     return "hipcc"
 
 
-def is_stale():
-    if not os.path.exists(OUT):
+def is_stale(out=None):
+    out = out or OUT
+    if not os.path.exists(out):
         return True
-    t = os.path.getmtime(OUT)
+    t = os.path.getmtime(out)
     return any(os.path.getmtime(d) > t for d in DEPS)
 
 
@@ -34,6 +36,14 @@ def build(force=False, verbose=False, extra=(), out=None):
         print(" ".join(cmd))
     subprocess.run(cmd, check=True)
     return out
+
+
+def build_exact(force=False, verbose=False):
+    """The same library with the supervised CNN's exact three-term products (tests/test_cnn_ties_gpu.py loads it through
+    PPDE_HIP_LIB); same staleness rule as the default one."""
+    if not force and not is_stale(OUT_EXACT):
+        return OUT_EXACT
+    return build(force=True, verbose=verbose, extra=["-DCNN_SPLIT=3"], out=OUT_EXACT)
 
 
 if __name__ == "__main__":

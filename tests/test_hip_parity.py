@@ -74,18 +74,18 @@ def test_energy_grad_vs_reference_fixture(name):
     assert float(e_wt[0]) == 0.0
 
 
-def _check_trained(tag, fx, out, label):
+def _check_trained(tag, fx, out, label, prefix=""):
     """HIP outputs on the trained networks (dict f2 / e2 / g2 / e / fit / g) against what the REFERENCE computed from the
     same checkpoint files (real_<tag>.npz): SURVEY 8(c)'s tolerances, relative for values beyond 1."""
     lam = float(fx["lamda"])
     ftol = 4e-6 * np.maximum(1.0, np.abs(fx["supervised"]))
-    assert observed(f"real_{tag}{label}:supervised", np.abs(out["f2"] - fx["supervised"]), ftol) <= 1.0
+    assert observed(f"{prefix}real_{tag}{label}:supervised", np.abs(out["f2"] - fx["supervised"]), ftol) <= 1.0
     assert np.array_equal(out["e2"], out["f2"])
     gs = max(1.0, float(np.abs(fx["supervised_grad"]).max()))
-    assert observed(f"real_{tag}{label}:supervised_grad", np.abs(out["g2"] - fx["supervised_grad"]).max(), 2e-6 * gs) <= 1.0
-    assert observed(f"real_{tag}{label}:fit", np.abs(out["fit"] - fx["fit"]), ftol) <= 1.0
-    assert observed(f"real_{tag}{label}:e", np.abs(out["e"] - fx["e"]), e_tol(fx["e"], lam) + 4e-6 * lam * np.maximum(1.0, np.abs(fx["fit"]))) <= 1.0
-    assert observed(f"real_{tag}{label}:grad", np.abs(out["g"] - fx["grad"]).max(), 2e-6 * max(1.0, lam) * max(1.0, float(np.abs(fx["grad"]).max()))) <= 1.0
+    assert observed(f"{prefix}real_{tag}{label}:supervised_grad", np.abs(out["g2"] - fx["supervised_grad"]).max(), 2e-6 * gs) <= 1.0
+    assert observed(f"{prefix}real_{tag}{label}:fit", np.abs(out["fit"] - fx["fit"]), ftol) <= 1.0
+    assert observed(f"{prefix}real_{tag}{label}:e", np.abs(out["e"] - fx["e"]), e_tol(fx["e"], lam) + 4e-6 * lam * np.maximum(1.0, np.abs(fx["fit"]))) <= 1.0
+    assert observed(f"{prefix}real_{tag}{label}:grad", np.abs(out["g"] - fx["grad"]).max(), 2e-6 * max(1.0, lam) * max(1.0, float(np.abs(fx["grad"]).max()))) <= 1.0
 
 
 @pytest.mark.parametrize("tag", ["pabp", "ube4b", "gfp"])
@@ -196,12 +196,12 @@ def test_energy_grad_vs_oracle_batch_sizes(n):
     assert observed(f"batch{n}:e_vs_oracle", np.abs(e.cpu().numpy() - eo.numpy()), e_tol(eo.numpy(), 5.0)) <= 1.0
     assert np.abs(fit.cpu().numpy() - fo.numpy()).max() <= 5e-6
     # the max over t picks a row: a chain's routed gradient may differ from the oracle's only where the fp64 evaluation shows two
-    # rows tied to within matmul rounding, or a pre-activation at the ReLU kink (numerics contract)
-    from helpers import smallest_argmax_gap
-    dg = np.abs(g.cpu().numpy() - go.numpy()).reshape(n, -1).max(1)
-    tied = [b for b in np.nonzero(dg > 1e-5)[0] if smallest_argmax_gap(cnn, idx[b:b + 1]) < 5e-6]
-    assert len(tied) <= 2, tied
-    assert dg[np.setdiff1d(np.arange(n), tied)].max() <= 1e-5
+    # rows tied to within matmul rounding, or a pre-activation at the ReLU kink (numerics contract) -- and then it must
+    # be the gradient of another admissible routing, within the same tolerance (helpers.classify_chain_gradient)
+    from helpers import vet_gradient_outliers
+    _, gc = en.cnn.fit_grad(torch.as_tensor(idx.astype(np.int64)))
+    dg, unresolved = vet_gradient_outliers(g.cpu().numpy(), go.numpy(), gc.numpy(), cnn, idx, 1e-5, lamda=5.0, label=f"batch{n}")
+    assert dg[np.setdiff1d(np.arange(n), unresolved)].max() <= 1e-5
     # a chain's numbers do not depend on which batch it sits in
     e1, f1, g1 = m.energy_grad(torch.as_tensor(idx[:1]).cuda(), 3)
     assert torch.equal(e1, e[:1]) and torch.equal(f1, fit[:1]) and torch.equal(g1, g[:1])
@@ -452,6 +452,44 @@ def test_config2_composition_against_the_oracle():
     assert (res["fitness_history"] == 0).all()                                  # no supervised expert in this energy
     for reuse in (False, True):                                                 # the untraced, graph-replayed runs bench.py times
         ch3, _, res3 = _philox_run(m, n, T, pas, 0, False, i0, Lp, wt_idx, which=1, trace=False, reuse_grad=reuse, use_graph=True)
+        assert ch3.graph_stats()["replayed_steps"] == T
+        for k in ("energy_history", "fitness_history", "best_idx", "best_step", "random_traj"):
+            assert np.array_equal(res[k], res3[k]), (reuse, k)
+
+
+@pytest.mark.parametrize("weights", ["seeded", "trained"])
+def test_config3_composition_against_the_oracle(weights):
+    """BASELINE config 3 exactly as bench.py runs it -- 128 chains, Potts + supervised CNN product of experts (which = 3,
+    lamda = 5), PABP geometry, no mutation cap, device RNG: the fused experts launch and the chain kernels -- against the oracle
+    fed with the device's own noise (T = 20), on the seeded networks and on the shipped checkpoints' values. Draws, accept bits
+    and best states exact; energies at this file's e_tol + 4e-6 * lamda * max(1, |fit|); the untraced graph-replayed runs
+    bench.py times, under both evaluation policies, bit-equal to the traced run."""
+    fx, J, h, i0, wt_idx, cnn, m = _philox_setup()
+    lam = 5.0
+    if weights == "trained":
+        from helpers import real_pabp_cnn_states
+        cnn = real_pabp_cnn_states()[0]
+        m = hip_model(J, h, i0, wt_idx, cnn, lam)
+    n, T, pas, Lp = 128, 20, 2, J.shape[0]
+    ch, tr, res = _philox_run(m, n, T, pas, 0, False, i0, Lp, wt_idx, which=3, reuse_grad=False, use_graph=False)
+    from helpers import device_noise
+    noise = device_noise(ch, T, pas)
+    en = oracle_energy(J, h, i0, wt_idx, cnn, lam)
+    ref = orc.run(en, np.tile(wt_idx.astype(np.int64), (n, 1)), wt_idx, lambda t: noise[t], T, i0, i0 + Lp - 1, pas, 0, False, trace=True)
+    for t in range(T):
+        U = noise[t][0].numpy()
+        assert np.array_equal(tr["U"][t], U)
+        for s in range(int(U.max())):
+            act = s < U
+            assert np.array_equal(tr["flat"][t, s][act], ref["traces"][t]["flat"][s].numpy()[act]), (t, s)
+    assert np.array_equal(tr["accepted"].astype(bool), ref["accepted"].numpy())
+    assert np.array_equal(res["best_idx"], ref["best_idx"].numpy())
+    eh, fh = ref["energy_history"].numpy(), ref["fitness_history"].numpy()
+    assert observed(f"config3_composition_{weights}:energy_history", np.abs(res["energy_history"] - eh),
+                    e_tol(eh, lam) + 4e-6 * lam * np.maximum(1.0, np.abs(fh))) <= 1.0
+    assert observed(f"config3_composition_{weights}:fitness_history", np.abs(res["fitness_history"] - fh), 5e-6 * np.maximum(1.0, np.abs(fh))) <= 1.0
+    for reuse in (False, True):                                                 # the untraced, graph-replayed runs bench.py times
+        ch3, _, res3 = _philox_run(m, n, T, pas, 0, False, i0, Lp, wt_idx, which=3, trace=False, reuse_grad=reuse, use_graph=True)
         assert ch3.graph_stats()["replayed_steps"] == T
         for k in ("energy_history", "fitness_history", "best_idx", "best_step", "random_traj"):
             assert np.array_equal(res[k], res3[k]), (reuse, k)

@@ -7,7 +7,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import ppde_oracle as orc
-from helpers import smallest_argmax_gap, oracle_energy
+from helpers import oracle_energy, vet_gradient_outliers
 from test_hip_parity import e_tol, observed
 from ppde_amd import synthetic
 from ppde_amd.encoding import seqs_to_idx
@@ -54,12 +54,13 @@ def test_energy_grad_shapes(L, Lp, i0, with_cnn):
     assert observed(tag + ":e", np.abs(e.cpu().numpy() - eo_), e_tol(eo_) + 4e-6 * lam * np.maximum(1.0, np.abs(fo_))) <= 1.0
     assert observed(tag + ":fit", np.abs(f.cpu().numpy() - fo_), 5e-6 * np.maximum(1.0, np.abs(fo_))) <= 1.0
     # the max over t picks a row: where two rows tie to within matmul rounding the routed gradient is implementation-defined
-    # (numerics contract); a chain may differ only if the fp64 evaluation shows such a tie in it (the 300-residue
-    # case holds one: network 1, feature 413, rows 200 / 168, relative gap 4.5e-7)
+    # (numerics contract); a chain over the tolerance must then sit, within the same tolerance, on the gradient of
+    # another admissible routing (helpers.classify_chain_gradient; the 300-residue case holds such a chain: network 1, feature
+    # 413, rows 200 / 168, relative gap 4.5e-7). Only chains whose routing cannot be read off the gradient are left out.
     gtol = 2e-6 * max(1.0, lam) * max(1.0, float(np.abs(go_).max()))
-    dg = np.abs(g.cpu().numpy() - go_).reshape(idx.shape[0], -1).max(1)
-    tied = [b for b in np.nonzero(dg > gtol)[0] if with_cnn and smallest_argmax_gap(cnn, idx[b:b + 1]) < 5e-6]
-    keep = np.setdiff1d(np.arange(idx.shape[0]), tied)
+    gc = en.cnn.fit_grad(torch.as_tensor(idx.astype(np.int64)))[1].numpy() if with_cnn else None
+    dg, unresolved = vet_gradient_outliers(g.cpu().numpy(), go_, gc, cnn, idx, gtol, lamda=lam, label=tag)
+    keep = np.setdiff1d(np.arange(idx.shape[0]), unresolved)
     assert observed(tag + ":grad", dg[keep], gtol) <= 1.0, (dg, gtol)
 
 
@@ -120,10 +121,10 @@ def test_cnn_weight_magnitudes(L, enc, emb, dec, spread):
     fscale = max(float(np.abs(fo_).max()), 1e-30)
     gscale = max(float(np.abs(go_).max()), 1e-30)
     assert observed(tag + ":fit", np.abs(f.cpu().numpy() - fo_), 5e-6 * fscale) <= 1.0
-    dg = np.abs(g.cpu().numpy() - go_).reshape(idx.shape[0], -1).max(1)
-    tied = [b for b in np.nonzero(dg > 4e-6 * gscale)[0] if smallest_argmax_gap(cnn, idx[b:b + 1]) < 5e-6]
-    keep = np.setdiff1d(np.arange(idx.shape[0]), tied)
-    assert len(tied) <= 2 and observed(tag + ":grad", dg[keep], 4e-6 * gscale) <= 1.0, (dg / gscale, tied)
+    # (which = 2: the gradient is d fit / d x itself; a chain over the tolerance must sit on another admissible vertex)
+    dg, unresolved = vet_gradient_outliers(g.cpu().numpy(), go_, go_, cnn, idx, 4e-6 * gscale, lamda=1.0, label=tag)
+    keep = np.setdiff1d(np.arange(idx.shape[0]), unresolved)
+    assert observed(tag + ":grad", dg[keep], 4e-6 * gscale) <= 1.0, (dg / gscale, unresolved)
 
 
 @pytest.mark.parametrize("L,Lp,i0,n,with_cnn", [(237, 237, 0, 24, False), (237, 237, 0, 6, True), (104, 76, 23, 20, True),
@@ -329,7 +330,10 @@ def test_repeated_evaluations_are_bit_identical(protein, reps):
     assert np.abs(f0 - fo.numpy()).max() <= 5e-6
     dg = np.abs(g0 - go.numpy()).reshape(n, -1).max(1)
     gtol = 2e-6 * 5.0 * max(1.0, float(go.abs().max()))
-    assert (dg > gtol).sum() <= 2, dg.max()                     # (up to two chains may sit on an exact arg-max tie: DESIGN.md section 5)
+    # (a chain over the tolerance must sit on the gradient of another admissible routing of a NEAR tie: DESIGN.md section 5)
+    gc = en.cnn.fit_grad(torch.as_tensor(idx.astype(np.int64)))[1].numpy()
+    dg, unresolved = vet_gradient_outliers(g0, go.numpy(), gc, cnn, idx, gtol, lamda=5.0, label=f"repeat_{protein}")
+    assert dg[np.setdiff1d(np.arange(n), unresolved)].max() <= gtol
     for rep in range(reps):
         e, f, g = [t.cpu().numpy() for t in m.energy_grad(x, 3)]
         assert np.array_equal(e, e0) and np.array_equal(f, f0) and np.array_equal(g, g0), rep
