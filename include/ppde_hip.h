@@ -193,6 +193,22 @@ typedef struct {
 int ppde_chains_create(ppde_chains** out, ppde_model* m, const ppde_chain_config* cfg);
 int ppde_chains_destroy(ppde_chains* c);
 
+/* Design library: allowed_host [L], one word per residue of the full sequence; bit k set = letter k (alphabet
+ * ACDEFGHIKLMNPQRSTVWY) may be PROPOSED at that residue, word 0 = the residue is frozen. Enforced exactly inside the
+ * forward path of every iteration (ppde.py:98-110), next to the position range (ppde.py:60-63) and the mutation cap:
+ *   z[l,k] = -inf where forbidden; p = clamp(softmax(z), 2^-23, 1 - 2^-23) (ppde/utils.py:106-111); p[l,k] = 0 where
+ *   forbidden, before any sum of p is formed; p_hat = p / sum(p); draw; log-probability = log clamp(p_hat[win]).
+ * So a forbidden entry can never be drawn, while entries masked only by the range or the cap keep the reference's
+ * 2^-23 floor (the range alone is no hard limit: about 1.2e-7 per masked entry and draw). The reverse path takes no
+ * masks, as the reference treats its own two; Philox counters and the variates consumed do not change; a library of
+ * all twenty letters everywhere gives the bits of no library. It constrains moves only: initial states need not lie
+ * inside it. "No admissible move" (nothing unmasked and allowed) is flagged PPDE_ERR_NUMERIC as without a library.
+ * Valid between ppde_chains_create and ppde_chains_init (the graphs captured there hold the pointer): afterwards
+ * PPDE_ERR_INVALID. NULL clears the library. PPDE_ERR_INVALID with a message when a bit >= 20 is set, when an open
+ * residue lacks its wild-type letter (the mutation cap's revert move must stay admissible), or when no residue of
+ * [min_pos, max_pos] is open. The words are copied; the chains own the device copy. */
+int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host /* [L] or NULL */);
+
 /* Start from idx0_dev [n, L] (ppde.py:35-47): evaluates the initial energies, fills history row 0. */
 int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev);
 

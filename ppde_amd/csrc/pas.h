@@ -72,6 +72,9 @@ struct PasArgs {
     int* tr_U;                  // [T][n]
     int* err_flag;
     unsigned long long* dbg;    // stamp buffer (diagnostic build)
+    // design library (ppde_chains_set_library): allowed[l] bit k = letter k may be PROPOSED at residue l, word 0 = frozen; NULL
+    // = no library. Forward paths only (ppde.py:98-110); the reverse path takes no masks, as the reference treats its own two.
+    const uint32_t* allowed;    // [L]
 };
 
 // LDS of a chain workgroup: the gradient row (float4[N/4]), the letters of the start state and of the wild
@@ -106,6 +109,7 @@ struct RowLds {
     uint8_t* Wt;    // wild-type letters         [L]
     float4* Pv;     // clamped probabilities of the current sub-step [N/4]          (two-level draw, device RNG)
     float* qv;      // reciprocal race variates of PAS_QS sub-steps [PAS_QS][LQ]     (two-level draw, device RNG)
+    uint32_t* Al;   // design library words [L]: only the *_lib kernels are launched with room for them (pas_lib_lds_bytes)
 };
 // sub-steps of race variates parked in LDS at a time (two-level draw); row = 4*ceil(L/4) residue entries + 20 letter entries
 #define PAS_QS 4
@@ -122,11 +126,15 @@ __device__ __forceinline__ RowLds carve_lds(unsigned char* base, const Geom& g) 
     r.Wt = r.St + ((g.L + 15) & ~15);
     r.Pv = (float4*)(r.Wt + ((g.L + 15) & ~15));
     r.qv = (float*)(r.Pv + g.N / 4);
+    r.Al = (uint32_t*)(r.qv + PAS_QS * pas_lq(g.L));
     return r;
 }
 __host__ __device__ inline size_t pas_lds_bytes(const Geom& g) {
     return (size_t)g.N * 4 + 16 * PPDE_NW * 4 + 1024 + 2 * (size_t)((g.L + 15) & ~15) + (size_t)g.N * 4 + (size_t)PAS_QS * pas_lq(g.L) * 4;
 }
+
+// what a launch with a design library adds behind pas_lds_bytes (launches without one keep their size)
+__host__ __device__ inline size_t pas_lib_lds_bytes(const Geom& g) { return (size_t)((g.L + 3) & ~3) * 4; }
 
 // a state byte in both forms: the row (CNN, chain kernels) and, for residues of the padded Potts window, its T4 slot
 __device__ __forceinline__ void store_letter(uint8_t* rows, uint8_t* T, const Geom& g, int n_pad, int b, int l, uint8_t v) {
@@ -592,8 +600,11 @@ __device__ __forceinline__ void reverse_rows_dev(const RowLds& lds, RowRegs<GPT>
 }
 
 // logits of one 4-letter group of residue l: (g - g[current letter]) / 2 with the forward masks
+// LIB: ok4 = the design library's bits of these four letters; a forbidden letter's logit is -inf like a masked one's, and
+// (unlike a masked one) its probability is zeroed again behind the clamp by the callers
+template <bool LIB = false>
 __device__ __forceinline__ float4 forward_logits(const PasArgs& a, const float* G, float4 gv, int l, int kb, int cur, int wt,
-                                                 bool capped) {
+                                                 bool capped, uint32_t ok4 = 15u) {
     const float gc = G[l * 20 + cur];
     float4 z = make_float4((gv.x - gc) * 0.5f, (gv.y - gc) * 0.5f, (gv.z - gc) * 0.5f, (gv.w - gc) * 0.5f);
     const bool outside = (l < a.min_pos) | (l > a.max_pos);
@@ -604,6 +615,12 @@ __device__ __forceinline__ float4 forward_logits(const PasArgs& a, const float* 
     if (outside | (capped & !(revertible & (kw == 1)))) z.y = -INFINITY;
     if (outside | (capped & !(revertible & (kw == 2)))) z.z = -INFINITY;
     if (outside | (capped & !(revertible & (kw == 3)))) z.w = -INFINITY;
+    if constexpr (LIB) {
+        if (!(ok4 & 1u)) z.x = -INFINITY;
+        if (!(ok4 & 2u)) z.y = -INFINITY;
+        if (!(ok4 & 4u)) z.z = -INFINITY;
+        if (!(ok4 & 8u)) z.w = -INFINITY;
+    }
     return z;
 }
 
@@ -687,7 +704,9 @@ __device__ __forceinline__ ProposePrefetch<GPT> propose_prefetch(const PasArgs& 
 // holding the current letters, `dist` = mutation count of that state.
 // EXACT: the race compares p / q with an IEEE division, as torch.multinomial does (replay of caller-supplied noise,
 // rng_mode 0); otherwise p * rcp(q) (device RNG).
-template <int GPT, bool EXACT>
+// LIB: a design library is staged in lds.Al: forbidden entries take logit -inf, probability exactly 0 behind the clamp (before
+// the row sum S3 is formed) and never enter the race.
+template <int GPT, bool EXACT, bool LIB = false>
 __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int b, int it, int dist0,
                                              const ProposePrefetch<GPT>& pp, bool stamp) {
     int dist = dist0;
@@ -701,6 +720,12 @@ __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds
 #pragma unroll
     for (int r = 0; r < GPT; ++r) q[r] = pp.q0[r];
 
+    uint32_t ok4[GPT];                               // the library's bits of each group's four letters (fixed along the path)
+#pragma unroll
+    for (int r = 0; r < GPT; ++r) {
+        ok4[r] = 15u;
+        if constexpr (LIB) ok4[r] = (lds.Al[R.l[r]] >> R.kb[r]) & 15u;
+    }
     int pend_l = 0, pend_k = 0;                      // the last move, not yet applied to lds.St
     constexpr bool exact_race = EXACT;             // (a compile-time switch: as a run-time branch in this loop it cost k_propose 0.55 us)
     for (int s = 0; s < Ub; ++s) {
@@ -708,7 +733,7 @@ __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds
         // ---- logits z = (g - g[current letter]) / 2 with the forward masks (ppde.py:98-104)
         float4 z[GPT];
 #pragma unroll
-        for (int r = 0; r < GPT; ++r) z[r] = forward_logits(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], capped);
+        for (int r = 0; r < GPT; ++r) z[r] = forward_logits<LIB>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], capped, ok4[r]);
         PPDE_STAMP(a.dbg, 10 + 4 * min(s, 1), stamp);
         float m, S1, scale;
         float4 e[GPT];
@@ -735,6 +760,12 @@ __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds
             const int g4 = tid + r * PPDE_BLOCK;
             float4 p;
             p.x = clampp(e[r].x * c); p.y = clampp(e[r].y * c); p.z = clampp(e[r].z * c); p.w = clampp(e[r].w * c);
+            if constexpr (LIB) {                    // a forbidden entry loses the clamp's floor again: exactly 0 in every sum
+                if (!(ok4[r] & 1u)) p.x = 0.f;
+                if (!(ok4[r] & 2u)) p.y = 0.f;
+                if (!(ok4[r] & 4u)) p.z = 0.f;
+                if (!(ok4[r] & 8u)) p.w = 0.f;
+            }
             s3 += p.x; s3 += p.y; s3 += p.z; s3 += p.w;
             // race value p / q (torch.multinomial: arg-max of probs / q with an IEEE division). Replaying the reference's
             // noise (rng_mode 0) keeps the division, so a near-tie resolves as it does there; on the device RNG, where no
@@ -744,6 +775,12 @@ __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds
             else {
                 vx = p.x * __builtin_amdgcn_rcpf(q[r].x); vy = p.y * __builtin_amdgcn_rcpf(q[r].y);
                 vz = p.z * __builtin_amdgcn_rcpf(q[r].z); vw = p.w * __builtin_amdgcn_rcpf(q[r].w);
+            }
+            if constexpr (LIB) {                    // ... and stays out of the race (0 / q = 0 would still beat the initial -1)
+                if (!(ok4[r] & 1u)) vx = -1.f;
+                if (!(ok4[r] & 2u)) vy = -1.f;
+                if (!(ok4[r] & 4u)) vz = -1.f;
+                if (!(ok4[r] & 8u)) vw = -1.f;
             }
             if (vx > bv) { bv = vx; bi = 4 * g4; bp = p.x; }
             if (vy > bv) { bv = vy; bi = 4 * g4 + 1; bp = p.y; }
@@ -853,7 +890,13 @@ __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds
 //    The two races draw exactly the reference's categorical: P(l*, k*) = P_l / S3 * p[l*][k*] / P_l.
 //  * The other seven waves wait at the closing barrier; then every thread writes its letters of the proposal from LDS and the
 //    winners' log-probabilities (a division and a logarithm each) are evaluated one sub-step per thread.
-template <int GPT>
+//  * LIB: a design library is staged in lds.Al. A forbidden entry's exponential is 0 (logit -inf), its clamped probability is set
+//    to exactly 0 before the residue masses are formed (same summation tree), and it takes no part in the letter race; a frozen
+//    residue (mass 0) takes no part in the residue race. The lanes of wave 0 keep their residues' words in registers. `mref`
+//    is KEPT as row_commit derives it (the spread over the position range, library ignored): forbidden entries only go to
+//    -inf, so it still bounds every logit from above; narrowing it to the open entries would change nothing a run can see but
+//    the rounding of the exponentials, and would break the bit-equality of an all-letters library with no library.
+template <int GPT, bool LIB = false>
 __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int b, int it, int dist0,
                                                  const ProposePrefetch<GPT>& pp, bool stamp, const float mref) {
     int dist = dist0;
@@ -873,7 +916,9 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
 #pragma unroll
         for (int r = 0; r < GPT; ++r) {
             if (!R.valid[r]) continue;
-            const float4 z = forward_logits(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], capped);
+            uint32_t ok4 = 15u;
+            if constexpr (LIB) ok4 = (lds.Al[R.l[r]] >> R.kb[r]) & 15u;
+            const float4 z = forward_logits<LIB>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], capped, ok4);
             lds.Pv[tid + r * PPDE_BLOCK] = make_float4(expf(z.x - mref), expf(z.y - mref), expf(z.z - mref), expf(z.w - mref));
         }
     }
@@ -886,7 +931,8 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
         auto letter_exp = [&](int l, int k, int cur, int wt, bool capped) {
             const bool outside = (l < a.min_pos) | (l > a.max_pos);
             const bool revertible = capped & (cur != wt);
-            const bool masked = outside | (capped & !(revertible & (k == wt)));
+            bool masked = outside | (capped & !(revertible & (k == wt)));
+            if constexpr (LIB) masked |= !((lds.Al[l] >> k) & 1u);      // forbidden by the design library
             const float z = (G[l * 20 + k] - G[l * 20 + cur]) * 0.5f;
             return masked ? 0.f : expf(z - mref);
         };
@@ -894,6 +940,12 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
         // authoritative copy: the letter race and the lanes that re-evaluate a residue use it); S1 is their total.
         constexpr int NRES = (GPT * PPDE_BLOCK * 4 / PPDE_A + 63) / 64;      // residues per lane: 2 / 4 / 5 for GPT = 1 / 2 / 3
         float4 ev[NRES][5];
+        uint32_t aw[NRES];                            // ... and their library words (fixed for the launch)
+#pragma unroll
+        for (int r = 0; r < NRES; ++r) {
+            aw[r] = 0xfffffu;
+            if constexpr (LIB) aw[r] = lds.Al[min(lane + 64 * r, g.L - 1)];
+        }
         auto load_res = [&](int r) {
             const float4* pe = lds.Pv + 5 * min(lane + 64 * r, g.L - 1);
             ev[r][0] = lds_load4(pe); ev[r][1] = lds_load4(pe + 1); ev[r][2] = lds_load4(pe + 2); ev[r][3] = lds_load4(pe + 3); ev[r][4] = lds_load4(pe + 4);
@@ -955,12 +1007,20 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
                 for (int i = 0; i < 5; ++i) {
                     p[i].x = __builtin_amdgcn_fmed3f(ev[r][i].x * c, PPDE_EPS, 1.0f - PPDE_EPS); p[i].y = __builtin_amdgcn_fmed3f(ev[r][i].y * c, PPDE_EPS, 1.0f - PPDE_EPS);
                     p[i].z = __builtin_amdgcn_fmed3f(ev[r][i].z * c, PPDE_EPS, 1.0f - PPDE_EPS); p[i].w = __builtin_amdgcn_fmed3f(ev[r][i].w * c, PPDE_EPS, 1.0f - PPDE_EPS);
+                    if constexpr (LIB) {             // forbidden: exactly 0, before the residue mass is formed
+                        const uint32_t o = aw[r] >> (4 * i);
+                        if (!(o & 1u)) p[i].x = 0.f;
+                        if (!(o & 2u)) p[i].y = 0.f;
+                        if (!(o & 4u)) p[i].z = 0.f;
+                        if (!(o & 8u)) p[i].w = 0.f;
+                    }
                 }
                 const float4 t = add4(add4(add4(p[0], p[1]), add4(p[2], p[3])), p[4]);
                 const float P = (t.x + t.y) + (t.z + t.w);
                 if (l < g.L) {
                     s3 += P;
-                    const float v = P * rq;
+                    float v = P * rq;
+                    if constexpr (LIB) { if (!(P > 0.f)) v = -1.f; }   // a frozen residue never enters the race
                     if (v > bv) { bv = v; bl = l; }  // (strict >, ascending l: the first index wins a tie)
                 }
             }
@@ -970,9 +1030,15 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
             const int ls = min(__builtin_amdgcn_readlane(bl, wl), g.L - 1);
             // (d) the letter inside the winning residue (lane = letter)
             const int kl = min(lane, PPDE_A - 1);
-            const float pk = __builtin_amdgcn_fmed3f(E[ls * PPDE_A + kl] * c, PPDE_EPS, 1.0f - PPDE_EPS);
+            float pk = __builtin_amdgcn_fmed3f(E[ls * PPDE_A + kl] * c, PPDE_EPS, 1.0f - PPDE_EPS);
+            bool in_race = lane < PPDE_A;
+            if constexpr (LIB) {
+                const bool ok = (lds.Al[ls] >> kl) & 1u;
+                if (!ok) pk = 0.f;
+                in_race &= ok;
+            }
             float vk;
-            const int ks = wave_argmax_lane(lane < PPDE_A ? pk * qs[RB4 + kl] : -1.f, lane, vk);
+            const int ks = wave_argmax_lane(in_race ? pk * qs[RB4 + kl] : -1.f, lane, vk);
             const float pw = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, pk), ks));
             const int win = ls * PPDE_A + ks;
             PPDE_STAMP(a.dbg, 12 + 4 * min(s, 1), stamp);
@@ -1010,8 +1076,19 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
     PPDE_STAMP(a.dbg, 19, stamp);
 }
 
-template <int GPT, bool EXACT, int SPEC = 0>
-__global__ __launch_bounds__(PPDE_BLOCK) void k_propose(PasArgs a) {
+// Loads this thread's word of the design library (issued with the row's loads), to be parked in lds.Al before row_commit's barrier
+template <bool LIB>
+__device__ __forceinline__ uint32_t library_issue(const PasArgs& a) {
+    if constexpr (LIB) return a.allowed[min((int)threadIdx.x, a.g.L - 1)];
+    return 0u;
+}
+template <bool LIB>
+__device__ __forceinline__ void library_stage(const PasArgs& a, const RowLds& lds, uint32_t w) {
+    if constexpr (LIB) { if ((int)threadIdx.x < a.g.L) lds.Al[threadIdx.x] = w; }
+}
+
+template <int GPT, bool EXACT, int SPEC, bool LIB>
+__device__ __forceinline__ void propose_kernel(PasArgs& a) {
     args_up_front(a);
     pin_config<SPEC>(a);
     extern __shared__ unsigned char smem_raw[];
@@ -1022,12 +1099,19 @@ __global__ __launch_bounds__(PPDE_BLOCK) void k_propose(PasArgs a) {
     RowRegs<GPT> R;
     const int it = iteration_of(a);
     const RowLetters<GPT> rl = row_issue<GPT>(a.g, current_grad_row(a, b), a.cur + (size_t)b * a.g.Ls, a.wt, R);
+    const uint32_t lw = library_issue<LIB>(a);
     const ProposePrefetch<GPT> pp = propose_prefetch<GPT, EXACT>(a, lds, b, it);
+    library_stage<LIB>(a, lds, lw);
     const float mref = row_commit<GPT, !EXACT>(lds, a.g, rl, R, a.min_pos, a.max_pos);
     PPDE_STAMP(a.dbg, 9, stamp);
-    if constexpr (EXACT) propose_body<GPT, true>(a, lds, R, b, it, __builtin_amdgcn_readfirstlane(pp.dist), pp, stamp);
-    else propose_body_dev<GPT>(a, lds, R, b, it, __builtin_amdgcn_readfirstlane(pp.dist), pp, stamp, mref);
+    if constexpr (EXACT) propose_body<GPT, true, LIB>(a, lds, R, b, it, __builtin_amdgcn_readfirstlane(pp.dist), pp, stamp);
+    else propose_body_dev<GPT, LIB>(a, lds, R, b, it, __builtin_amdgcn_readfirstlane(pp.dist), pp, stamp, mref);
 }
+template <int GPT, bool EXACT, int SPEC = 0>
+__global__ __launch_bounds__(PPDE_BLOCK) void k_propose(PasArgs a) { propose_kernel<GPT, EXACT, SPEC, false>(a); }
+// with a design library (PasArgs::allowed != NULL): the general kernel only, launched with pas_lib_lds_bytes more LDS
+template <int GPT, bool EXACT>
+__global__ __launch_bounds__(PPDE_BLOCK) void k_propose_lib(PasArgs a) { propose_kernel<GPT, EXACT, 0, true>(a); }
 
 // ------------------------------------------------------------------------------------------------
 // energy of slot `slot` for chain b (all lanes of the calling wave get the value)
@@ -1283,8 +1367,8 @@ __global__ __launch_bounds__(PPDE_BLOCK) void k_accept(PasArgs a) {
 // Accept phase of iteration `it` and forward path of iteration `it + 1` in one launch (gradient reuse only): an
 // accepted chain already has its next gradient row staged; a rejected / reset chain re-stages the row it falls
 // back to. Saves a launch boundary and a row staging per iteration.
-template <int GPT, int SPEC = 0>
-__global__ __launch_bounds__(PPDE_BLOCK) void k_accept_propose(PasArgs a) {
+template <int GPT, int SPEC, bool LIB>
+__device__ __forceinline__ void accept_propose_kernel(PasArgs& a) {
     args_up_front(a);
     pin_config<SPEC>(a);
     a.reuse = 1; a.rng_mode = 1;                     // (this kernel exists for gradient reuse on the device RNG only)
@@ -1297,9 +1381,11 @@ __global__ __launch_bounds__(PPDE_BLOCK) void k_accept_propose(PasArgs a) {
     PPDE_STAMP(a.dbg, 24, stamp);
     RowRegs<GPT> R;
     const RowLetters<GPT> rl = row_issue<GPT>(g, slot_row(a, 1, b), a.cur + (size_t)b * g.Ls, a.wt, R);
+    const uint32_t lw = library_issue<LIB>(a);
     const AcceptPrefetch pf = accept_prefetch(a, lds, b, it);
     const ProposePrefetch<GPT> pp = propose_prefetch<GPT, false>(a, lds, b, it + 1);
     accept_stage_path(a, lds, pf);
+    library_stage<LIB>(a, lds, lw);                  // (the accept phase never reads it: no masks on the way back)
     const float mref_y = row_commit<GPT, true>(lds, g, rl, R, 0, g.L - 1);
     const AcceptOut o = accept_body<GPT, true>(a, lds, R, b, it, pf, stamp, mref_y);
     // ---- the state and gradient the chain continues from
@@ -1338,8 +1424,12 @@ __global__ __launch_bounds__(PPDE_BLOCK) void k_accept_propose(PasArgs a) {
         mref = fminf(fmaxf((row8_max(xa) + row8_max(xb)) * 0.5f, 0.f), 64.f);
     }
     __syncthreads();
-    propose_body_dev<GPT>(a, lds, R, b, it + 1, o.dist, pp, stamp, mref);   // (fused launches exist on the device RNG only)
+    propose_body_dev<GPT, LIB>(a, lds, R, b, it + 1, o.dist, pp, stamp, mref);   // (fused launches exist on the device RNG only)
 }
+template <int GPT, int SPEC = 0>
+__global__ __launch_bounds__(PPDE_BLOCK) void k_accept_propose(PasArgs a) { accept_propose_kernel<GPT, SPEC, false>(a); }
+template <int GPT>
+__global__ __launch_bounds__(PPDE_BLOCK) void k_accept_propose_lib(PasArgs a) { accept_propose_kernel<GPT, 0, true>(a); }
 
 // history row 0 and the running best from the initial population (ppde.py:38-47): one wave per chain
 __global__ void k_init_chain(PasArgs a) {

@@ -1131,6 +1131,7 @@ struct ppde_chains {
     int n_captures = 0, n_captures_in_run = 0;   // graphs captured in all / inside ppde_chains_run (must stay 0)
     long long n_replayed_steps = 0, n_eager_steps = 0;
     std::vector<void*> allocs;
+    uint32_t* allowed = nullptr;                 // design library [L] (ppde_chains_set_library), owned here; NULL = none
 };
 
 static PasArgs chain_args(const ppde_chains* c) {
@@ -1155,6 +1156,7 @@ static PasArgs chain_args(const ppde_chains* c) {
     a.tr_flat = c->tr_flat; a.tr_acc = c->tr_acc; a.tr_logacc = c->tr_logacc; a.tr_U = c->tr_U;
     a.err_flag = c->err_flag;
     a.dbg = c->dbg;
+    a.allowed = c->allowed;
     return a;
 }
 
@@ -1171,7 +1173,10 @@ enum ChainKernel { KP_PROPOSE, KP_ACCEPT, KP_ACCEPT_PROPOSE };
 
 static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs& a, int n_sub, hipStream_t s) {
     const ppde_model* m = c->m;
-    const size_t lds = pas_lds_bytes(m->g);
+    // a run with a design library: the forward paths go to the general *_lib kernels with room for the words in LDS; the
+    // accept kernel (no masks on the way back) and every run without a library keep their instantiations and LDS size
+    const bool lib = a.allowed != nullptr && which != KP_ACCEPT;
+    const size_t lds = pas_lds_bytes(m->g) + (lib ? pas_lib_lds_bytes(m->g) : 0);
     const int gpt = (m->g.N / 4 + PPDE_BLOCK - 1) / PPDE_BLOCK;
     // specialised instantiation for the common configurations (pas.h pin_config), the general kernel otherwise
     static const bool spec_on = []() { const char* e = getenv("PPDE_CHAIN_SPEC"); return !e || atoi(e) != 0; }();   // tuning knob
@@ -1203,6 +1208,12 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
                         else hipLaunchKernelGGL(K, dim3(n_sub), dim3(PPDE_BLOCK), lds, s, a); } while (0)
     with_gpt([&](auto G) {
         constexpr int GP = decltype(G)::value;
+        if (lib) {
+            if (which == KP_ACCEPT_PROPOSE) PPDE_CL((k_accept_propose_lib<GP>));
+            else if (a.rng_mode == 0) PPDE_CL((k_propose_lib<GP, true>));
+            else PPDE_CL((k_propose_lib<GP, false>));
+            return;
+        }
         if (which == KP_PROPOSE && a.rng_mode == 0) {
             PPDE_CL((k_propose<GP, true, 0>));
             return;
@@ -1414,11 +1425,45 @@ int ppde_chains_destroy(ppde_chains* c) {
         if (gs.graph) hipGraphDestroy(gs.graph);
     }
     for (void* p : c->allocs) hipFree(p);
+    if (c->allowed) hipFree(c->allowed);
     delete c->tfw;
     if (c->h_err) hipHostFree(c->h_err);
     for (hipStream_t st : c->streams) if (st) hipStreamDestroy(st);
     for (hipEvent_t ev : c->events) if (ev) hipEventDestroy(ev);
     delete c;
+    return PPDE_OK;
+}
+
+int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_library: the library must be set before ppde_chains_init (its graphs hold the pointer)");
+    const ppde_model* m = c->m;
+    HIPCHK(hipSetDevice(c->device));
+    if (!allowed_host) {                            // clear
+        if (c->allowed) { hipFree(c->allowed); c->allowed = nullptr; }
+        return PPDE_OK;
+    }
+    int open_in_range = 0;
+    for (int l = 0; l < m->L; ++l) {
+        const uint32_t w = allowed_host[l];
+        if (w >> PPDE_A)
+            return fail(PPDE_ERR_INVALID, "design library: residue " + std::to_string(l) + " has a bit >= 20 set (20 letters)");
+        if (w && !((w >> m->h_wt[l]) & 1u))          // (the mutation cap's only move is the revert to the wild type)
+            return fail(PPDE_ERR_INVALID, "design library: open residue " + std::to_string(l) + " lacks its wild-type letter");
+        if (w && l >= c->cfg.min_pos && l <= c->cfg.max_pos) open_in_range++;
+    }
+    if (!open_in_range)
+        return fail(PPDE_ERR_INVALID, "design library: no open residue in [min_pos, max_pos] = [" + std::to_string(c->cfg.min_pos) +
+                                      ", " + std::to_string(c->cfg.max_pos) + "]");
+    uint32_t* d = nullptr;
+    HIPCHK(dalloc(&d, (size_t)m->L));
+    hipError_t e = hipMemcpy(d, allowed_host, (size_t)m->L * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(d);
+        return fail(PPDE_ERR_HIP, std::string("design library upload: ") + hipGetErrorString(e));
+    }
+    if (c->allowed) hipFree(c->allowed);
+    c->allowed = d;
     return PPDE_OK;
 }
 

@@ -19,6 +19,11 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         separate HIP streams and overlap on the GPU (independent chains: results unchanged).
     ppde_cpu_alias      False (default): state histories hold the pre-reset state (reference on cuda);
                         True reproduces the reference's `--device cpu` aliasing artefact.
+    ppde_library        None (default), or a design library: uint32 [L] / bool [L, 20] of the letters that may be proposed at
+                        each residue (ppde_amd/library.py). Enforced exactly inside the proposal kernels; every site outside
+                        [min_pos, max_pos] is frozen in it and the chains run over the full range, so nothing in such a run
+                        relies on the range mask (which leaks 2^-23 per masked entry, as in the reference). Every rank of a
+                        sharded run passes the same library.
     ppde_shard          False (default). True with torch.distributed initialised: chains are split over ranks
                         and gathered at the end (one RCCL all_gather); every rank returns the full result.
 """
@@ -29,7 +34,7 @@ import time
 import numpy as np
 import torch
 
-from . import _hip
+from . import _hip, library as design_library
 from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
@@ -64,6 +69,14 @@ class Chains:
             self.close()
         except Exception:
             pass
+
+    def set_library(self, mask):
+        """Design library for the forward proposals: uint32 [L] (bit k = letter k allowed, 0 = frozen) or bool [L, 20]; None
+        clears it. Only before init() (the graphs captured there hold the device copy's address)."""
+        words = None if mask is None else design_library.as_words(mask, self.model.L)
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_set_library(self.handle, _hip.ptr(words)))
+        self.library = words
 
     def init(self, idx0):
         idx0 = idx0.to(self.model.device, torch.uint8).contiguous()
@@ -177,6 +190,7 @@ class PPDE_PAS(BaseSampler):
         self.cpu_alias = getattr(args, "ppde_cpu_alias", False)
         self.shard = getattr(args, "ppde_shard", False)
         self.trace = getattr(args, "ppde_trace", False)
+        self.library = getattr(args, "ppde_library", None)
         self.noise_bytes = getattr(args, "ppde_noise_bytes", 96 << 20)   # host->device noise is uploaded in chunks of about this size
         self.last_chains = None
         self.timings = {}       # seconds of the last run(): setup (chains + hipGraph capture), iterations, log path, collect
@@ -210,11 +224,19 @@ class PPDE_PAS(BaseSampler):
                   "another trajectory.", file=sys.stderr, flush=True)
         t_begin = time.perf_counter()
         t_log = 0.0
-        chains = Chains(model, n, num_steps, self.ppde_pas_length, self.nmut_threshold, self.paper_results, min_pos,
-                        max_pos, energy_function.which, 0 if self.rng == "torch" else 1, self.reuse_grad, self.cpu_alias,
+        lib_words = None
+        if self.library is not None:
+            # the range goes INTO the library (exact) and the chains run over the full range: no entry of a library run is
+            # masked by the leaky range mask. The same words on every rank.
+            lib_words = design_library.fold_range(design_library.as_words(self.library, L), min_pos, max_pos)
+        chains = Chains(model, n, num_steps, self.ppde_pas_length, self.nmut_threshold, self.paper_results,
+                        0 if lib_words is not None else min_pos,
+                        L - 1 if lib_words is not None else max_pos, energy_function.which, 0 if self.rng == "torch" else 1, self.reuse_grad, self.cpu_alias,
                         self.trace, random_idx - lo if lo <= random_idx < hi else -1, self.use_graph, seed, lo,
                         self.n_streams)
         self.last_chains = chains
+        if lib_words is not None:
+            chains.set_library(lib_words)
         chains.init(idx0[lo:hi])
 
         def gathered(a):

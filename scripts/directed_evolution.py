@@ -10,7 +10,7 @@ transformer-L | potts+transformer` (the ESM-2 checkpoint must be in <hub_dir>/ch
 the MSA-Transformer scoring are out of scope.
 
 Extra flags: --ppde_rng {torch,philox}, --ppde_seed, --ppde_reuse_grad {0,1}, --ppde_shard (with torchrun), --ppde_full_grad,
---ppde_timing.
+--ppde_timing; design library (the letters the sampler may propose per residue): --ppde_sites, --ppde_exclude, --ppde_library.
 """
 import argparse
 import datetime
@@ -27,17 +27,36 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 torch.set_printoptions(threshold=5000)
 
-from ppde_amd.encoding import read_fasta, seqs_to_onehot  # noqa: E402
+from ppde_amd import library as design_library  # noqa: E402
+from ppde_amd.encoding import read_fasta, seqs_to_idx, seqs_to_onehot  # noqa: E402
 from ppde_amd.energy import ProteinProductOfExperts, ProteinSupervised  # noqa: E402
 from ppde_amd.nets import AugmentedLinearRegression, proteins_potts_score  # noqa: E402
 from ppde_amd.sampler import PPDE_PAS  # noqa: E402
 
 
-def get_sampler(args):
+def get_sampler(args, library=None):
     if args.sampler == "PPDE":
-        return PPDE_PAS(args)
+        # (a copy: the namespace itself is what config.txt records, and a mask is no JSON)
+        return PPDE_PAS(argparse.Namespace(**{**vars(args), "ppde_library": library}))
     raise NotImplementedError(f"--sampler {args.sampler}: only PPDE is implemented on the MI355X path "
                               "(simulated_annealing / MALA-approx / CMAES / Random are the paper's baselines)")
+
+
+def design_library_from_flags(args, wt_idx, min_pos, max_pos):
+    """--ppde_sites / --ppde_exclude / --ppde_library -> uint32 [L], or None when none of them is given. Positions are 0-based
+    indices of the full sequence, the index space of the `min_pos max_pos` line the run prints."""
+    sites, exclude, path = getattr(args, "ppde_sites", None), getattr(args, "ppde_exclude", "") or "", getattr(args, "ppde_library_file", None)
+    if sites is None and not exclude and path is None:
+        return None
+    L = len(wt_idx)
+    window = (int(min_pos), int(max_pos))
+    if path is not None:            # replaces --ppde_sites; --ppde_exclude still applies on top of it
+        lib = design_library.build_library(wt_idx, window, exclude=exclude, entries=design_library.parse_library_file(path, L))
+    else:
+        lib = design_library.build_library(wt_idx, window, exclude=exclude,
+                                           sites=None if sites is None else design_library.parse_sites(sites, L))
+    print(design_library.summary(lib), flush=True)
+    return lib
 
 
 def main(args):
@@ -81,7 +100,8 @@ def main(args):
     with torch.no_grad():
         print(f"WT protein energy: {energy_func.get_energy(initial_population)[0].mean():.3f}")
 
-    sampler = get_sampler(args)
+    library = design_library_from_flags(args, seqs_to_idx(wtseqs)[0], oracle.potts.index_list[0], oracle.potts.index_list[-1])
+    sampler = get_sampler(args, library)
     t_loaded = time.perf_counter()
     best_samples, best_energy, best_fitness, energy_history, fitness_history, random_traj = \
         sampler.run(initial_population, args.n_iters, energy_func, oracle.potts.index_list[0],
@@ -165,6 +185,15 @@ def build_parser():
     pp.add_argument("--ppde_timing", action="store_true", help="print one '[ppde timing] {json}' line with the wall-clock split of the run")
     pp.add_argument("--ppde_full_grad", action="store_true",
                     help="transformer experts only: let lamda * d fit/dx into the proposal gradient (the reference leaves it out)")
+    pp.add_argument("--ppde_sites", type=str, default=None,
+                    help="residues the sampler may mutate, e.g. '8-20,33,40-44': 0-based, inclusive, the index space of the "
+                         "'min_pos max_pos' line the run prints; every other residue is frozen (default: every site of the window)")
+    pp.add_argument("--ppde_exclude", type=str, default="",
+                    help="letters never proposed at any open site, e.g. 'CM'. The wild-type letter of an open site is always kept")
+    pp.add_argument("--ppde_library", dest="ppde_library_file", metavar="FILE", type=str, default=None,
+                    help="file of lines '<pos> <letters>' ('#' comments): the letters that may be proposed at each listed residue, "
+                         "unlisted residues frozen. Replaces --ppde_sites; --ppde_exclude still applies on top. The wild-type "
+                         "letter of an open site is always kept")
     return parser
 
 
