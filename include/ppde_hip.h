@@ -21,15 +21,22 @@
  *     and is not thread-safe; the stateless calls (ppde_energy_grad ...) share one scratch set per model
  *     and must not run concurrently with each other on the same model.
  *
- * Shape limits (checked; violations return PPDE_ERR_INVALID with a message, nothing falls back):
+ * Shape limits (checked where the shape is given -- ppde_model_create, the set_* call, ppde_chains_create; violations return
+ * PPDE_ERR_INVALID with a message and leave the object as it was, nothing falls back; tests/test_abi_limits_{cpu,gpu}.py run
+ * each limit at its edge):
  *   - alphabet 20; sequence length 5 <= L <= 4096 for the model, L <= 307 for ppde_chains (a chain's
  *     L*20 proposal logits live in the registers of one 512-thread workgroup);
- *   - state rows (L + alignment padding) <= 512 bytes for the Potts kernel, i.e. L <= ~500;
- *   - Potts window 1 <= Lp <= L; windows of more than 128 residues stream through an LDS ring
- *     (no upper bound besides the state-row limit), shorter ones keep a resident slab of <= 32 KiB
- *     pieces per wave;
- *   - supervised expert: 1..4 networks of one shape, kernel size 1..8, embedding width F <= 512
- *     for the single-launch kernel (wider or longer networks take the chunked kernels);
+ *   - Potts window 1 <= Lp <= min(L, 512), anywhere in the sequence (the kernel reads a transposed copy of the window's
+ *     letters: no limit on the state row): windows of more than 128 residues stream through an LDS ring of at most 32 chunks
+ *     of 16 residues, shorter ones keep a resident slab of <= 32 KiB pieces per wave;
+ *   - supervised expert: 1..4 networks of one shape, kernel size 1 <= K <= min(8, L), C >= 1 channels, F >= 1 features, as
+ *     independent numbers. Up to 128 output rows (T = L - K + 1), F <= 512 and a shape of which two workgroups fit a CU's
+ *     LDS run the single-launch kernel; longer or wider networks take the chunked kernels, which hold 64 rows of ALL channels
+ *     (padded to a multiple of 32: CP; features to a multiple of 16: FP) in LDS: 264 CP + 12 FP + 512 <= 163840 bytes. That
+ *     bounds the WIDTH, not the length: C <= 608 at small F, C <= 544 at F = 2C. For networks of the reference's shape
+ *     (C = L, F = 2L) it means L <= 544; ppde_model_set_cnn refuses a wider one and names the bound in channels. The chunked
+ *     kernels also need FP <= 32 * max(CP, 20 * taps) (taps = 5 for K = 5, else 8): F <= 3200 for narrow five-tap networks
+ *     (the exact-fp32 build, PPDE_CNN_BF16=0, has its own form of this bound: FP <= 32 * the padded row stride of CP channels);
  *   - transformer expert: head width 24, 32 or 64, dim a multiple of 8 (<= 1536; padded to a multiple of 128 internally), ffn a
  *     multiple of 128, L <= 256;
  *   - ppde_pas_length 1..64; chain_offset + n_chains < 2^32.

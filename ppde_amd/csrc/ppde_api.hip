@@ -124,7 +124,7 @@ static int state_rows_to_t4(const ppde_model* m, const uint8_t* rows, uint32_t* 
 }
 
 static int upload_wt(ppde_model* m) {
-    if (m->d_wt) HIPCHK(hipFree(m->d_wt));
+    if (m->d_wt) { uint8_t* old = m->d_wt; m->d_wt = nullptr; HIPCHK(hipFree(old)); }   // (never left dangling if what follows fails)
     std::vector<uint8_t> row(m->g.Ls, 0);
     for (int l = 0; l < m->L; ++l) row[m->g.sh + l] = m->h_wt[l];
     HIPCHK(dalloc(&m->d_wt, (size_t)m->g.Ls));
@@ -271,15 +271,43 @@ static bool cnn_bf16() {
 static size_t cnn_single_lds(const ppde_model* m) {
     return cnn_bf16() ? cnn_bf_lds_bytes(m->T, m->CP, m->FP, m->J, m->L) : cnn_lds_bytes(m->T, m->CP, m->FP, m->J, m->L);
 }
-static bool cnn_single_launch(const ppde_model* m) {
+// launch form of a supervised expert of this (padded) shape: single launch, or the forward / backward chunk kernels
+static bool cnn_single_launch_shape(int T, int CP, int FP, int J, int L) {
     static const int chunked_override = []() { const char* e = getenv("PPDE_CNN_CHUNKED"); return e ? atoi(e) : -1; }();   // tuning knob
     if (chunked_override == 1) return false;
-    const size_t lds = cnn_single_lds(m);
-    if (cnn_rows(m->T) > 16 * CNN_MAX_RT || lds > 160 * 1024 || m->FP > 512) return false;   // (cnn_body keeps two features per thread)
+    const size_t lds = cnn_bf16() ? cnn_bf_lds_bytes(T, CP, FP, J, L) : cnn_lds_bytes(T, CP, FP, J, L);
+    if (cnn_rows(T) > 16 * CNN_MAX_RT || lds > 160 * 1024 || FP > 512) return false;   // (cnn_body keeps two features per thread)
     // Where only ONE workgroup of the single-launch kernel fits a CU (L >= 100), the chunked path (two to four
     // workgroups per CU, balanced grids) is faster: UBE4B, L = 104: 166 us/step against 214 (180 with an 8-wave
     // variant of the single-launch kernel that was built and dropped again). PABP (two per CU): 108 vs 136.
     return 2 * lds <= 160 * 1024 || chunked_override == 0;
+}
+static bool cnn_single_launch(const ppde_model* m) { return cnn_single_launch_shape(m->T, m->CP, m->FP, m->J, m->L); }
+
+// The chunk kernels keep 64 rows of ALL padded channels in LDS (forward: the split h1 image; backward: the routed gradient's, 12
+// bytes per padded feature beside it): what bounds the width of a network that does not fit the single-launch kernel.
+static size_t cnn_chunk_lds(int CP, int FP, int J) {
+    const bool bf = cnn_bf16();
+    const size_t lds_f = bf ? cnn_bf_fwd_chunk_lds(CP, FP) : cnn_fwd_chunk_lds(CP);
+    const size_t lds_b = bf ? cnn_bf_bwd_chunk_lds(CP, FP, J) : cnn_bwd_chunk_lds(CP, FP, J);
+    return std::max(lds_f, lds_b);
+}
+// "" if the chunk kernels serve this width, else the refusal (the bound in channels at this embedding width)
+static std::string cnn_chunk_refusal(int C, int CP, int F, int FP, int J) {
+    // the backward window's route bitmap (one bit per row and padded feature) lies in the storage the routed gradient takes after
+    // it (k_cnn_bwd_chunk: sB = sD): it must fit there, or it runs into the gate bits behind it. (The exact-fp32 layout is held to
+    // its own routed-gradient rows: cautious there, where what lies behind is written only after the routing.)
+    const size_t rows_b = cnn_bf16() ? CNN_BCH_RT * 16 : CNN_BCH_RT_F32 * 16, bitmap = rows_b * ((FP + 31) / 32) * 4;
+    const size_t region = cnn_bf16() ? std::max((size_t)CNN_BCH_RT * BFT * (CP / 32) * 1024, rows_b * J * 4) : rows_b * cnn_astride(CP) * 4;
+    if (bitmap > region)
+        return "supervised expert: F = " + std::to_string(F) + " features are too many for the chunked CNN kernels at C = " + std::to_string(C) +
+               " channels: F (padded to 16) <= 32 * max(C padded to 32, 20 * taps), here " + std::to_string(region / (rows_b / 8));
+    if (cnn_chunk_lds(CP, FP, J) <= 160 * 1024) return "";
+    int cp_max = 0;
+    for (int cp = 32; cp < CP; cp += 32) if (cnn_chunk_lds(cp, FP, J) <= 160 * 1024) cp_max = cp;
+    return "supervised expert too wide for the chunked CNN kernels: C = " + std::to_string(C) + " channels (padded to " +
+           std::to_string(CP) + ") with F = " + std::to_string(F) + " features need more than 160 KiB of LDS; at this F at most " +
+           std::to_string(cp_max) + " channels (reference-shaped networks, C = L and F = 2L: L <= 544)";
 }
 
 // Output rows of the CNN expert per chain. The single-launch kernel cuts the LAST network's features into two workgroups:
@@ -342,7 +370,8 @@ static int launch_cnn(const ppde_model* m, const States& st, int n, const EvalTa
         const int frt = cnn_fwd_rt(m);
         const size_t lds_f = bf ? cnn_bf_fwd_chunk_lds(m->CP, m->FP) : cnn_fwd_chunk_lds(m->CP);
         const size_t lds_b = bf ? cnn_bf_bwd_chunk_lds(m->CP, m->FP, m->J) : cnn_bwd_chunk_lds(m->CP, m->FP, m->J);
-        ARGCHK(lds_f <= 160 * 1024 && lds_b <= 160 * 1024, "sequence too long for the chunked CNN kernels");
+        // (ppde_model_set_cnn refuses such a shape; this is the backstop in front of the launch)
+        ARGCHK(lds_f <= 160 * 1024 && lds_b <= 160 * 1024, cnn_chunk_refusal(m->C, m->CP, m->F, m->FP, m->J));
         CnnChunkArgs ca{a, t.cmax, t.carg, t.cgate, cnn_fwd_chunks(m->T, frt), frt * 16};
         const dim3 gf(n_sub, m->n_nets, ca.NCH), gb(n_sub, m->n_nets, want_grad ? cnn_bwd_chunks(m->L, m->KT, bf) : 1);
         // the two long real proteins have instantiations with their network shape pinned (cnn.h CnnChunkShape)
@@ -787,10 +816,7 @@ int ppde_model_get_transformer_wt_score(ppde_model* m, float* out_host) {
     return PPDE_OK;
 }
 
-int ppde_model_set_potts(ppde_model* m, const float* J, const float* h, int Lp, int win_start) {
-    ARGCHK(m && J && h, "null argument");
-    ARGCHK(Lp >= 1 && win_start >= 0 && win_start + Lp <= m->L, "Potts window does not fit the sequence");
-    HIPCHK(hipSetDevice(m->device));
+static int set_potts_body(ppde_model* m, const float* J, const float* h, int Lp, int win_start) {
     set_geom(m, Lp, win_start);
     free_scratch(m);
     int rc = upload_wt(m);
@@ -800,9 +826,6 @@ int ppde_model_set_potts(ppde_model* m, const float* J, const float* h, int Lp, 
     DevTmp raw;
     HIPCHK(raw.alloc<float>(nJ));
     HIPCHK(hipMemcpy(raw.p, J, nJ * sizeof(float), hipMemcpyHostToDevice));
-    if (m->d_Jt) { hipFree(m->d_Jt); m->d_Jt = nullptr; }
-    if (m->d_h) { hipFree(m->d_h); m->d_h = nullptr; }
-    m->has_potts = false;
     const size_t nJt = (size_t)Lp * 5 * g.NC * 320;           // float4s
     HIPCHK(dalloc(&m->d_Jt, nJt));
     HIPCHK(dalloc(&m->d_h, (size_t)Lp * 20));
@@ -810,7 +833,6 @@ int ppde_model_set_potts(ppde_model* m, const float* J, const float* h, int Lp, 
     hipLaunchKernelGGL(potts_prepare_kernel, dim3(1024), dim3(256), 0, 0, raw.as<float>(), (float*)m->d_Jt, Lp, g.NC);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    m->has_potts = true;
     // wt_H = H(wild type) with the same kernel that evaluates every other state
     DevTmp grad, ep, e;
     HIPCHK(grad.alloc<float>((size_t)g.N));
@@ -822,6 +844,31 @@ int ppde_model_set_potts(ppde_model* m, const float* J, const float* h, int Lp, 
     hipLaunchKernelGGL(potts_energy_finalize_kernel, dim3(1), dim3(64), 0, 0, ep.as<float>(), Lp, 0.0f, e.as<float>(), 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(&m->wt_H, e.p, sizeof(float), hipMemcpyDeviceToHost));
+    return PPDE_OK;
+}
+
+int ppde_model_set_potts(ppde_model* m, const float* J, const float* h, int Lp, int win_start) {
+    ARGCHK(m && J && h, "null argument");
+    ARGCHK(Lp >= 1 && win_start >= 0 && win_start + Lp <= m->L, "Potts window does not fit the sequence");
+    // (the ring kernel walks at most 32 chunks of 16 residues; refused before the model is touched)
+    ARGCHK(Lp <= 512, "Potts window longer than 512 residues (Lp <= 512)");
+    HIPCHK(hipSetDevice(m->device));
+    m->has_potts = false;
+    if (m->d_Jt) { hipFree(m->d_Jt); m->d_Jt = nullptr; }
+    if (m->d_h) { hipFree(m->d_h); m->d_h = nullptr; }
+    const int rc = set_potts_body(m, J, h, Lp, win_start);
+    if (rc) {
+        // no half-set expert: no window, the wild type in the layout of a model without one (the first failure is what is reported)
+        const std::string why = g_err;
+        if (m->d_Jt) { hipFree(m->d_Jt); m->d_Jt = nullptr; }
+        if (m->d_h) { hipFree(m->d_h); m->d_h = nullptr; }
+        m->wt_H = 0.f;
+        set_geom(m, 0, 0);
+        free_scratch(m);
+        upload_wt(m);
+        return fail(rc, why);
+    }
+    m->has_potts = true;
     return PPDE_OK;
 }
 
@@ -838,9 +885,18 @@ int ppde_model_set_cnn(ppde_model* m, int n_nets, int C, int K, int F, const flo
     ARGCHK(m && conv_w && conv_b && lin_w && lin_b && dec_w && dec_b, "null argument");
     ARGCHK(n_nets >= 1 && n_nets <= 4, "1..4 networks supported");
     ARGCHK(K >= 1 && K <= CNN_MAX_K && K <= m->L && C >= 1 && F >= 1, "bad CNN shape (kernel size 1..8)");
+    {
+        // a shape neither launch form serves is refused here, where it is known, before the model is touched
+        const int kt = (K == 5) ? 5 : CNN_MAX_K, cp = (C + 4 * CNN_KB - 1) / (4 * CNN_KB) * (4 * CNN_KB), fp = (F + 15) & ~15;
+        if (!cnn_single_launch_shape(m->L - K + 1, cp, fp, kt * 20, m->L)) {
+            const std::string why = cnn_chunk_refusal(C, cp, F, fp, kt * 20);
+            ARGCHK(why.empty(), why);
+        }
+    }
     HIPCHK(hipSetDevice(m->device));
     for (void* p : m->cnn_allocs) hipFree(p);
     m->cnn_allocs.clear();
+    m->has_cnn = false;
     m->n_nets = n_nets; m->C = C; m->K = K; m->F = F; m->T = m->L - K + 1;
     m->KT = (K == 5) ? 5 : CNN_MAX_K;            // tables hold KT taps (zero padded beyond K)
     m->J = m->KT * 20;
@@ -1039,6 +1095,10 @@ int ppde_energy_grad(ppde_model* m, const uint8_t* idx_dev, int n, int which, fl
                      float* grad_dev, void* stream) {
     ARGCHK(m && idx_dev && n >= 0, "bad argument");
     ARGCHK(which >= 1 && which <= 15 && (which & 7), "which: bit 0 Potts, bit 1 supervised, bit 2 transformer expert, bit 3 full gradient");
+    // (an energy whose expert was never set is refused before scratch is allocated or a kernel goes out)
+    ARGCHK(!(which & 1) || m->has_potts, "the energy uses the Potts expert but ppde_model_set_potts was not called");
+    ARGCHK(!(which & 2) || m->has_cnn, "the energy uses the supervised expert but ppde_model_set_cnn was not called");
+    ARGCHK(!(which & 4) || m->tf, "no transformer expert");
     if (n == 0) return PPDE_OK;
     HIPCHK(hipSetDevice(m->device));
     hipStream_t s = (hipStream_t)stream;

@@ -73,7 +73,12 @@ class HipModel:
         # register_potts_model when these ARE a potts.pkl's couplings)
         for k in [k for k, r in _POTTS_MODELS.items() if r() is self]:
             del _POTTS_MODELS[k]
-        _hip.check(self.lib.ppde_model_set_potts(self.handle, _hip.ptr(J), _hip.ptr(h), Lp, int(win_start)))
+        try:
+            _hip.check(self.lib.ppde_model_set_potts(self.handle, _hip.ptr(J), _hip.ptr(h), Lp, int(win_start)))
+        except _hip.PpdeHipError:
+            # a window refused up front leaves the expert that was there, a failure later leaves none: the library knows which
+            self.has_potts = self.lib.ppde_model_get_wt_hamiltonian(self.handle, C.byref(C.c_float())) == 0
+            raise
         self.has_potts, self.win_start, self.Lp = True, int(win_start), Lp
 
     def set_cnn(self, states):

@@ -157,7 +157,7 @@ def _cnn_fp64(sd, row):
     return pre1.numpy(), h1.numpy(), h2.numpy(), Wflat.numpy(), W["embedding.0.weight"].numpy(), W["decoder.weight"].reshape(-1).numpy(), K
 
 
-def cnn_grad_decompose(cnn, row, gap=5e-6):
+def cnn_grad_decompose(cnn, row, gap=5e-6, want_rank=True):
     """The supervised ensemble's input gradient d fit / d x of ONE chain (`row`: its L letters), evaluated in fp64 and written
     as  g = fixed + sum over groups of exactly one alternative per group  (the gradient is linear in the routing):
       * one group per (network, positive feature) whose candidate rows {t : h2[t, f] >= top * (1 - gap)} number more than one,
@@ -168,7 +168,8 @@ def cnn_grad_decompose(cnn, row, gap=5e-6):
     Returns a dict: fixed [L, 20]; groups (lists of [L, 20] alternatives); exact (per group: the tied rows' K-mer windows are
     identical, so every implementation computes the same bits for them); info (per group: ("max", net, feature, rows) or
     ("kink", net, row, channel)); unresolved (a kink on a row that a tied feature may be routed to, or an option matrix without
-    full column rank: the routing cannot be read off the gradient); rank / columns of the option matrix."""
+    full column rank: the routing cannot be read off the gradient); rank / columns of the option matrix. want_rank=False
+    leaves the rank (and its part of `unresolved`) out: a caller that reads only the groups' kind need not pay for it."""
     row = np.asarray(row).reshape(-1)
     L, nn = row.shape[0], len(cnn)
     fixed = np.zeros((L, A))
@@ -209,11 +210,12 @@ def cnn_grad_decompose(cnn, row, gap=5e-6):
             groups.append([np.zeros((L, A)), -delta if gate[t, c] else delta])
             exact.append(False)
             info.append(("kink", ni, t, c))
-    cols = [alt - g[0] for g in groups for alt in g[1:]]
+    cols = [alt - g[0] for g in groups for alt in g[1:]] if want_rank else []
     rank = int(np.linalg.matrix_rank(np.stack([c.ravel() for c in cols], 1))) if cols else 0
     if rank < len(cols):
         unresolved = True
-    return dict(fixed=fixed, groups=groups, exact=exact, info=info, unresolved=unresolved, rank=rank, columns=len(cols))
+    return dict(fixed=fixed, groups=groups, exact=exact, info=info, unresolved=unresolved, rank=rank,
+                columns=sum(len(g) - 1 for g in groups))
 
 
 def cnn_grad_vertex(dec, picks):

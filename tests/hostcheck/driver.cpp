@@ -12,6 +12,9 @@
 
 extern "C" long hipmock_calls();
 extern "C" void hipmock_rearm(long fail_at);
+extern "C" long hipmock_launches();
+extern "C" long hipmock_allocs();
+extern "C" long hipmock_writes();
 
 namespace {
 std::mt19937 rng(7);
@@ -183,6 +186,94 @@ int argument_errors() {
     ppde_model_destroy(m);
     return 0;
 }
+
+// The shape limits of include/ppde_hip.h that need no kernel result: each refusal is PPDE_ERR_INVALID with a message, happens before
+// the object is touched -- across the refused call the runtime sees no kernel launch, no allocation and no copy or fill -- and leaves
+// it usable (the mock runs no kernel, so "usable" = the next valid call succeeds and nothing leaks).
+#define EXPECT_INVALID(x) do { const long l_ = hipmock_launches(), a_ = hipmock_allocs(), w_ = hipmock_writes(); int rc_ = (x); \
+    if (rc_ != PPDE_ERR_INVALID || !ppde_last_error()[0]) { \
+        fprintf(stderr, "expected PPDE_ERR_INVALID with a message from %s, got %d (%s)\n", #x, rc_, ppde_last_error()); return 99; } \
+    if (hipmock_launches() != l_ || hipmock_allocs() != a_ || hipmock_writes() != w_) { \
+        fprintf(stderr, "%s was refused after %ld launches, %ld allocations, %ld copies / fills\n", #x, hipmock_launches() - l_, \
+                hipmock_allocs() - a_, hipmock_writes() - w_); return 98; } } while (0)
+int set_cnn_of(ppde_model* m, int n_nets, int C, int K, int F) {
+    const int k = n_nets > 0 ? n_nets : 1, c = C > 0 ? C : 1, kk = K > 0 ? K : 1, f = F > 0 ? F : 1;
+    auto cw = many(k, (size_t)c * 20 * kk), cb = many(k, c), lw = many(k, (size_t)f * c), lb = many(k, f), dw = many(k, f), db = many(k, 1);
+    return ppde_model_set_cnn(m, n_nets, C, K, F, cw.p.data(), cb.p.data(), lw.p.data(), lb.p.data(), dw.p.data(), db.p.data());
+}
+int shape_limits() {
+    ppde_model* m = nullptr;
+    std::vector<uint8_t> wt(4097, 3);
+    EXPECT_INVALID(ppde_model_create(&m, 0, 4, wt.data()));
+    EXPECT_INVALID(ppde_model_create(&m, 0, 4097, wt.data()));
+    if (ppde_model_create(&m, 0, 40, wt.data()) != PPDE_OK) return 97;
+    if (set_cnn_of(m, 3, 33, 5, 33) != PPDE_OK) return 96;
+    EXPECT_INVALID(set_cnn_of(m, 0, 8, 5, 16));
+    EXPECT_INVALID(set_cnn_of(m, 5, 8, 5, 16));
+    EXPECT_INVALID(set_cnn_of(m, 3, 8, 0, 16));
+    EXPECT_INVALID(set_cnn_of(m, 3, 8, 9, 16));
+    EXPECT_INVALID(set_cnn_of(m, 3, 0, 5, 16));
+    EXPECT_INVALID(set_cnn_of(m, 3, 8, 5, 0));
+    EXPECT_INVALID(set_cnn_of(m, 3, 1024, 5, 64));                                   // wider than the chunk kernels' LDS
+    if (!strstr(ppde_last_error(), "channels")) { fprintf(stderr, "the width refusal does not speak of channels: %s\n", ppde_last_error()); return 95; }
+    EXPECT_INVALID(set_cnn_of(m, 3, 32, 5, 3201));                                   // more features than the route bitmap holds
+    if (!strstr(ppde_last_error(), "features")) { fprintf(stderr, "the F refusal does not speak of features: %s\n", ppde_last_error()); return 95; }
+    std::vector<uint8_t> idx(2 * 40, 1);
+    std::vector<float> e(2), fit(2), grad((size_t)2 * 40 * 20);
+    if (ppde_energy_grad(m, idx.data(), 2, 2, e.data(), fit.data(), grad.data(), nullptr) != PPDE_OK) return 94;   // the expert that was there
+    ppde_model_destroy(m); m = nullptr;
+    if (ppde_model_create(&m, 0, 7, wt.data()) != PPDE_OK) return 93;
+    EXPECT_INVALID(set_cnn_of(m, 3, 8, 8, 16));                                      // K > L
+    if (set_cnn_of(m, 3, 8, 7, 16) != PPDE_OK) return 92;                            // K = L: one output row
+    ppde_model_destroy(m); m = nullptr;
+    // the reference's network shape (C = L, F = 2L) at the last accepted width and one step past it
+    if (ppde_model_create(&m, 0, 545, wt.data()) != PPDE_OK) return 91;
+    EXPECT_INVALID(set_cnn_of(m, 3, 545, 5, 1090));
+    if (!strstr(ppde_last_error(), "channels") || !strstr(ppde_last_error(), "544")) { fprintf(stderr, "L = 545: %s\n", ppde_last_error()); return 90; }
+    EXPECT_INVALID(ppde_energy_grad(m, idx.data(), 1, 2, e.data(), fit.data(), nullptr, nullptr));   // no supervised expert was set
+    ppde_model_destroy(m); m = nullptr;
+    if (ppde_model_create(&m, 0, 544, wt.data()) != PPDE_OK) return 89;
+    if (set_cnn_of(m, 3, 544, 5, 1088) != PPDE_OK) { fprintf(stderr, "L = 544: %s\n", ppde_last_error()); return 88; }
+    ppde_model_destroy(m); m = nullptr;
+    // Potts window of 513 residues: refused before the model is touched (J is never read: a short array will do)
+    if (ppde_model_create(&m, 0, 520, wt.data()) != PPDE_OK) return 87;
+    std::vector<float> J((size_t)64 * 64 * 400), h(64 * 20);
+    EXPECT_INVALID(ppde_model_set_potts(m, J.data(), h.data(), 513, 0));
+    std::vector<uint8_t> idx520(520, 2);
+    EXPECT_INVALID(ppde_energy_grad(m, idx520.data(), 1, 1, e.data(), fit.data(), nullptr, nullptr));
+    float wtH = 0.f;
+    EXPECT_INVALID(ppde_model_get_wt_hamiltonian(m, &wtH));
+    ppde_chain_config cfg{};
+    cfg.n_chains = 2; cfg.max_steps = 4; cfg.pas_length = 2; cfg.max_pos = 519; cfg.which = 1; cfg.rng_mode = 1;
+    ppde_chains* c = nullptr;
+    EXPECT_INVALID(ppde_chains_create(&c, m, &cfg));
+    if (ppde_model_set_potts(m, J.data(), h.data(), 64, 100) != PPDE_OK) return 86;   // a valid window on the same model
+    if (ppde_energy_grad(m, idx520.data(), 1, 1, e.data(), fit.data(), nullptr, nullptr) != PPDE_OK) return 85;
+    EXPECT_INVALID(ppde_model_set_potts(m, J.data(), h.data(), 513, 0));             // and the refusal leaves THAT expert in place
+    if (ppde_energy_grad(m, idx520.data(), 1, 1, e.data(), fit.data(), nullptr, nullptr) != PPDE_OK) return 84;
+    EXPECT_INVALID(ppde_chains_create(&c, m, &cfg));                                 // L = 520 > 307
+    ppde_model_destroy(m); m = nullptr;
+    // chains: L = 308, ppde_pas_length 0 and 65
+    if (ppde_model_create(&m, 0, 308, wt.data()) != PPDE_OK) return 83;
+    if (ppde_model_set_potts(m, J.data(), h.data(), 64, 100) != PPDE_OK) return 82;
+    cfg.max_pos = 307;
+    EXPECT_INVALID(ppde_chains_create(&c, m, &cfg));
+    ppde_model_destroy(m); m = nullptr;
+    if (ppde_model_create(&m, 0, 307, wt.data()) != PPDE_OK) return 81;
+    if (ppde_model_set_potts(m, J.data(), h.data(), 64, 100) != PPDE_OK) return 80;
+    cfg.max_pos = 306; cfg.pas_length = 0;
+    EXPECT_INVALID(ppde_chains_create(&c, m, &cfg));
+    cfg.pas_length = 65;
+    EXPECT_INVALID(ppde_chains_create(&c, m, &cfg));
+    cfg.pas_length = 64;
+    if (ppde_chains_create(&c, m, &cfg) != PPDE_OK) { fprintf(stderr, "L = 307, pas 64: %s\n", ppde_last_error()); return 79; }
+    std::vector<uint8_t> idx307(2 * 307, 1);
+    if (ppde_chains_init(c, idx307.data()) != PPDE_OK || ppde_chains_run(c, 2, nullptr, nullptr, nullptr, nullptr) != PPDE_OK ||
+        ppde_chains_sync(c) != PPDE_OK) { fprintf(stderr, "L = 307, pas 64 run: %s\n", ppde_last_error()); return 78; }
+    ppde_chains_destroy(c);
+    ppde_model_destroy(m);
+    return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -199,6 +290,8 @@ int main(int argc, char** argv) {
     if (rc != PPDE_OK) { fprintf(stderr, "head-width-64 run failed: %d (%s)\n", rc, ppde_last_error()); return 1; }
     rc = argument_errors();
     if (rc) { fprintf(stderr, "argument_errors: %d\n", rc); return 1; }
+    rc = shape_limits();
+    if (rc) { fprintf(stderr, "shape_limits: %d\n", rc); return 1; }
     long failures = 0;
     if (sweep) {
         for (long k = 1; k <= fallible; ++k) {

@@ -7,12 +7,14 @@
 // shows up in the leak report.
 // Fault injection: HIPMOCK_FAIL_AT=k makes the k-th fallible call (allocations, stream / event / graph creation)
 // return an error, which drives the library's clean-up paths; hipmock_calls() reports how many there were.
+// hipmock_launches() / hipmock_allocs() / hipmock_writes() count kernel launches, allocations and copies / fills so far: a call
+// that must refuse its arguments "before anything is touched" is checked to move none of them.
 #include <hip/hip_runtime_api.h>
 #include <cstdlib>
 #include <cstring>
 
 namespace {
-long g_calls = 0, g_fail_at = -1;
+long g_calls = 0, g_fail_at = -1, g_launches = 0, g_allocs = 0, g_writes = 0;
 bool g_armed = false;
 bool fail_now() {
     if (!g_armed) { const char* e = getenv("HIPMOCK_FAIL_AT"); g_fail_at = e ? atol(e) : -1; g_armed = true; }
@@ -24,6 +26,9 @@ thread_local Cfg t_cfg;
 
 extern "C" {
 long hipmock_calls() { return g_calls; }
+long hipmock_launches() { return g_launches; }
+long hipmock_allocs() { return g_allocs; }
+long hipmock_writes() { return g_writes; }
 void hipmock_rearm(long fail_at) { g_calls = 0; g_fail_at = fail_at; g_armed = true; }
 
 void** __hipRegisterFatBinary(const void*) { static void* h; return &h; }
@@ -33,6 +38,7 @@ void __hipRegisterVar(void**, void*, char*, const char*, int, size_t, int, int) 
 hipError_t __hipPushCallConfiguration(dim3 g, dim3 b, size_t sh, hipStream_t s) { t_cfg = Cfg{g, b, sh, s}; return hipSuccess; }
 hipError_t __hipPopCallConfiguration(dim3* g, dim3* b, size_t* sh, hipStream_t* s) { *g = t_cfg.grid; *b = t_cfg.block; *sh = t_cfg.shmem; *s = t_cfg.stream; return hipSuccess; }
 hipError_t hipLaunchKernel(const void*, dim3 g, dim3 b, void**, size_t sh, hipStream_t) {
+    ++g_launches;
     if (g.x == 0 || g.y == 0 || g.z == 0 || b.x == 0 || b.x * b.y * b.z > 1024 || sh > 160 * 1024) return hipErrorInvalidConfiguration;
     return hipSuccess;
 }
@@ -45,16 +51,16 @@ hipError_t hipGetLastError() { return hipSuccess; }
 const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory (mock)" : "error (mock)"; }
 hipError_t hipDeviceSynchronize() { return hipSuccess; }
 
-hipError_t hipMalloc(void** p, size_t n) { if (fail_now()) { *p = nullptr; return hipErrorOutOfMemory; } *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+hipError_t hipMalloc(void** p, size_t n) { ++g_allocs; if (fail_now()) { *p = nullptr; return hipErrorOutOfMemory; } *p = calloc(n ? n : 1, 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void** p, size_t n, unsigned) { if (fail_now()) { *p = nullptr; return hipErrorOutOfMemory; } *p = calloc(n ? n : 1, 1); return hipSuccess; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { ++g_allocs; if (fail_now()) { *p = nullptr; return hipErrorOutOfMemory; } *p = calloc(n ? n : 1, 1); return hipSuccess; }
 hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
-hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { if (n) memcpy(d, s, n); return hipSuccess; }
-hipError_t hipMemset(void* d, int v, size_t n) { if (n) memset(d, v, n); return hipSuccess; }
-hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { if (n) memset(d, v, n); return hipSuccess; }
-hipError_t hipMemsetD32Async(hipDeviceptr_t d, int v, size_t count, hipStream_t) { for (size_t i = 0; i < count; ++i) ((int*)d)[i] = v; return hipSuccess; }
+hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { ++g_writes; if (n) memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { ++g_writes; if (n) memcpy(d, s, n); return hipSuccess; }
+hipError_t hipMemset(void* d, int v, size_t n) { ++g_writes; if (n) memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { ++g_writes; if (n) memset(d, v, n); return hipSuccess; }
+hipError_t hipMemsetD32Async(hipDeviceptr_t d, int v, size_t count, hipStream_t) { ++g_writes; for (size_t i = 0; i < count; ++i) ((int*)d)[i] = v; return hipSuccess; }
 
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { if (fail_now()) return hipErrorOutOfMemory; *s = (hipStream_t)malloc(8); return hipSuccess; }
 hipError_t hipStreamDestroy(hipStream_t s) { free((void*)s); return hipSuccess; }
