@@ -216,6 +216,29 @@ int ppde_chains_destroy(ppde_chains* c);
  * [min_pos, max_pos] is open. The words are copied; the chains own the device copy. */
 int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host /* [L] or NULL */);
 
+/* Reversible mode (off by default). The reference scores the reverse move of sub-step s at the index the FORWARD move chose
+ * (ppde.py:122-153, :128-132): in the reverse state that index is the letter the residue already holds, its logit is exactly
+ * 0, the move that actually undoes the step is never scored, and the reverse rows take no masks while the forward rows do --
+ * so the chains' stationary law is not exp(energy)/Z. With `on` != 0 the accept phase replaces ppde.py:122-153 by a
+ * Metropolis-Hastings step of the same forward proposal:
+ *   row(g, state) = the forward row: logits (g[l,k] - g[l,state_l]) / 2, the range mask and the mutation-cap mask OF THAT
+ *     STATE as -inf, the design library as in ppde_chains_set_library (forbidden: -inf, exactly 0 behind the clamp);
+ *   forward path: unchanged (same rows, Philox counters, variates consumed, recorded forward log-probabilities);
+ *   reverse row of sub-step s = row(g_y, x_{s+1}), read at the move that undoes the sub-step: (l_s, old_s), old_s the
+ *     letter residue l_s held in x_s; logp_rev = log clamp(p_hat[l_s, old_s]);
+ *   log_acc = (e_y - e_x) + sum_s (logp_rev_s - logp_fwd_s), accepted when exp(log_acc) >= u, as before;
+ *   a path with a reverse move the library forbids (probability exactly 0) is rejected, whatever u is;
+ *   the mutation cap is a constraint, not a reset: a proposal with dist(y) >= nmut_threshold is rejected and nothing is
+ *     ever reset to the wild type (stationary law exp(E) * 1[dist < threshold] / Z). A rejected proposal records accept
+ *     bit 0 and the current energy.
+ * The clamp to [2^-23, 1 - 2^-23] makes the log-probabilities of the ratio differ from the draw probabilities at entries on
+ * the floor or the ceiling; with a library that folds the range in (no masked-but-drawable entry) the law is exp(energy)/Z
+ * over the library up to that. Valid between ppde_chains_create and ppde_chains_init (the captured graphs hold the kernel
+ * choice): afterwards PPDE_ERR_INVALID. `on` with paper_results is PPDE_ERR_INVALID: its reject-to-initial-state move is no
+ * Metropolis step. Initial states need not lie inside the library: a residue holding a letter outside it never moves (its
+ * reverse move is forbidden). */
+int ppde_chains_set_reversible(ppde_chains* c, int on);
+
 /* Start from idx0_dev [n, L] (ppde.py:35-47): evaluates the initial energies, fills history row 0. */
 int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev);
 

@@ -10,6 +10,9 @@
 //                        forward log-probabilities, state update
 //   k_accept  : :122-153 reverse-path log-probabilities on grad(y) (no masks), log acceptance ratio,
 //                        accept/reject, histories, running best (ppde.py:172-183), mutation-cap reset
+//   k_accept_rev, k_accept_propose_rev : reversible mode (ppde_chains_set_reversible, off by default): the Metropolis-Hastings
+//                        accept phase of the same forward proposal -- the reverse rows are the forward row function (masks and
+//                        library included) read at the moves that undo the path; the cap constrains instead of resetting
 // A row of L*20 logits lives in registers (the gradient row it is formed from in LDS); row reductions are DPP wavefront
 // reductions + one LDS exchange per barrier. The kernels are instantiated in a general form and per common configuration
 // (pin_config below).
@@ -73,7 +76,8 @@ struct PasArgs {
     int* err_flag;
     unsigned long long* dbg;    // stamp buffer (diagnostic build)
     // design library (ppde_chains_set_library): allowed[l] bit k = letter k may be PROPOSED at residue l, word 0 = frozen; NULL
-    // = no library. Forward paths only (ppde.py:98-110); the reverse path takes no masks, as the reference treats its own two.
+    // = no library. Forward paths only (ppde.py:98-110); the reverse path takes no masks, as the reference treats its own two
+    // (in reversible mode the reverse rows are forward rows and take it too).
     const uint32_t* allowed;    // [L]
 };
 
@@ -460,22 +464,83 @@ __device__ __forceinline__ void row_max_sumexp_batch(const RowLds& lds, const fl
 
 // NR consecutive sub-steps s0.. of the reverse path (ppde.py:122-132): returns their summed log-ratio terms in
 // path order. lds.G = gradient at the proposal, R.cur = letters before sub-step s0 (advanced on return).
-template <int GPT, int NR>
-__device__ __forceinline__ void reverse_rows(const RowLds& lds, RowRegs<GPT>& R, int s0, float& log_ratio) {
+// REV (reversible mode, ppde_chains_set_reversible): row j is row(g_y, x_{s+1}), the FORWARD row function -- forward_logits<LIB>
+// with the range mask, the cap mask of x_{s+1}'s own mutation count (`rp.dist`, carried along the path) and the library, the
+// forbidden entries zeroed behind the clamp before the row sum as propose_body orders them -- and it is read at the move that
+// UNDOES sub-step s: (l_s, old_s), the letter residue l_s held in x_s (rev_annotate_path). A reverse move the library forbids
+// (probability exactly 0) or a row with no admissible entry sets rp.forbid: the proposal is rejected.
+struct RevPath {
+    int dist;        // mutation count of the state the next reverse row belongs to (x_{s+1} once sub-step s is consumed)
+    bool forbid;     // some reverse move of the path has probability exactly 0
+};
+// Reversible mode: the path's entries in lds.mv become  flat move | old letter << 16 | (change of the mutation count + 1) << 24.
+// old_s is x's letter at l_s unless an earlier move of the same path wrote that residue; one thread per sub-step scans back.
+__device__ __forceinline__ void rev_annotate_path(const RowLds& lds, int Ub) {
+    const int t = threadIdx.x;
+    int packed = 0;
+    if (t < Ub) {
+        const int win = lds.mv[t];
+        const int l = win / 20, k = win - 20 * l;
+        int old = lds.St[l];
+        for (int s = t - 1; s >= 0; --s) {
+            const int w = lds.mv[s];
+            if (w / 20 == l) { old = w - 20 * l; break; }
+        }
+        const int wt = lds.Wt[l];
+        packed = win | (old << 16) | (((int)(k != wt) - (int)(old != wt) + 1) << 24);
+    }
+    __syncthreads();                                 // every scan has read the plain entries
+    if (t < Ub) lds.mv[t] = packed;
+    __syncthreads();
+}
+// logit of the move (l, cur -> old) in row(g, state): the scalar form of forward_logits<LIB> for one entry
+template <bool LIB>
+__device__ __forceinline__ float restore_logit(const PasArgs& a, const RowLds& lds, const float* G, int l, int cur, int old,
+                                               bool capped, bool& forbidden) {
+    const int wt = lds.Wt[l];
+    const bool outside = (l < a.min_pos) | (l > a.max_pos);
+    const bool revertible = capped & (cur != wt);
+    bool masked = outside | (capped & !(revertible & (old == wt)));
+    forbidden = false;
+    if constexpr (LIB) { forbidden = !((lds.Al[l] >> old) & 1u); masked |= forbidden; }
+    const float z = (G[l * 20 + old] - G[l * 20 + cur]) * 0.5f;
+    return masked ? -INFINITY : z;
+}
+template <int GPT, int NR, bool REV = false, bool LIB = false>
+__device__ __forceinline__ void reverse_rows(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int s0, float& log_ratio,
+                                             RevPath& rp) {
     const int tid = threadIdx.x, lane = tid & 63;
     const float* G = (const float*)lds.G;
     const float* lpf = (const float*)(lds.mv + 128);
     float4 z[NR][GPT];
+    int rl[NR], rk[NR], ro[NR];                      // REV: residue, new letter, old letter of each sub-step
+    bool rc[NR];                                     //      and whether the state behind it sits at the mutation cap
+    uint32_t ok4[GPT];
+#pragma unroll
+    for (int r = 0; r < GPT; ++r) {
+        ok4[r] = 15u;
+        if constexpr (REV && LIB) ok4[r] = R.valid[r] ? (lds.Al[R.l[r]] >> R.kb[r]) & 15u : 0u;
+    }
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
-        const int win = lds.mv[s0 + j];
+        const int ent = lds.mv[s0 + j];
+        const int win = REV ? (ent & 0xffff) : ent;
         const int ls = win / 20, ks = win - 20 * ls;
+        if constexpr (REV) {
+            rl[j] = ls; rk[j] = ks; ro[j] = (ent >> 16) & 31;
+            rp.dist += ((ent >> 24) & 3) - 1;
+            rc[j] = rp.dist >= a.thr;
+        }
 #pragma unroll
         for (int r = 0; r < GPT; ++r) {
             if (R.l[r] == ls) R.cur[r] = ks;            // state after sub-step s0 + j
-            const float gc = G[R.l[r] * 20 + R.cur[r]];
-            const float4 gv = R.gv[r];
-            z[j][r] = make_float4((gv.x - gc) * 0.5f, (gv.y - gc) * 0.5f, (gv.z - gc) * 0.5f, (gv.w - gc) * 0.5f);
+            if constexpr (REV) {
+                z[j][r] = forward_logits<LIB>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], rc[j], ok4[r]);
+            } else {
+                const float gc = G[R.l[r] * 20 + R.cur[r]];
+                const float4 gv = R.gv[r];
+                z[j][r] = make_float4((gv.x - gc) * 0.5f, (gv.y - gc) * 0.5f, (gv.z - gc) * 0.5f, (gv.w - gc) * 0.5f);
+            }
         }
     }
     float m[NR], S1[NR], sc[NR], inv[NR], s3w[NR];
@@ -483,6 +548,9 @@ __device__ __forceinline__ void reverse_rows(const RowLds& lds, RowRegs<GPT>& R,
     row_max_sumexp_batch<GPT, NR>(lds, z, R.valid, e, m, S1, sc);
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
+        if constexpr (REV) {
+            if (m[j] == -INFINITY) { rp.forbid = true; m[j] = 0.f; S1[j] = 1.f; }   // no admissible entry: nothing leads back
+        }
         // softmax -> clamp (ppde/utils.py:106-111): p = clamp(exp(z - m) / S1) with exp(z - m) = e * exp(m_w - m)
         inv[j] = 1.0f / S1[j];
         const float c = sc[j] * inv[j];
@@ -490,8 +558,18 @@ __device__ __forceinline__ void reverse_rows(const RowLds& lds, RowRegs<GPT>& R,
 #pragma unroll
         for (int r = 0; r < GPT; ++r) {
             if (!R.valid[r]) continue;
-            s3 += clampp(e[j][r].x * c); s3 += clampp(e[j][r].y * c);
-            s3 += clampp(e[j][r].z * c); s3 += clampp(e[j][r].w * c);
+            if constexpr (REV && LIB) {             // a forbidden entry loses the clamp's floor again, as in propose_body
+                float4 p;
+                p.x = clampp(e[j][r].x * c); p.y = clampp(e[j][r].y * c); p.z = clampp(e[j][r].z * c); p.w = clampp(e[j][r].w * c);
+                if (!(ok4[r] & 1u)) p.x = 0.f;
+                if (!(ok4[r] & 2u)) p.y = 0.f;
+                if (!(ok4[r] & 4u)) p.z = 0.f;
+                if (!(ok4[r] & 8u)) p.w = 0.f;
+                s3 += p.x; s3 += p.y; s3 += p.z; s3 += p.w;
+            } else {
+                s3 += clampp(e[j][r].x * c); s3 += clampp(e[j][r].y * c);
+                s3 += clampp(e[j][r].z * c); s3 += clampp(e[j][r].w * c);
+            }
         }
         s3w[j] = wave_sum(s3);
     }
@@ -502,9 +580,18 @@ __device__ __forceinline__ void reverse_rows(const RowLds& lds, RowRegs<GPT>& R,
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
-        // probability of the recorded move under the reverse proposal: its residue now holds letter ks, so the
-        // logit is (g[win] - g[win]) / 2 = 0 exactly
-        const float pwin = clampp(expf(0.f - m[j]) * inv[j]);
+        float pwin;
+        if constexpr (REV) {
+            // the move that undoes sub-step s: the restored letter's own logit in this row
+            bool forbidden;
+            const float zr = restore_logit<LIB>(a, lds, G, rl[j], rk[j], ro[j], rc[j], forbidden);
+            pwin = clampp(expf(zr - m[j]) * inv[j]);
+            if (forbidden) { pwin = 0.f; rp.forbid = true; }
+        } else {
+            // probability of the recorded move under the reverse proposal: its residue now holds letter ks, so the
+            // logit is (g[win] - g[win]) / 2 = 0 exactly
+            pwin = clampp(expf(0.f - m[j]) * inv[j]);
+        }
         const float S3 = row8_sum(lane < PPDE_NW ? lds.xb[8 * (lane & (PPDE_NW - 1)) + j] : 0.f);
         const float logp_rev = logf(clampp(pwin / S3));
         log_ratio += logp_rev - lpf[s0 + j];
@@ -513,26 +600,44 @@ __device__ __forceinline__ void reverse_rows(const RowLds& lds, RowRegs<GPT>& R,
 
 // Device-RNG form of reverse_rows (rng_mode 1; replay mode keeps the form above, whose bits the reference's fixtures pin):
 //  * a fixed softmax reference for all rows of the path, as in propose_body_dev: half the largest spread of a residue's 20
-//    gradient entries bounds every reverse logit (no masks on the way back), so no maximum is reduced per row;
+//    gradient entries bounds every reverse logit (the default mode takes no masks on the way back; reversible mode's masks
+//    only send entries to -inf), so no maximum is reduced per row;
 //  * the rows of a path differ only at the residues the path moves: a wave none of whose lanes holds such a residue
 //    evaluates its exponentials ONCE and uses them for every row (the clamp and the row sums still run per row: the
 //    normalisation differs).
-template <int GPT, int NR>
-__device__ __forceinline__ void reverse_rows_dev(const RowLds& lds, RowRegs<GPT>& R, int s0, const float mref, const float e0ref,
-                                                 float& log_ratio) {
+template <int GPT, int NR, bool REV = false, bool LIB = false>
+__device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int s0, const float mref,
+                                                 const float e0ref, float& log_ratio, RevPath& rp) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* G = (const float*)lds.G;
     const float* lpf = (const float*)(lds.mv + 128);
     int ls[NR], ks[NR];
-    bool mine = false;
+    int ro[NR];                                      // REV: the letter each sub-step replaced
+    bool rc[NR];                                     //      and whether the state behind it sits at the mutation cap
+    bool mine = false, anycap = false;
+    uint32_t ok4[GPT];
+#pragma unroll
+    for (int r = 0; r < GPT; ++r) {
+        ok4[r] = 15u;
+        if constexpr (REV && LIB) ok4[r] = R.valid[r] ? (lds.Al[R.l[r]] >> R.kb[r]) & 15u : 0u;
+    }
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
-        const int win = lds.mv[s0 + j];
+        const int ent = lds.mv[s0 + j];
+        const int win = REV ? (ent & 0xffff) : ent;
         ls[j] = win / 20; ks[j] = win - 20 * ls[j];
+        if constexpr (REV) {
+            ro[j] = (ent >> 16) & 31;
+            rp.dist += ((ent >> 24) & 3) - 1;
+            rc[j] = rp.dist >= a.thr;
+            anycap |= rc[j];
+        }
 #pragma unroll
         for (int r = 0; r < GPT; ++r) mine |= R.valid[r] & (R.l[r] == ls[j]);
     }
-    const bool split = __any(mine);
+    // REV: the cap's mask changes every entry of a row, so the shared evaluation below holds only while no row of the pass is capped
+    bool split = __any(mine);
+    if constexpr (REV) split = split || anycap;
     float4 e[NR][GPT];
     float sw[NR];
     auto row_exp = [&](int j) {
@@ -541,10 +646,15 @@ __device__ __forceinline__ void reverse_rows_dev(const RowLds& lds, RowRegs<GPT>
         for (int r = 0; r < GPT; ++r) {
             e[j][r] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (!R.valid[r]) continue;
-            const float gc = G[R.l[r] * 20 + R.cur[r]];
-            const float4 gv = R.gv[r];
-            e[j][r].x = expf((gv.x - gc) * 0.5f - mref); e[j][r].y = expf((gv.y - gc) * 0.5f - mref);
-            e[j][r].z = expf((gv.z - gc) * 0.5f - mref); e[j][r].w = expf((gv.w - gc) * 0.5f - mref);
+            if constexpr (REV) {
+                const float4 z = forward_logits<LIB>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], rc[j], ok4[r]);
+                e[j][r].x = expf(z.x - mref); e[j][r].y = expf(z.y - mref); e[j][r].z = expf(z.z - mref); e[j][r].w = expf(z.w - mref);
+            } else {
+                const float gc = G[R.l[r] * 20 + R.cur[r]];
+                const float4 gv = R.gv[r];
+                e[j][r].x = expf((gv.x - gc) * 0.5f - mref); e[j][r].y = expf((gv.y - gc) * 0.5f - mref);
+                e[j][r].z = expf((gv.z - gc) * 0.5f - mref); e[j][r].w = expf((gv.w - gc) * 0.5f - mref);
+            }
             sm += e[j][r].x; sm += e[j][r].y; sm += e[j][r].z; sm += e[j][r].w;
         }
         sw[j] = wave_sum(sm);
@@ -574,14 +684,30 @@ __device__ __forceinline__ void reverse_rows_dev(const RowLds& lds, RowRegs<GPT>
     float inv[NR], s3w[NR];
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
-        const float S1 = row8_sum(lane < PPDE_NW ? lds.xa[(lane & (PPDE_NW - 1)) * PAS_SB + j] : 0.f);
+        float S1 = row8_sum(lane < PPDE_NW ? lds.xa[(lane & (PPDE_NW - 1)) * PAS_SB + j] : 0.f);
+        if constexpr (REV) {
+            // no admissible entry: nothing leads back. Also reached, silently, when every admissible entry of a capped or
+            // library-restricted row underflows against the fixed reference (mref spans ALL residues, up to 64, and is kept by
+            // design): such a path is rejected, where the forward path would flag PPDE_ERR_NUMERIC
+            if (!(S1 > 0.f && S1 < INFINITY)) { rp.forbid = true; S1 = 1.f; }
+        }
         inv[j] = 1.0f / S1;
         float s3 = 0.f;
 #pragma unroll
         for (int r = 0; r < GPT; ++r) {
             if (!R.valid[r]) continue;
-            s3 += clampp(e[j][r].x * inv[j]); s3 += clampp(e[j][r].y * inv[j]);
-            s3 += clampp(e[j][r].z * inv[j]); s3 += clampp(e[j][r].w * inv[j]);
+            if constexpr (REV && LIB) {             // a forbidden entry loses the clamp's floor again, as in propose_body_dev
+                float4 p;
+                p.x = clampp(e[j][r].x * inv[j]); p.y = clampp(e[j][r].y * inv[j]); p.z = clampp(e[j][r].z * inv[j]); p.w = clampp(e[j][r].w * inv[j]);
+                if (!(ok4[r] & 1u)) p.x = 0.f;
+                if (!(ok4[r] & 2u)) p.y = 0.f;
+                if (!(ok4[r] & 4u)) p.z = 0.f;
+                if (!(ok4[r] & 8u)) p.w = 0.f;
+                s3 += p.x; s3 += p.y; s3 += p.z; s3 += p.w;
+            } else {
+                s3 += clampp(e[j][r].x * inv[j]); s3 += clampp(e[j][r].y * inv[j]);
+                s3 += clampp(e[j][r].z * inv[j]); s3 += clampp(e[j][r].w * inv[j]);
+            }
         }
         s3w[j] = wave_sum(s3);
     }
@@ -592,8 +718,18 @@ __device__ __forceinline__ void reverse_rows_dev(const RowLds& lds, RowRegs<GPT>
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
-        // the recorded move under the reverse proposal: its residue now holds letter ks, so the logit is exactly 0
-        const float pwin = clampp(e0ref * inv[j]);
+        float pwin;
+        if constexpr (REV) {
+            // the move that undoes sub-step s: exp(z_restore - mref) takes the place of e0ref (mref still bounds every logit:
+            // masks only send entries to -inf)
+            bool forbidden;
+            const float zr = restore_logit<LIB>(a, lds, G, ls[j], ks[j], ro[j], rc[j], forbidden);
+            pwin = clampp(expf(zr - mref) * inv[j]);
+            if (forbidden) { pwin = 0.f; rp.forbid = true; }
+        } else {
+            // the recorded move under the reverse proposal: its residue now holds letter ks, so the logit is exactly 0
+            pwin = clampp(e0ref * inv[j]);
+        }
         const float S3 = row8_sum(lane < PPDE_NW ? lds.xb[8 * (lane & (PPDE_NW - 1)) + j] : 0.f);
         log_ratio += logf(clampp(pwin / S3)) - lpf[s0 + j];
     }
@@ -1225,7 +1361,10 @@ __device__ __forceinline__ void accept_stage_path(const PasArgs& a, const RowLds
 
 // Reverse path, accept/reject, records (ppde.py:122-153). Expects lds.G = gradient at the proposal, lds.St = x,
 // R.cur = x's letters, lds.mv / lpf filled by accept_prefetch. On return R.cur holds the proposal's letters.
-template <int GPT, bool DEV = false>
+// REV (reversible mode): the reverse rows are the forward row function read at the undoing moves (reverse_rows above); a path
+// with a forbidden reverse move and a proposal at or over the mutation cap are rejected explicitly (never through the test
+// against u, which can be 0); nothing is reset to the wild type: the cap is a constraint of the target, not a reset.
+template <int GPT, bool DEV = false, bool REV = false, bool LIB = false>
 __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int b, int it,
                                                  const AcceptPrefetch& pf, bool stamp, const float mref = 0.f) {
     const Geom g = a.g;
@@ -1240,22 +1379,25 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
     const int d_cur = pf.dist_cur, d_prop = pf.dist_prop, d_fb = pf.dist_fb;
     PPDE_STAMP(a.dbg, 25, stamp);
     float log_ratio = 0.f;
+    RevPath rp;
+    rp.dist = d_cur; rp.forbid = false;
+    if constexpr (REV) rev_annotate_path(lds, Ub);
     // The reverse rows of a path are independent of each other (gradient at y, states along the recorded path), so
     // up to PAS_SB of them are evaluated per pass: two barriers per pass instead of two per sub-step.
     if constexpr (DEV) {
         const float e0ref = expf(0.f - mref);
         for (int s0 = 0; s0 < Ub; s0 += PAS_SB) {
             const int nrows = Ub - s0;
-            if (nrows >= 3) reverse_rows_dev<GPT, 3>(lds, R, s0, mref, e0ref, log_ratio);
-            else if (nrows == 2) reverse_rows_dev<GPT, 2>(lds, R, s0, mref, e0ref, log_ratio);
-            else reverse_rows_dev<GPT, 1>(lds, R, s0, mref, e0ref, log_ratio);
+            if (nrows >= 3) reverse_rows_dev<GPT, 3, REV, LIB>(a, lds, R, s0, mref, e0ref, log_ratio, rp);
+            else if (nrows == 2) reverse_rows_dev<GPT, 2, REV, LIB>(a, lds, R, s0, mref, e0ref, log_ratio, rp);
+            else reverse_rows_dev<GPT, 1, REV, LIB>(a, lds, R, s0, mref, e0ref, log_ratio, rp);
         }
     } else
     for (int s0 = 0; s0 < Ub; s0 += PAS_SB) {
         const int nrows = Ub - s0;
-        if (nrows >= 3) reverse_rows<GPT, 3>(lds, R, s0, log_ratio);
-        else if (nrows == 2) reverse_rows<GPT, 2>(lds, R, s0, log_ratio);
-        else reverse_rows<GPT, 1>(lds, R, s0, log_ratio);
+        if (nrows >= 3) reverse_rows<GPT, 3, REV, LIB>(a, lds, R, s0, log_ratio, rp);
+        else if (nrows == 2) reverse_rows<GPT, 2, REV, LIB>(a, lds, R, s0, log_ratio, rp);
+        else reverse_rows<GPT, 1, REV, LIB>(a, lds, R, s0, log_ratio, rp);
     }
 
     PPDE_STAMP(a.dbg, 26, stamp);
@@ -1265,7 +1407,7 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
     if (a.reuse) { e_x = cur_e; f_x = cur_f; }
     else finish_energy(a, 0, b, px, e_x, f_x);
     const float log_acc = (e_y - e_x) + log_ratio;
-    const bool acc = expf(log_acc) >= u;
+    const bool acc = REV ? (!rp.forbid & (d_prop < a.thr) & (expf(log_acc) >= u)) : (expf(log_acc) >= u);
     const float e_new = acc ? e_y : e_x, f_new = acc ? f_y : f_x;
 
     PPDE_STAMP(a.dbg, 27, stamp);
@@ -1281,7 +1423,7 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
     }
     const int d_rej = a.paper ? d_fb : d_cur;
     const int dist = __builtin_amdgcn_readfirstlane(acc ? d_prop : d_rej);
-    const bool reset = (!a.paper) & (dist >= a.thr);
+    const bool reset = REV ? false : (!a.paper) & (dist >= a.thr);
     PPDE_STAMP(a.dbg, 28, stamp);
     const bool better = e_new > best_e;             // strict: first index on ties, like torch.max over history
 #pragma unroll
@@ -1340,6 +1482,31 @@ __device__ __forceinline__ void commit_current_row(const PasArgs& a, const RowLd
     }
 }
 
+// The accept kernel of reversible mode: k_accept's sequence (general form only) with the library staged for the reverse rows
+template <int GPT, bool DEV, bool LIB>
+__device__ __forceinline__ void accept_rev_kernel(PasArgs& a) {
+    args_up_front(a);
+    extern __shared__ unsigned char smem_raw[];
+    const RowLds lds = carve_lds(smem_raw, a.g);
+    const int b = a.b_off + blockIdx.x;
+    const bool stamp = blockIdx.x == 0;
+    PPDE_STAMP(a.dbg, 24, stamp);
+    const int it = iteration_of(a);
+    RowRegs<GPT> R;
+    const RowLetters<GPT> rl = row_issue<GPT>(a.g, slot_row(a, 1, b), a.cur + (size_t)b * a.g.Ls, a.wt, R);
+    const uint32_t lw = library_issue<LIB>(a);
+    PPDE_STAMP(a.dbg, 30, stamp);
+    const AcceptPrefetch pf = accept_prefetch(a, lds, b, it);
+    PPDE_STAMP(a.dbg, 31, stamp);
+    accept_stage_path(a, lds, pf);
+    library_stage<LIB>(a, lds, lw);
+    PPDE_STAMP(a.dbg, 32, stamp);
+    // the softmax reference spans every residue: the reverse rows' masks only send entries to -inf, so it still bounds every logit
+    const float mref = row_commit<GPT, DEV>(lds, a.g, rl, R, 0, a.g.L - 1);
+    PPDE_STAMP(a.dbg, 33, stamp);
+    const AcceptOut o = accept_body<GPT, DEV, true, LIB>(a, lds, R, b, it, pf, stamp, mref);
+    if (a.reuse) commit_current_row<GPT>(a, lds, R, b, o, false);
+}
 // DEV: the device-RNG arithmetic of the reverse path (reverse_rows_dev); the specialised instantiations imply it
 template <int GPT, int SPEC = 0, bool DEV = (SPEC != 0)>
 __global__ __launch_bounds__(PPDE_BLOCK) void k_accept(PasArgs a) {
@@ -1363,11 +1530,14 @@ __global__ __launch_bounds__(PPDE_BLOCK) void k_accept(PasArgs a) {
     const AcceptOut o = accept_body<GPT, DEV>(a, lds, R, b, it, pf, stamp, mref);
     if (a.reuse) commit_current_row<GPT>(a, lds, R, b, o, false);
 }
+// reversible mode (ppde_chains_set_reversible): the general kernel only; with a library, launched with pas_lib_lds_bytes more LDS
+template <int GPT, bool DEV, bool LIB>
+__global__ __launch_bounds__(PPDE_BLOCK) void k_accept_rev(PasArgs a) { accept_rev_kernel<GPT, DEV, LIB>(a); }
 
 // Accept phase of iteration `it` and forward path of iteration `it + 1` in one launch (gradient reuse only): an
 // accepted chain already has its next gradient row staged; a rejected / reset chain re-stages the row it falls
 // back to. Saves a launch boundary and a row staging per iteration.
-template <int GPT, int SPEC, bool LIB>
+template <int GPT, int SPEC, bool LIB, bool REV = false>
 __device__ __forceinline__ void accept_propose_kernel(PasArgs& a) {
     args_up_front(a);
     pin_config<SPEC>(a);
@@ -1385,9 +1555,9 @@ __device__ __forceinline__ void accept_propose_kernel(PasArgs& a) {
     const AcceptPrefetch pf = accept_prefetch(a, lds, b, it);
     const ProposePrefetch<GPT> pp = propose_prefetch<GPT, false>(a, lds, b, it + 1);
     accept_stage_path(a, lds, pf);
-    library_stage<LIB>(a, lds, lw);                  // (the accept phase never reads it: no masks on the way back)
+    library_stage<LIB>(a, lds, lw);                  // (staged once for both phases; the accept phase reads it in reversible mode only)
     const float mref_y = row_commit<GPT, true>(lds, g, rl, R, 0, g.L - 1);
-    const AcceptOut o = accept_body<GPT, true>(a, lds, R, b, it, pf, stamp, mref_y);
+    const AcceptOut o = accept_body<GPT, true, REV, LIB>(a, lds, R, b, it, pf, stamp, mref_y);
     // ---- the state and gradient the chain continues from
     const uint8_t* rej = a.paper ? a.fb_state + (size_t)b * a.fb_state_stride : nullptr;
     __syncthreads();                                 // everyone is done reading lds.G / lds.St of the accept phase
@@ -1430,6 +1600,8 @@ template <int GPT, int SPEC = 0>
 __global__ __launch_bounds__(PPDE_BLOCK) void k_accept_propose(PasArgs a) { accept_propose_kernel<GPT, SPEC, false>(a); }
 template <int GPT>
 __global__ __launch_bounds__(PPDE_BLOCK) void k_accept_propose_lib(PasArgs a) { accept_propose_kernel<GPT, 0, true>(a); }
+template <int GPT, bool LIB>
+__global__ __launch_bounds__(PPDE_BLOCK) void k_accept_propose_rev(PasArgs a) { accept_propose_kernel<GPT, 0, LIB, true>(a); }
 
 // history row 0 and the running best from the initial population (ppde.py:38-47): one wave per chain
 __global__ void k_init_chain(PasArgs a) {

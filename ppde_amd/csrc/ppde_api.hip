@@ -1192,6 +1192,7 @@ struct ppde_chains {
     long long n_replayed_steps = 0, n_eager_steps = 0;
     std::vector<void*> allocs;
     uint32_t* allowed = nullptr;                 // design library [L] (ppde_chains_set_library), owned here; NULL = none
+    bool reversible = false;                     // ppde_chains_set_reversible: the accept phases run the *_rev kernels
 };
 
 static PasArgs chain_args(const ppde_chains* c) {
@@ -1234,8 +1235,11 @@ enum ChainKernel { KP_PROPOSE, KP_ACCEPT, KP_ACCEPT_PROPOSE };
 static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs& a, int n_sub, hipStream_t s) {
     const ppde_model* m = c->m;
     // a run with a design library: the forward paths go to the general *_lib kernels with room for the words in LDS; the
-    // accept kernel (no masks on the way back) and every run without a library keep their instantiations and LDS size
-    const bool lib = a.allowed != nullptr && which != KP_ACCEPT;
+    // accept kernel (no masks on the way back in the default mode) and every run without a library keep their instantiations
+    // and LDS size
+    // (reversible mode: the reverse rows take the library too, so its accept kernel stages the words as well)
+    const bool rev = c->reversible && which != KP_PROPOSE;
+    const bool lib = a.allowed != nullptr && (which != KP_ACCEPT || rev);
     const size_t lds = pas_lds_bytes(m->g) + (lib ? pas_lib_lds_bytes(m->g) : 0);
     const int gpt = (m->g.N / 4 + PPDE_BLOCK - 1) / PPDE_BLOCK;
     // specialised instantiation for the common configurations (pas.h pin_config), the general kernel otherwise
@@ -1268,6 +1272,12 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
                         else hipLaunchKernelGGL(K, dim3(n_sub), dim3(PPDE_BLOCK), lds, s, a); } while (0)
     with_gpt([&](auto G) {
         constexpr int GP = decltype(G)::value;
+        if (rev) {                                   // general instantiations only; the forward path keeps its kernels
+            if (which == KP_ACCEPT_PROPOSE) { if (lib) PPDE_CL((k_accept_propose_rev<GP, true>)); else PPDE_CL((k_accept_propose_rev<GP, false>)); }
+            else if (a.rng_mode == 1) { if (lib) PPDE_CL((k_accept_rev<GP, true, true>)); else PPDE_CL((k_accept_rev<GP, true, false>)); }
+            else { if (lib) PPDE_CL((k_accept_rev<GP, false, true>)); else PPDE_CL((k_accept_rev<GP, false, false>)); }
+            return;
+        }
         if (lib) {
             if (which == KP_ACCEPT_PROPOSE) PPDE_CL((k_accept_propose_lib<GP>));
             else if (a.rng_mode == 0) PPDE_CL((k_propose_lib<GP, true>));
@@ -1524,6 +1534,15 @@ int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host) {
     }
     if (c->allowed) hipFree(c->allowed);
     c->allowed = d;
+    return PPDE_OK;
+}
+
+int ppde_chains_set_reversible(ppde_chains* c, int on) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_reversible: the mode must be set before ppde_chains_init (its graphs hold the kernel choice)");
+    ARGCHK(!(on && c->cfg.paper_results), "ppde_chains_set_reversible: paper_results restarts a rejected chain from its initial state, "
+                                          "which is no Metropolis step; the two cannot be combined");
+    c->reversible = on != 0;
     return PPDE_OK;
 }
 

@@ -133,6 +133,19 @@ def build_library(wt_idx, window=None, sites=None, exclude="", entries=None):
     return out
 
 
+def check_population(allowed, idx):
+    """ValueError if a state of idx [n, L] holds a letter outside the library at an OPEN residue. Reversible mode refuses such a
+    population: the residue could never move (the move back to that letter is forbidden, so every path through it is rejected)."""
+    ok = as_bool(allowed)
+    idx = np.asarray(idx).astype(np.int64)
+    opened = np.flatnonzero(ok.any(1))
+    bad = ~ok[opened[None, :], idx[:, opened]]
+    if bad.any():
+        b, j = np.argwhere(bad)[0]
+        raise ValueError(f"design library: chain {int(b)} starts with letter {ALPHABET[int(idx[b, opened[j]])]} at open residue "
+                         f"{int(opened[j])}, which the library does not hold; in reversible mode that residue could never move")
+
+
 def as_words(mask, L=None):
     """uint32 [L] from uint32 [L] or bool [L, 20]."""
     m = np.asarray(mask)

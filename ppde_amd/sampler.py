@@ -24,6 +24,12 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         [min_pos, max_pos] is frozen in it and the chains run over the full range, so nothing in such a run
                         relies on the range mask (which leaks 2^-23 per masked entry, as in the reference). Every rank of a
                         sharded run passes the same library.
+    ppde_reversible     False (default): the reference's accept ratio, whose stationary law is not exp(energy)/Z (it scores the
+                        reverse move at the index the forward move chose, ppde.py:128-132). True: a Metropolis-Hastings step of the
+                        same forward proposal (include/ppde_hip.h, ppde_chains_set_reversible): the chains sample
+                        exp(energy) / Z over the library, with nmut_threshold as a constraint (dist < threshold) instead of a
+                        reset. Such a run always has a library (all letters over [min_pos, max_pos] when none is given), so the
+                        restriction is hard; paper_results and an initial population outside the library are refused.
     ppde_shard          False (default). True with torch.distributed initialised: chains are split over ranks
                         and gathered at the end (one RCCL all_gather); every rank returns the full result.
 """
@@ -77,6 +83,12 @@ class Chains:
         with torch.cuda.device(self.model.device):
             _hip.check(self.lib.ppde_chains_set_library(self.handle, _hip.ptr(words)))
         self.library = words
+
+    def set_reversible(self, on=True):
+        """Reversible mode (include/ppde_hip.h, ppde_chains_set_reversible): the accept phase scores the moves that undo the
+        path under the forward row function, so the chains sample exp(energy)/Z over the library. Only before init()."""
+        _hip.check(self.lib.ppde_chains_set_reversible(self.handle, int(bool(on))))
+        self.reversible = bool(on)
 
     def init(self, idx0):
         idx0 = idx0.to(self.model.device, torch.uint8).contiguous()
@@ -191,6 +203,10 @@ class PPDE_PAS(BaseSampler):
         self.shard = getattr(args, "ppde_shard", False)
         self.trace = getattr(args, "ppde_trace", False)
         self.library = getattr(args, "ppde_library", None)
+        self.reversible = bool(getattr(args, "ppde_reversible", False))
+        if self.reversible and self.paper_results:
+            raise ValueError("ppde_reversible: paper_results restarts a rejected chain from its initial state, which is no "
+                             "Metropolis step; the two cannot be combined")
         self.noise_bytes = getattr(args, "ppde_noise_bytes", 96 << 20)   # host->device noise is uploaded in chunks of about this size
         self.last_chains = None
         self.timings = {}       # seconds of the last run(): setup (chains + hipGraph capture), iterations, log path, collect
@@ -206,6 +222,13 @@ class PPDE_PAS(BaseSampler):
                             "there is no generic torch fallback")
         n_global, L = int(initial_population.size(0)), int(initial_population.size(1))
         min_pos, max_pos = int(min_pos), int(max_pos)
+        lib_words = None
+        if self.reversible:
+            # a reversible run always has a library, the range folded in: the restriction is hard and the law exact. The
+            # population is checked on the host, before anything touches the device.
+            lib = design_library.full_library(L) if self.library is None else design_library.as_words(self.library, L)
+            lib_words = design_library.fold_range(lib, min_pos, max_pos)
+            design_library.check_population(lib_words, initial_population.detach().argmax(-1).cpu().numpy())
         random_idx = np.random.randint(0, n_global)                       # ppde.py:37 (same numpy RNG consumption)
         rank, ws = world() if self.shard else (0, 1)
         comm = self.shard and collectives_active()        # (ws > 1, or the one-rank rehearsal of the RCCL path)
@@ -224,8 +247,7 @@ class PPDE_PAS(BaseSampler):
                   "another trajectory.", file=sys.stderr, flush=True)
         t_begin = time.perf_counter()
         t_log = 0.0
-        lib_words = None
-        if self.library is not None:
+        if self.library is not None and not self.reversible:
             # the range goes INTO the library (exact) and the chains run over the full range: no entry of a library run is
             # masked by the leaky range mask. The same words on every rank.
             lib_words = design_library.fold_range(design_library.as_words(self.library, L), min_pos, max_pos)
@@ -237,6 +259,8 @@ class PPDE_PAS(BaseSampler):
         self.last_chains = chains
         if lib_words is not None:
             chains.set_library(lib_words)
+        if self.reversible:
+            chains.set_reversible(True)
         chains.init(idx0[lo:hi])
 
         def gathered(a):

@@ -10,7 +10,8 @@ transformer-L | potts+transformer` (the ESM-2 checkpoint must be in <hub_dir>/ch
 the MSA-Transformer scoring are out of scope.
 
 Extra flags: --ppde_rng {torch,philox}, --ppde_seed, --ppde_reuse_grad {0,1}, --ppde_shard (with torchrun), --ppde_full_grad,
---ppde_timing; design library (the letters the sampler may propose per residue): --ppde_sites, --ppde_exclude, --ppde_library.
+--ppde_timing; design library (the letters the sampler may propose per residue): --ppde_sites, --ppde_exclude, --ppde_library;
+--ppde_reversible (chains that sample exp(energy)/Z over the library).
 """
 import argparse
 import datetime
@@ -194,6 +195,11 @@ def build_parser():
                     help="file of lines '<pos> <letters>' ('#' comments): the letters that may be proposed at each listed residue, "
                          "unlisted residues frozen. Replaces --ppde_sites; --ppde_exclude still applies on top. The wild-type "
                          "letter of an open site is always kept")
+    pp.add_argument("--ppde_reversible", action="store_true",
+                    help="accept with the Metropolis-Hastings ratio of the forward proposal instead of the reference's (which scores "
+                         "the reverse move at the forward index): the chains sample exp(energy)/Z over the design library (all "
+                         "letters of the window when none is given), --nmut_threshold becomes a constraint instead of a reset. "
+                         "Not with --paper_results")
     return parser
 
 
