@@ -1,0 +1,346 @@
+"""The transformer expert stage by stage: a plain torch restatement of the architecture in the header of
+oracle/esm_oracle.py, written so that every stage can be evaluated from GIVEN inputs (the device's own: teacher forcing),
+in fp64 (the reference) or in fp32 with the fp16 rounding points of `EsmOracle(half_points=True)` (`half=True`: used ONLY
+as the yardstick -- how far an evaluation that rounds where the device rounds lies from fp64 -- never as the reference).
+
+The matrices enter every evaluation at their fp16 values (that quantisation is the specification: the device multiplies
+fp16 copies); biases, layer-norm gains and the rotary tables are not quantised. Stages, with the buffer ids of
+ppde_debug_transformer_read:
+
+  A   xin_i (0)            -> q|k|v_i (1)                    LN1, the fused q|k|v GEMM, q scaling
+  B   xin_i, q|k|v_i       -> xmid_i (3)                     rotary, attention, output projection, residual
+  B'  q|k|v of a layer     -> ctx (10)                       the attention alone (the buffer is shared by the layers and the
+                                                             backward does not write it: after an evaluation, with or without
+                                                             the gradient, it holds the LAST layer's)
+  C   xmid_i               -> GELU' (4), xin_{i+1} / xlast (5)   LN2, fc1, GELU, fc2, residual
+  D   xlast                -> logits (6)                     final LN, head
+  E   logits, tokens       -> score, d logits (7)            tf_score
+  F   d embedding (8)      -> d tokens (9)                   the tied embedding GEMM
+  G   d tokens, logits     -> gradient on the Potts one-hot  tf_finish_grad: G[token(a)] + log_softmax(logits)[token(a)]
+
+`model()` is the whole network under autograd; it yields what no stage can be fed: d q|k|v of layer 0 (11; the q third is the
+gradient w.r.t. the projection BEFORE the q scaling, as the device stores it), d embedding (8) and the gradient.
+
+Rounding points of the half evaluation beyond EsmOracle's, each one the device's own (found by reading tf.h):
+  * GELU' is stored in fp16 by the forward GEMM and multiplied into the fp16 gradient by the backward: the
+    factor is rounded once more than autograd of the oracle's GELU would (`gelu_grad_fp16`).
+  * the energy is the score minus the wild type's, subtracted in fp32 (stage E's `wt_score`).
+
+`mut` (a `Mut`) plants ONE fault of the kind a kernel could have into an evaluation; tests/test_transformer_stages_cpu.py
+shows that each lands far outside the bound the GPU tests apply."""
+import collections
+import math
+
+import numpy as np
+import torch
+
+import esm_oracle as eo
+
+F64, F32 = torch.float64, torch.float32
+TAIL = 128            # rows from here on exist only in the 256-residue attention kernels
+MARGIN = 4.0          # bound = MARGIN x yardstick (2: the larger of two draws of the same rounding process; 2: margin)
+
+Mut = collections.namedtuple("Mut", "name head chain", defaults=(None, None))
+
+
+def _h(t, half):
+    return t.half().to(t.dtype) if half else t
+
+
+class Params:
+    """The state dict as the stages read it. fp16_matrices=False (true fp32 matrices) exists for the identity with
+    EsmOracle(half_points=False) only."""
+
+    def __init__(self, state, n_layers, dim, heads, fp16_matrices=True):
+        self.p = {k: torch.as_tensor(np.asarray(v), dtype=F32) for k, v in state.items()}
+        self.n_layers, self.dim, self.heads, self.hd = n_layers, dim, heads, dim // heads
+        self.fp16_matrices = fp16_matrices
+        self.perm = torch.as_tensor(eo.potts_to_esm_index())
+
+    def mat(self, name, dtype):
+        w = self.p[name]
+        return (w.half() if self.fp16_matrices else w).to(dtype)
+
+    def vec(self, name, dtype):
+        return self.p[name].to(dtype)
+
+
+def _pick(mut, mutated, normal):
+    """`mutated` on the (chain, head) pairs the mutant is restricted to ([n, H, ...] tensors), `normal` elsewhere."""
+    if mut.head is None and mut.chain is None:
+        return mutated
+    n, H = normal.shape[:2]
+    m = torch.ones(n, H, dtype=torch.bool)
+    if mut.head is not None:
+        m &= (torch.arange(H) == mut.head)[None, :]
+    if mut.chain is not None:
+        m &= (torch.arange(n) == mut.chain)[:, None]
+    return torch.where(m.reshape(n, H, *([1] * (normal.dim() - 2))), mutated, normal)
+
+
+def _ln(P, x, pre, dtype, mut=None):
+    g, b = P.vec(pre + ".weight", dtype), P.vec(pre + ".bias", dtype)
+    if mut is not None and mut.name == "ln_bwd_mean_const":      # the backward treats the row mean as a constant
+        mu = x.mean(-1, keepdim=True).detach()
+        var = ((x - mu) ** 2).mean(-1, keepdim=True)
+        return (x - mu) * torch.rsqrt(var + 1e-5) * g + b
+    return torch.nn.functional.layer_norm(x, (x.shape[-1],), g, b, 1e-5)
+
+
+def _lin(P, x, pre, dtype, half, bias=True):
+    y = _h(x, half) @ P.mat(pre + ".weight", dtype).t()
+    if bias:
+        y = y + P.vec(pre + ".bias", dtype)
+    return _h(y, half)
+
+
+def _rotary(x, dtype, half, shift_from=None, wrong_grad_sign=False):
+    T, hd = x.shape[-2], x.shape[-1]
+    inv = 1.0 / (10000 ** (torch.arange(0, hd, 2).to(dtype) / hd))
+    pos = torch.arange(T).to(dtype)
+    if shift_from is not None:
+        pos = pos + (torch.arange(T) >= shift_from).to(dtype)
+    fr = torch.outer(pos, inv)
+    emb = torch.cat((fr, fr), -1)
+    cos, sin = emb.cos(), emb.sin()
+    rot = lambda t: torch.cat((-t[..., hd // 2:], t[..., : hd // 2]), -1)
+    y = x * cos + rot(x) * sin
+    if wrong_grad_sign:                                            # same value; the gradient of the rotation by -angle
+        y = (x * cos - rot(x) * sin) + (2.0 * rot(x) * sin).detach()
+    return _h(y, half)
+
+
+class _SoftmaxRowsumCut(torch.autograd.Function):
+    """softmax whose backward sums dP o P over the first `keep` keys only (the partial last key tile left out)."""
+
+    @staticmethod
+    def forward(ctx, s, keep):
+        p = torch.softmax(s, -1)
+        ctx.save_for_backward(p)
+        ctx.keep = keep
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        p, = ctx.saved_tensors
+        return p * (dp - (dp * p)[..., : ctx.keep].sum(-1, keepdim=True)), None
+
+
+class _GeluStoredGrad(torch.autograd.Function):
+    """GELU of an fp16-valued pre-activation, rounded to fp16; the backward multiplies the fp16 gradient by GELU' ROUNDED TO
+    fp16, which is what the forward GEMM stores and the backward GEMM's epilogue reads (tf_gelu_both, TF_EPI_GELU_BWD)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(_h(gelu_grad(x), True))
+        return _h(gelu(x), True)
+
+    @staticmethod
+    def backward(ctx, g):
+        gp, = ctx.saved_tensors
+        return _h(g, True) * gp
+
+
+def gelu(x):
+    return x * 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def gelu_grad(x):
+    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0))) + x * torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+
+
+def _act(x, half, gelu_grad_fp16):
+    if half and gelu_grad_fp16:
+        return _GeluStoredGrad.apply(x)
+    return _h(gelu(x), half)
+
+
+# ---- the stages -----------------------------------------------------------------------------------------------------
+def qkv_unscaled(P, i, xin, dtype=F64, half=False, mut=None):
+    """LN1 and the three projections, q not yet scaled: [n, L, 3 dim]."""
+    pre = f"layers.{i}."
+    y = _ln(P, xin.to(dtype), pre + "self_attn_layer_norm", dtype, mut)
+    return torch.cat([_lin(P, y, pre + f"self_attn.{nm}_proj", dtype, half) for nm in "qkv"], -1)
+
+
+def scale_q(P, raw, half=False, mut=None):
+    D = P.dim
+    ql = raw[..., :D]
+    q = ql * (P.hd ** -0.5)
+    if mut is not None and mut.name == "dq_no_scale":              # the gradient passes the scaling with factor 1
+        q = ql + (q - ql).detach()
+    return torch.cat((_h(q, half), raw[..., D:]), -1)
+
+
+def stage_a(P, i, xin, dtype=F64, half=False, mut=None):
+    return scale_q(P, qkv_unscaled(P, i, xin, dtype, half, mut), half, mut)
+
+
+def attention(P, qkv, dtype=F64, half=False, mut=None):
+    """Stage B': q|k|v [n, L, 3 dim] (q scaled) -> ctx [n, L, dim]."""
+    qkv = qkv.to(dtype)
+    n, L, _ = qkv.shape
+    H, hd, D = P.heads, P.hd, P.dim
+    name = mut.name if mut is not None else None
+    sp = lambda t: t.reshape(n, L, H, hd).transpose(1, 2)
+    q, k, v = (sp(qkv[..., j * D:(j + 1) * D]) for j in range(3))
+    qr, kr = _rotary(q, dtype, half), _rotary(k, dtype, half)
+    if name == "rope_shift_tail":                                  # rows >= 128 rotated by the next row's angle
+        qr, kr = _pick(mut, _rotary(q, dtype, half, TAIL), qr), _pick(mut, _rotary(k, dtype, half, TAIL), kr)
+    if name == "drot_sign_dk":
+        kr = _pick(mut, _rotary(k, dtype, half, wrong_grad_sign=True), kr)
+    s = qr @ kr.transpose(-1, -2)
+    if name == "dk_no_tail":                                       # dK lacks the last query tile's contribution
+        s = _pick(mut, torch.cat((s[..., :TAIL, :], qr[..., TAIL:, :] @ kr.detach().transpose(-1, -2)), -2), s)
+    s = _h(s, half)
+    if name == "tail_no_last_key":                                 # queries of the last tile never see key L - 1
+        sm = s.clone()
+        sm[..., TAIL:, L - 1] = -math.inf
+        s = _pick(mut, sm, s)
+    if name == "pad_keys":                                         # keys L .. 16 ceil(L / 16) - 1 admitted with score 0, v 0
+        pm = torch.softmax(torch.cat((s, s.new_zeros(n, H, L, -L % 16)), -1), -1)[..., :L]
+        p = _pick(mut, pm, torch.softmax(s, -1))
+    elif name == "softmax_bwd_rowsum_no_pad_tile":
+        p = _pick(mut, _SoftmaxRowsumCut.apply(s, L // 16 * 16), torch.softmax(s, -1))
+    else:
+        p = torch.softmax(s, -1)
+    p = _h(p, half)
+    ctx = p @ v
+    if name == "dv_no_tail":
+        ctx = _pick(mut, torch.cat((ctx[..., :TAIL, :], p[..., TAIL:, :] @ v.detach()), -2), ctx)
+    return _h(ctx, half).transpose(1, 2).reshape(n, L, D)
+
+
+def stage_b(P, i, xin, qkv, dtype=F64, half=False, mut=None):
+    """-> (ctx_i, xmid_i)."""
+    ctx = attention(P, qkv, dtype, half, mut)
+    return ctx, _h(xin.to(dtype) + _lin(P, ctx, f"layers.{i}.self_attn.out_proj", dtype, half), half)
+
+
+def stage_c(P, i, xmid, dtype=F64, half=False, mut=None, gelu_grad_fp16=True):
+    """-> (GELU' of the fc1 pre-activation [n, L, ffn], the layer's output stream)."""
+    pre = f"layers.{i}."
+    xmid = xmid.to(dtype)
+    hdn = _lin(P, _ln(P, xmid, pre + "final_layer_norm", dtype, mut), pre + "fc1", dtype, half)
+    act = _act(hdn, half, gelu_grad_fp16)
+    return _h(gelu_grad(hdn.detach()), half), _h(xmid + _lin(P, act, pre + "fc2", dtype, half), half)
+
+
+def stage_d(P, xlast, dtype=F64, half=False, mut=None, gelu_grad_fp16=True):
+    x = _ln(P, xlast.to(dtype), "emb_layer_norm_after", dtype, mut)
+    y = _act(_lin(P, x, "lm_head.dense", dtype, half), half, gelu_grad_fp16)
+    y = _ln(P, y, "lm_head.layer_norm", dtype, mut)
+    return _h(_h(y, half) @ P.mat("embed_tokens.weight", dtype).t() + P.vec("lm_head.bias", dtype), half)
+
+
+def stage_e(P, logits, idx, dtype=F64, half=False, wt_score=None):
+    """logits [n, L, 33], idx [n, L] Potts letters -> (score [n], d score / d logits [n, L, 33]). With wt_score (the
+    device's own wild-type score, an input like the tokens) the first is the energy score - wt_score, which the half
+    evaluation subtracts in fp32 as the device does. The score is ONE number per chain, and in fp32 its distance from fp64
+    is the rounding of the sum over the residues alone: the half evaluation adds them one after the other, the plainest
+    order and one that does not depend on the host's reduction kernels (the device's fixed tree is another order of the
+    same sum)."""
+    lp = torch.log_softmax(logits.to(dtype), -1)
+    onehot = torch.nn.functional.one_hot(P.perm[torch.as_tensor(np.asarray(idx)).long()], 33).to(dtype)
+    rows = (onehot * lp).sum(-1)                                   # [n, L]: one non-zero term each
+    if half:
+        s = torch.zeros_like(rows[:, 0])
+        for l in range(rows.shape[1]):
+            s = s + rows[:, l]
+    else:
+        s = rows.sum(1)
+    if wt_score is not None:
+        s = s - torch.tensor(float(wt_score), dtype=F64).to(dtype)
+    return s, _h(onehot - lp.exp(), half)
+
+
+def stage_f(P, demb, dtype=F64, half=False):
+    """d score / d (one-hot @ E) [n, L, dim] -> d score / d tokens [n, L, 33] through the embedding."""
+    return _h(_h(demb.to(dtype), half) @ P.mat("embed_tokens.weight", dtype).t(), half)
+
+
+def stage_g(P, dtok, logits, dtype=F64, half=False):
+    """-> the gradient on the Potts one-hot [n, L, 20]: the path through the network plus the explicit x in
+    sum x * log_softmax (tf_score's gdirect, computed from the fp16 logits in fp32 and never rounded)."""
+    return dtok.to(dtype)[..., P.perm] + torch.log_softmax(logits.to(dtype), -1)[..., P.perm]
+
+
+def model(P, idx, dtype=F64, half=False, mut=None, gelu_grad_fp16=True, want_grad=True):
+    """The whole network on Potts letters idx [n, L]. Returns a dict: score, every stage's output (xin{i}, qkv{i}, ctx{i},
+    xmid{i}, gp{i}, xlast, logits) and, with want_grad, grad [n, L, 20], demb and dqkv0."""
+    idx = torch.as_tensor(np.asarray(idx)).long()
+    x_potts = torch.nn.functional.one_hot(idx, 20).to(dtype).requires_grad_(want_grad)
+    Pm = torch.zeros(20, 33, dtype=dtype)
+    Pm[torch.arange(20), P.perm] = 1.0
+    x_esm = x_potts @ Pm
+    emb = _h(x_esm, half) @ P.mat("embed_tokens.weight", dtype)
+    x = _h(_h(emb, half) * eo.TOKEN_DROPOUT_SCALE, half)
+    out, raw0 = {}, None
+    for i in range(P.n_layers):
+        out[f"xin{i}"] = x
+        raw = qkv_unscaled(P, i, x, dtype, half, mut)
+        if i == 0:
+            raw0 = raw
+            if want_grad:
+                raw0.retain_grad()
+        qkv = scale_q(P, raw, half, mut)
+        ctx, x = stage_b(P, i, x, qkv, dtype, half, mut)
+        out[f"qkv{i}"], out[f"ctx{i}"], out[f"xmid{i}"] = qkv, ctx, x
+        out[f"gp{i}"], x = stage_c(P, i, x, dtype, half, mut, gelu_grad_fp16)
+    out["xlast"] = x
+    lg = out["logits"] = stage_d(P, x, dtype, half, mut, gelu_grad_fp16)
+    s = (x_esm * torch.log_softmax(lg, -1)).sum(dim=[1, 2])
+    if want_grad:
+        emb.retain_grad()
+        s.sum().backward()
+        out["grad"], out["demb"], out["dqkv0"] = x_potts.grad, emb.grad, raw0.grad
+    out["score"] = s
+    return {k: v.detach() for k, v in out.items()}
+
+
+# ---- measures (no row, head, chain or stage is exempted) -------------------------------------------------------------
+def _t(a):
+    return torch.as_tensor(np.asarray(a)).to(F64)
+
+
+def row_rel(got, ref):
+    """Activations and teacher-forced outputs [n, L, d]: the largest ||got_row - ref_row|| / ||ref_row||."""
+    got, ref = _t(got), _t(ref)
+    return float(((got - ref).norm(dim=-1) / ref.norm(dim=-1)).max())
+
+
+def slice_rel(got, ref, hd, thirds=1):
+    """ctx [n, L, dim] (thirds=1) and d q|k|v [n, L, 3 dim] (thirds=3): the error of every (row, head slice), per third of
+    q|k|v, over that third's largest row norm in the chain."""
+    got, ref = _t(got), _t(ref)
+    n, L, W = ref.shape
+    D = W // thirds
+    worst = 0.0
+    for j in range(thirds):
+        g, r = got[..., j * D:(j + 1) * D], ref[..., j * D:(j + 1) * D]
+        err = (g - r).reshape(n, L, D // hd, hd).norm(dim=-1)                       # [n, L, H]
+        worst = max(worst, float((err / r.norm(dim=-1).amax(dim=1)[:, None, None]).max()))
+    return worst
+
+
+def chain_rel(got, ref):
+    """Gradient and d embedding [n, L, d]: per chain, the largest row error over that chain's largest row norm."""
+    got, ref = _t(got), _t(ref)
+    return float(((got - ref).norm(dim=-1).amax(dim=1) / ref.norm(dim=-1).amax(dim=1)).max())
+
+
+def score_rel(got, ref, scale=None):
+    """|delta| / |s| (scale: the raw scores, where got / ref are energies against the wild type)."""
+    got, ref = _t(got), _t(ref)
+    return float(((got - ref).abs() / (_t(scale) if scale is not None else ref).abs()).max())
+
+
+def chains_like_the_parity_test(L, n, seed=3):
+    """The wild type and n chains perturbed as in test_score_and_gradient_vs_oracle: chain b differs at 3 b residues."""
+    wt = np.random.default_rng(seed).integers(0, 20, L).astype(np.uint8)
+    rng = np.random.default_rng(L)
+    idx = np.tile(wt, (n, 1))
+    for b in range(1, n):
+        pos = rng.choice(L, size=min(L, 3 * b), replace=False)
+        idx[b, pos] = rng.integers(0, 20, len(pos))
+    return wt, idx
