@@ -239,6 +239,40 @@ int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host /* [L] 
  * reverse move is forbidden). */
 int ppde_chains_set_reversible(ppde_chains* c, int on);
 
+/* Parallel tempering (off by default; needs reversible mode, where the law at an inverse temperature beta is defined:
+ * exp(beta E)/Z_beta over the library). beta_host [n_rungs] is a ladder beta[0] > beta[1] > ... > beta[R-1] > 0, R = n_rungs.
+ *   ensembles: R chains with consecutive GLOBAL indices g = chain_offset + local index; chain g belongs to ensemble g / R and
+ *     starts on rung g % R;
+ *   a chain on rung r runs the reversible iteration above on the energy beta_r * E: every row, forward and reverse, is
+ *     row(beta g, state) with logits beta * ((g[l,k] - g[l,state_l]) * 0.5f) in this order of operations (beta = 1 gives the
+ *     untempered bits, a power of two commutes with the rounding); masks, library, clamp and zeroing as before;
+ *     log_acc = beta * (e_y - e_x) + sum_s (logp_rev_s - logp_fwd_s), accepted when exp(log_acc) >= u; the explicit rejections
+ *     and the mutation cap as a constraint are unchanged. Philox counters and the variates consumed do not change;
+ *   histories, best states, peek and collect hold the UNTEMPERED energy and fitness; "best" is the largest E on any rung;
+ *   swap events: after the accept phase of iteration `it` (0-based) when swap_every > 0 and (it + 1) % swap_every == 0;
+ *     event s = (it + 1) / swap_every - 1 pairs, in every ensemble, the rungs (r, r + 1) with r = s (mod 2), r + 1 < R;
+ *   swap rule: a = the chain on rung r, b = the chain on rung r + 1, d = (beta_r - beta_{r+1}) * (E_b - E_a) in fp32 on the
+ *     post-accept energies, accepted when expf(d) >= u, u the uniform of Philox word .x at counter (global index of the
+ *     ensemble's first chain, it, 0x40000000, r), a stream the chain kernels never use. A swap exchanges TEMPERATURES (beta,
+ *     rung, and the ensemble's rung -> chain map), never states, gradients, records or histories;
+ *   every joint kernel (the product of the rungs' kernels, then the swap) keeps prod_r exp(beta_r E(x_r)) / Z_r invariant;
+ *   results do not depend on the sharding (Philox is keyed by global indices). swap_every = 0: a ladder without exchange.
+ * A tempering run enqueues propose, experts, accept, swap per iteration: the fused accept + propose launch is not used (the
+ * next proposal must see the post-swap beta, the swap the post-accept energy). Valid between ppde_chains_create and
+ * ppde_chains_init; n_rungs = 0 or NULL clears it. PPDE_ERR_INVALID with a message, the object unchanged: after init;
+ * reversible mode not on; n_rungs > 64; a beta that is not finite and positive, or a ladder not strictly decreasing;
+ * swap_every < 0; n_chains or chain_offset no multiple of n_rungs; n_streams > 1. While it is set,
+ * ppde_chains_set_reversible(c, 0) is PPDE_ERR_INVALID. The ladder is copied; the chains own the device arrays. */
+int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_host, int swap_every);
+
+/* Where the temperatures are now: rung host int32 [n], beta host fp32 [n] (per chain), swap_attempts / swap_accepts host
+ * int64 [n / R][R - 1] per (ensemble, pair of rungs r, r + 1). Any pointer may be NULL. Synchronises. PPDE_ERR_INVALID
+ * without tempering. */
+int ppde_chains_tempering_state(ppde_chains* c, int32_t* rung, float* beta, int64_t* swap_attempts, int64_t* swap_accepts);
+
+/* rung_history host uint8 [steps_done + 1, n]: the rung each chain held after every iteration (row 0: the start). */
+int ppde_chains_tempering_history(ppde_chains* c, uint8_t* rung_history);
+
 /* Start from idx0_dev [n, L] (ppde.py:35-47): evaluates the initial energies, fills history row 0. */
 int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev);
 

@@ -58,6 +58,9 @@ SIGNATURES = {
     "ppde_chains_destroy": (_i, [_p]),
     "ppde_chains_set_library": (_i, [_p, _p]),
     "ppde_chains_set_reversible": (_i, [_p, _i]),
+    "ppde_chains_set_tempering": (_i, [_p, _i, _p, _i]),
+    "ppde_chains_tempering_state": (_i, [_p, _p, _p, _p, _p]),
+    "ppde_chains_tempering_history": (_i, [_p, _p]),
     "ppde_chains_init": (_i, [_p, _p]),
     "ppde_chains_run": (_i, [_p, _i, _p, _p, _p, _p]),
     "ppde_chains_sync": (_i, [_p]),

@@ -79,6 +79,14 @@ struct PasArgs {
     // = no library. Forward paths only (ppde.py:98-110); the reverse path takes no masks, as the reference treats its own two
     // (in reversible mode the reverse rows are forward rows and take it too).
     const uint32_t* allowed;    // [L]
+    // parallel tempering (ppde_chains_set_tempering): NULL / 0 = none. The *_temp chain kernels read beta[b] only; k_swap owns the rest.
+    float* beta;                // [n]        inverse temperature of the rung each chain holds
+    int* rung;                  // [n]        that rung
+    int* slot;                  // [n/R][R]   rung -> chain (local index)
+    long long* swap_attempts;   // [n/R][R-1] per (ensemble, pair of rungs r, r+1)
+    long long* swap_accepts;
+    uint8_t* rung_hist;         // [T+1][n]
+    int n_rungs, swap_every;
 };
 
 // LDS of a chain workgroup: the gradient row (float4[N/4]), the letters of the start state and of the wild
@@ -331,9 +339,10 @@ __device__ __forceinline__ RowLetters<GPT> row_issue(const Geom& g, const RowSrc
 // whatever the reference is. (Beyond 64 it stops following the spread: logits up to 64 + 88 still evaluate, and what underflows
 // against a reference of 64 lies below the 2^-23 clamp floor of the categorical anyway.) The per-wave extrema travel through
 // the staging barrier that is there anyway.
-template <int GPT, bool SPREAD = false>
+// TEMP (tempering): the logits are beta * ((g - g[current letter]) / 2), so the reference is beta * (spread / 2): beta > 0, the bound holds.
+template <int GPT, bool SPREAD = false, bool TEMP = false>
 __device__ __forceinline__ float row_commit(const RowLds& lds, const Geom& g, const RowLetters<GPT>& q, RowRegs<GPT>& R,
-                                            int lo = 0, int hi = 0) {
+                                            int lo = 0, int hi = 0, float beta = 1.f) {
     const int tid = threadIdx.x;
     float mx = -INFINITY, mn = INFINITY;
 #pragma unroll
@@ -366,6 +375,7 @@ __device__ __forceinline__ float row_commit(const RowLds& lds, const Geom& g, co
         const float a = lane < PPDE_NW ? lds.xb[lane & (PPDE_NW - 1)] : -INFINITY;
         const float b = lane < PPDE_NW ? -lds.xb[PPDE_NW + (lane & (PPDE_NW - 1))] : -INFINITY;
         const float spread = row8_max(a) + row8_max(b);            // max - min (NaN / inf rows end in the S1 check of the sub-steps)
+        if constexpr (TEMP) return fminf(fmaxf(beta * (spread * 0.5f), 0.f), 64.f);
         return fminf(fmaxf(spread * 0.5f, 0.f), 64.f);
     }
     return 0.f;
@@ -494,21 +504,22 @@ __device__ __forceinline__ void rev_annotate_path(const RowLds& lds, int Ub) {
     __syncthreads();
 }
 // logit of the move (l, cur -> old) in row(g, state): the scalar form of forward_logits<LIB> for one entry
-template <bool LIB>
+template <bool LIB, bool TEMP = false>
 __device__ __forceinline__ float restore_logit(const PasArgs& a, const RowLds& lds, const float* G, int l, int cur, int old,
-                                               bool capped, bool& forbidden) {
+                                               bool capped, bool& forbidden, float beta = 1.f) {
     const int wt = lds.Wt[l];
     const bool outside = (l < a.min_pos) | (l > a.max_pos);
     const bool revertible = capped & (cur != wt);
     bool masked = outside | (capped & !(revertible & (old == wt)));
     forbidden = false;
     if constexpr (LIB) { forbidden = !((lds.Al[l] >> old) & 1u); masked |= forbidden; }
-    const float z = (G[l * 20 + old] - G[l * 20 + cur]) * 0.5f;
+    float z = (G[l * 20 + old] - G[l * 20 + cur]) * 0.5f;
+    if constexpr (TEMP) z = beta * z;
     return masked ? -INFINITY : z;
 }
-template <int GPT, int NR, bool REV = false, bool LIB = false>
+template <int GPT, int NR, bool REV = false, bool LIB = false, bool TEMP = false>
 __device__ __forceinline__ void reverse_rows(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int s0, float& log_ratio,
-                                             RevPath& rp) {
+                                             RevPath& rp, float beta = 1.f) {
     const int tid = threadIdx.x, lane = tid & 63;
     const float* G = (const float*)lds.G;
     const float* lpf = (const float*)(lds.mv + 128);
@@ -535,7 +546,7 @@ __device__ __forceinline__ void reverse_rows(const PasArgs& a, const RowLds& lds
         for (int r = 0; r < GPT; ++r) {
             if (R.l[r] == ls) R.cur[r] = ks;            // state after sub-step s0 + j
             if constexpr (REV) {
-                z[j][r] = forward_logits<LIB>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], rc[j], ok4[r]);
+                z[j][r] = forward_logits<LIB, TEMP>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], rc[j], ok4[r], beta);
             } else {
                 const float gc = G[R.l[r] * 20 + R.cur[r]];
                 const float4 gv = R.gv[r];
@@ -584,7 +595,7 @@ __device__ __forceinline__ void reverse_rows(const PasArgs& a, const RowLds& lds
         if constexpr (REV) {
             // the move that undoes sub-step s: the restored letter's own logit in this row
             bool forbidden;
-            const float zr = restore_logit<LIB>(a, lds, G, rl[j], rk[j], ro[j], rc[j], forbidden);
+            const float zr = restore_logit<LIB, TEMP>(a, lds, G, rl[j], rk[j], ro[j], rc[j], forbidden, beta);
             pwin = clampp(expf(zr - m[j]) * inv[j]);
             if (forbidden) { pwin = 0.f; rp.forbid = true; }
         } else {
@@ -605,9 +616,9 @@ __device__ __forceinline__ void reverse_rows(const PasArgs& a, const RowLds& lds
 //  * the rows of a path differ only at the residues the path moves: a wave none of whose lanes holds such a residue
 //    evaluates its exponentials ONCE and uses them for every row (the clamp and the row sums still run per row: the
 //    normalisation differs).
-template <int GPT, int NR, bool REV = false, bool LIB = false>
+template <int GPT, int NR, bool REV = false, bool LIB = false, bool TEMP = false>
 __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int s0, const float mref,
-                                                 const float e0ref, float& log_ratio, RevPath& rp) {
+                                                 const float e0ref, float& log_ratio, RevPath& rp, float beta = 1.f) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* G = (const float*)lds.G;
     const float* lpf = (const float*)(lds.mv + 128);
@@ -647,7 +658,7 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
             e[j][r] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (!R.valid[r]) continue;
             if constexpr (REV) {
-                const float4 z = forward_logits<LIB>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], rc[j], ok4[r]);
+                const float4 z = forward_logits<LIB, TEMP>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], rc[j], ok4[r], beta);
                 e[j][r].x = expf(z.x - mref); e[j][r].y = expf(z.y - mref); e[j][r].z = expf(z.z - mref); e[j][r].w = expf(z.w - mref);
             } else {
                 const float gc = G[R.l[r] * 20 + R.cur[r]];
@@ -723,7 +734,7 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
             // the move that undoes sub-step s: exp(z_restore - mref) takes the place of e0ref (mref still bounds every logit:
             // masks only send entries to -inf)
             bool forbidden;
-            const float zr = restore_logit<LIB>(a, lds, G, ls[j], ks[j], ro[j], rc[j], forbidden);
+            const float zr = restore_logit<LIB, TEMP>(a, lds, G, ls[j], ks[j], ro[j], rc[j], forbidden, beta);
             pwin = clampp(expf(zr - mref) * inv[j]);
             if (forbidden) { pwin = 0.f; rp.forbid = true; }
         } else {
@@ -738,11 +749,14 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
 // logits of one 4-letter group of residue l: (g - g[current letter]) / 2 with the forward masks
 // LIB: ok4 = the design library's bits of these four letters; a forbidden letter's logit is -inf like a masked one's, and
 // (unlike a masked one) its probability is zeroed again behind the clamp by the callers
-template <bool LIB = false>
+// TEMP (tempering): the row of beta * g, formed as beta * ((g - g[current letter]) * 0.5f) in this order: beta = 1 gives the untempered
+// bits and a power-of-two beta commutes with the rounding
+template <bool LIB = false, bool TEMP = false>
 __device__ __forceinline__ float4 forward_logits(const PasArgs& a, const float* G, float4 gv, int l, int kb, int cur, int wt,
-                                                 bool capped, uint32_t ok4 = 15u) {
+                                                 bool capped, uint32_t ok4 = 15u, float beta = 1.f) {
     const float gc = G[l * 20 + cur];
     float4 z = make_float4((gv.x - gc) * 0.5f, (gv.y - gc) * 0.5f, (gv.z - gc) * 0.5f, (gv.w - gc) * 0.5f);
+    if constexpr (TEMP) { z.x = beta * z.x; z.y = beta * z.y; z.z = beta * z.z; z.w = beta * z.w; }
     const bool outside = (l < a.min_pos) | (l > a.max_pos);
     // capped chains may only move a mutated residue back to its wild-type letter (ppde/utils.py:17-28)
     const bool revertible = capped & (cur != wt);
@@ -842,9 +856,9 @@ __device__ __forceinline__ ProposePrefetch<GPT> propose_prefetch(const PasArgs& 
 // rng_mode 0); otherwise p * rcp(q) (device RNG).
 // LIB: a design library is staged in lds.Al: forbidden entries take logit -inf, probability exactly 0 behind the clamp (before
 // the row sum S3 is formed) and never enter the race.
-template <int GPT, bool EXACT, bool LIB = false>
+template <int GPT, bool EXACT, bool LIB = false, bool TEMP = false>
 __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int b, int it, int dist0,
-                                             const ProposePrefetch<GPT>& pp, bool stamp) {
+                                             const ProposePrefetch<GPT>& pp, bool stamp, float beta = 1.f) {
     int dist = dist0;
     const Geom g = a.g;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -869,7 +883,7 @@ __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds
         // ---- logits z = (g - g[current letter]) / 2 with the forward masks (ppde.py:98-104)
         float4 z[GPT];
 #pragma unroll
-        for (int r = 0; r < GPT; ++r) z[r] = forward_logits<LIB>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], capped, ok4[r]);
+        for (int r = 0; r < GPT; ++r) z[r] = forward_logits<LIB, TEMP>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], capped, ok4[r], beta);
         PPDE_STAMP(a.dbg, 10 + 4 * min(s, 1), stamp);
         float m, S1, scale;
         float4 e[GPT];
@@ -1032,9 +1046,9 @@ __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds
 //    is KEPT as row_commit derives it (the spread over the position range, library ignored): forbidden entries only go to
 //    -inf, so it still bounds every logit from above; narrowing it to the open entries would change nothing a run can see but
 //    the rounding of the exponentials, and would break the bit-equality of an all-letters library with no library.
-template <int GPT, bool LIB = false>
+template <int GPT, bool LIB = false, bool TEMP = false>
 __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int b, int it, int dist0,
-                                                 const ProposePrefetch<GPT>& pp, bool stamp, const float mref) {
+                                                 const ProposePrefetch<GPT>& pp, bool stamp, const float mref, float beta = 1.f) {
     int dist = dist0;
     const Geom g = a.g;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1054,7 +1068,7 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
             if (!R.valid[r]) continue;
             uint32_t ok4 = 15u;
             if constexpr (LIB) ok4 = (lds.Al[R.l[r]] >> R.kb[r]) & 15u;
-            const float4 z = forward_logits<LIB>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], capped, ok4);
+            const float4 z = forward_logits<LIB, TEMP>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], capped, ok4, beta);
             lds.Pv[tid + r * PPDE_BLOCK] = make_float4(expf(z.x - mref), expf(z.y - mref), expf(z.z - mref), expf(z.w - mref));
         }
     }
@@ -1069,7 +1083,8 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
             const bool revertible = capped & (cur != wt);
             bool masked = outside | (capped & !(revertible & (k == wt)));
             if constexpr (LIB) masked |= !((lds.Al[l] >> k) & 1u);      // forbidden by the design library
-            const float z = (G[l * 20 + k] - G[l * 20 + cur]) * 0.5f;
+            float z = (G[l * 20 + k] - G[l * 20 + cur]) * 0.5f;
+            if constexpr (TEMP) z = beta * z;
             return masked ? 0.f : expf(z - mref);
         };
         // The lane's residues (lane + 64 r) keep their 20 exponentials in REGISTERS across the sub-steps (LDS stays the
@@ -1223,7 +1238,14 @@ __device__ __forceinline__ void library_stage(const PasArgs& a, const RowLds& ld
     if constexpr (LIB) { if ((int)threadIdx.x < a.g.L) lds.Al[threadIdx.x] = w; }
 }
 
-template <int GPT, bool EXACT, int SPEC, bool LIB>
+// this chain's inverse temperature (tempering): one wave-uniform load next to the row's, off every sub-step's dependent path
+template <bool TEMP>
+__device__ __forceinline__ float beta_issue(const PasArgs& a, int b) {
+    if constexpr (TEMP) return a.beta[b];
+    return 1.f;
+}
+
+template <int GPT, bool EXACT, int SPEC, bool LIB, bool TEMP = false>
 __device__ __forceinline__ void propose_kernel(PasArgs& a) {
     args_up_front(a);
     pin_config<SPEC>(a);
@@ -1236,18 +1258,22 @@ __device__ __forceinline__ void propose_kernel(PasArgs& a) {
     const int it = iteration_of(a);
     const RowLetters<GPT> rl = row_issue<GPT>(a.g, current_grad_row(a, b), a.cur + (size_t)b * a.g.Ls, a.wt, R);
     const uint32_t lw = library_issue<LIB>(a);
+    const float beta = beta_issue<TEMP>(a, b);
     const ProposePrefetch<GPT> pp = propose_prefetch<GPT, EXACT>(a, lds, b, it);
     library_stage<LIB>(a, lds, lw);
-    const float mref = row_commit<GPT, !EXACT>(lds, a.g, rl, R, a.min_pos, a.max_pos);
+    const float mref = row_commit<GPT, !EXACT, TEMP>(lds, a.g, rl, R, a.min_pos, a.max_pos, beta);
     PPDE_STAMP(a.dbg, 9, stamp);
-    if constexpr (EXACT) propose_body<GPT, true, LIB>(a, lds, R, b, it, __builtin_amdgcn_readfirstlane(pp.dist), pp, stamp);
-    else propose_body_dev<GPT, LIB>(a, lds, R, b, it, __builtin_amdgcn_readfirstlane(pp.dist), pp, stamp, mref);
+    if constexpr (EXACT) propose_body<GPT, true, LIB, TEMP>(a, lds, R, b, it, __builtin_amdgcn_readfirstlane(pp.dist), pp, stamp, beta);
+    else propose_body_dev<GPT, LIB, TEMP>(a, lds, R, b, it, __builtin_amdgcn_readfirstlane(pp.dist), pp, stamp, mref, beta);
 }
 template <int GPT, bool EXACT, int SPEC = 0>
 __global__ __launch_bounds__(PPDE_BLOCK) void k_propose(PasArgs a) { propose_kernel<GPT, EXACT, SPEC, false>(a); }
 // with a design library (PasArgs::allowed != NULL): the general kernel only, launched with pas_lib_lds_bytes more LDS
 template <int GPT, bool EXACT>
 __global__ __launch_bounds__(PPDE_BLOCK) void k_propose_lib(PasArgs a) { propose_kernel<GPT, EXACT, 0, true>(a); }
+// tempering (PasArgs::beta != NULL; reversible mode): the general kernel only, its rows those of beta[b] * g
+template <int GPT, bool EXACT, bool LIB>
+__global__ __launch_bounds__(PPDE_BLOCK) void k_propose_temp(PasArgs a) { propose_kernel<GPT, EXACT, 0, LIB, true>(a); }
 
 // ------------------------------------------------------------------------------------------------
 // energy of slot `slot` for chain b (all lanes of the calling wave get the value)
@@ -1364,9 +1390,11 @@ __device__ __forceinline__ void accept_stage_path(const PasArgs& a, const RowLds
 // REV (reversible mode): the reverse rows are the forward row function read at the undoing moves (reverse_rows above); a path
 // with a forbidden reverse move and a proposal at or over the mutation cap are rejected explicitly (never through the test
 // against u, which can be 0); nothing is reset to the wild type: the cap is a constraint of the target, not a reset.
-template <int GPT, bool DEV = false, bool REV = false, bool LIB = false>
+// TEMP (tempering, REV only): the chain targets exp(beta E): reverse rows of beta * g, log_acc = beta * (e_y - e_x) + the path's
+// log-ratio; everything recorded (histories, best, cur_e) stays the untempered energy and fitness.
+template <int GPT, bool DEV = false, bool REV = false, bool LIB = false, bool TEMP = false>
 __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int b, int it,
-                                                 const AcceptPrefetch& pf, bool stamp, const float mref = 0.f) {
+                                                 const AcceptPrefetch& pf, bool stamp, const float mref = 0.f, float beta = 1.f) {
     const Geom g = a.g;
     const int tid = threadIdx.x;
     const int Ub = __builtin_amdgcn_readfirstlane(pf.Ub);
@@ -1388,16 +1416,16 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
         const float e0ref = expf(0.f - mref);
         for (int s0 = 0; s0 < Ub; s0 += PAS_SB) {
             const int nrows = Ub - s0;
-            if (nrows >= 3) reverse_rows_dev<GPT, 3, REV, LIB>(a, lds, R, s0, mref, e0ref, log_ratio, rp);
-            else if (nrows == 2) reverse_rows_dev<GPT, 2, REV, LIB>(a, lds, R, s0, mref, e0ref, log_ratio, rp);
-            else reverse_rows_dev<GPT, 1, REV, LIB>(a, lds, R, s0, mref, e0ref, log_ratio, rp);
+            if (nrows >= 3) reverse_rows_dev<GPT, 3, REV, LIB, TEMP>(a, lds, R, s0, mref, e0ref, log_ratio, rp, beta);
+            else if (nrows == 2) reverse_rows_dev<GPT, 2, REV, LIB, TEMP>(a, lds, R, s0, mref, e0ref, log_ratio, rp, beta);
+            else reverse_rows_dev<GPT, 1, REV, LIB, TEMP>(a, lds, R, s0, mref, e0ref, log_ratio, rp, beta);
         }
     } else
     for (int s0 = 0; s0 < Ub; s0 += PAS_SB) {
         const int nrows = Ub - s0;
-        if (nrows >= 3) reverse_rows<GPT, 3, REV, LIB>(a, lds, R, s0, log_ratio, rp);
-        else if (nrows == 2) reverse_rows<GPT, 2, REV, LIB>(a, lds, R, s0, log_ratio, rp);
-        else reverse_rows<GPT, 1, REV, LIB>(a, lds, R, s0, log_ratio, rp);
+        if (nrows >= 3) reverse_rows<GPT, 3, REV, LIB, TEMP>(a, lds, R, s0, log_ratio, rp, beta);
+        else if (nrows == 2) reverse_rows<GPT, 2, REV, LIB, TEMP>(a, lds, R, s0, log_ratio, rp, beta);
+        else reverse_rows<GPT, 1, REV, LIB, TEMP>(a, lds, R, s0, log_ratio, rp, beta);
     }
 
     PPDE_STAMP(a.dbg, 26, stamp);
@@ -1406,7 +1434,9 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
     finish_energy(a, sloty, b, py, e_y, f_y);
     if (a.reuse) { e_x = cur_e; f_x = cur_f; }
     else finish_energy(a, 0, b, px, e_x, f_x);
-    const float log_acc = (e_y - e_x) + log_ratio;
+    float de = e_y - e_x;
+    if constexpr (TEMP) de = beta * de;
+    const float log_acc = de + log_ratio;
     const bool acc = REV ? (!rp.forbid & (d_prop < a.thr) & (expf(log_acc) >= u)) : (expf(log_acc) >= u);
     const float e_new = acc ? e_y : e_x, f_new = acc ? f_y : f_x;
 
@@ -1483,7 +1513,7 @@ __device__ __forceinline__ void commit_current_row(const PasArgs& a, const RowLd
 }
 
 // The accept kernel of reversible mode: k_accept's sequence (general form only) with the library staged for the reverse rows
-template <int GPT, bool DEV, bool LIB>
+template <int GPT, bool DEV, bool LIB, bool TEMP = false>
 __device__ __forceinline__ void accept_rev_kernel(PasArgs& a) {
     args_up_front(a);
     extern __shared__ unsigned char smem_raw[];
@@ -1495,6 +1525,7 @@ __device__ __forceinline__ void accept_rev_kernel(PasArgs& a) {
     RowRegs<GPT> R;
     const RowLetters<GPT> rl = row_issue<GPT>(a.g, slot_row(a, 1, b), a.cur + (size_t)b * a.g.Ls, a.wt, R);
     const uint32_t lw = library_issue<LIB>(a);
+    const float beta = beta_issue<TEMP>(a, b);
     PPDE_STAMP(a.dbg, 30, stamp);
     const AcceptPrefetch pf = accept_prefetch(a, lds, b, it);
     PPDE_STAMP(a.dbg, 31, stamp);
@@ -1502,9 +1533,9 @@ __device__ __forceinline__ void accept_rev_kernel(PasArgs& a) {
     library_stage<LIB>(a, lds, lw);
     PPDE_STAMP(a.dbg, 32, stamp);
     // the softmax reference spans every residue: the reverse rows' masks only send entries to -inf, so it still bounds every logit
-    const float mref = row_commit<GPT, DEV>(lds, a.g, rl, R, 0, a.g.L - 1);
+    const float mref = row_commit<GPT, DEV, TEMP>(lds, a.g, rl, R, 0, a.g.L - 1, beta);
     PPDE_STAMP(a.dbg, 33, stamp);
-    const AcceptOut o = accept_body<GPT, DEV, true, LIB>(a, lds, R, b, it, pf, stamp, mref);
+    const AcceptOut o = accept_body<GPT, DEV, true, LIB, TEMP>(a, lds, R, b, it, pf, stamp, mref, beta);
     if (a.reuse) commit_current_row<GPT>(a, lds, R, b, o, false);
 }
 // DEV: the device-RNG arithmetic of the reverse path (reverse_rows_dev); the specialised instantiations imply it
@@ -1533,6 +1564,9 @@ __global__ __launch_bounds__(PPDE_BLOCK) void k_accept(PasArgs a) {
 // reversible mode (ppde_chains_set_reversible): the general kernel only; with a library, launched with pas_lib_lds_bytes more LDS
 template <int GPT, bool DEV, bool LIB>
 __global__ __launch_bounds__(PPDE_BLOCK) void k_accept_rev(PasArgs a) { accept_rev_kernel<GPT, DEV, LIB>(a); }
+// tempering: the reversible accept phase on beta[b] * E
+template <int GPT, bool DEV, bool LIB>
+__global__ __launch_bounds__(PPDE_BLOCK) void k_accept_temp(PasArgs a) { accept_rev_kernel<GPT, DEV, LIB, true>(a); }
 
 // Accept phase of iteration `it` and forward path of iteration `it + 1` in one launch (gradient reuse only): an
 // accepted chain already has its next gradient row staged; a rejected / reset chain re-stages the row it falls
@@ -1631,6 +1665,48 @@ __global__ void k_init_chain(PasArgs a) {
 }
 
 __global__ void k_bump(int* it_base, int by) { *it_base += by; }
+
+// Replica exchange (parallel tempering), launched behind the accept phase of EVERY iteration `it` of a tempering run: one thread
+// per (ensemble, rung). Ensembles are R chains with consecutive indices; slot[e][r] is the chain that holds rung r.
+// A swap event happens when swap_every > 0 and (it + 1) % swap_every == 0; event s = (it + 1) / swap_every - 1 pairs the rungs
+// (r, r + 1) with r = s (mod 2). The thread of the pair's LOWER rung owns the pair: with a = slot[r], b = slot[r + 1] it accepts
+// when expf((beta_r - beta_{r+1}) * (E_b - E_a)) >= u, E the post-accept (untempered) energies of this iteration (history row
+// it + 1), u from Philox at (first chain of the ensemble, it, 0x40000000, r) -- a stream the chain kernels never draw from --, and
+// then exchanges the TEMPERATURES (beta, rung, slot), never a state, and counts the attempt. The upper rung's thread does
+// nothing; an unpaired rung's thread owns its slot alone. Every owner then writes its chains' rungs into row it + 1 of rung_hist.
+// No thread reads what another thread of the launch writes.
+__global__ void k_swap(PasArgs a) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= a.n) return;
+    const int R = a.n_rungs, it = iteration_of(a);
+    const int ens = t / R, r = t - ens * R;
+    const bool event = a.swap_every > 0 && (it + 1) % a.swap_every == 0;
+    const int par = event ? ((it + 1) / a.swap_every - 1) & 1 : 0;
+    const bool lower = event && (r & 1) == par && r + 1 < R;
+    const bool upper = event && r >= 1 && ((r - 1) & 1) == par;
+    if (upper) return;
+    int* slot = a.slot + (size_t)ens * R;
+    uint8_t* hist = a.rung_hist + (size_t)(it + 1) * a.n;
+    const int ca = slot[r];
+    if (!lower) { hist[ca] = (uint8_t)r; return; }
+    const int cb = slot[r + 1];
+    const float* e = a.e_hist + (size_t)(it + 1) * a.n;
+    const float ba = a.beta[ca], bb = a.beta[cb];
+    const float d = (ba - bb) * (e[cb] - e[ca]);
+    const float u = unif_from_bits(philox4x32_10(U4{a.key.chain_lo + (uint32_t)(ens * R), (uint32_t)it, 0x40000000u, (uint32_t)r},
+                                                 a.key.k0, a.key.k1).x);
+    const bool acc = expf(d) >= u;
+    const size_t pair = (size_t)ens * (R - 1) + r;
+    a.swap_attempts[pair] += 1;
+    if (acc) {
+        a.swap_accepts[pair] += 1;
+        a.beta[ca] = bb; a.beta[cb] = ba;
+        a.rung[ca] = r + 1; a.rung[cb] = r;
+        slot[r] = cb; slot[r + 1] = ca;
+    }
+    hist[acc ? cb : ca] = (uint8_t)r;
+    hist[acc ? ca : cb] = (uint8_t)(r + 1);
+}
 
 // records -> plain arrays for the host (final collect / periodic log)
 __global__ void k_rec_gather(PasArgs a, float* best_e, float* best_f, int* best_t, uint8_t* acc) {

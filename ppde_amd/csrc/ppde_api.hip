@@ -1193,7 +1193,25 @@ struct ppde_chains {
     std::vector<void*> allocs;
     uint32_t* allowed = nullptr;                 // design library [L] (ppde_chains_set_library), owned here; NULL = none
     bool reversible = false;                     // ppde_chains_set_reversible: the accept phases run the *_rev kernels
+    // parallel tempering (ppde_chains_set_tempering): owned here, allocated there; n_rungs 0 = none
+    int n_rungs = 0, swap_every = 0;
+    std::vector<float> ladder;                   // beta[0] > beta[1] > ... > 0
+    float* beta = nullptr;                       // [n]
+    int *rung = nullptr, *slot = nullptr;        // [n], [n/R][R]
+    long long *swap_attempts = nullptr, *swap_accepts = nullptr;   // [n/R][R-1]
+    uint8_t* rung_hist = nullptr;                // [T+1][n]
 };
+
+static void free_tempering(ppde_chains* c) {
+    if (c->beta) hipFree(c->beta);
+    if (c->rung) hipFree(c->rung);
+    if (c->slot) hipFree(c->slot);
+    if (c->swap_attempts) hipFree(c->swap_attempts);
+    if (c->swap_accepts) hipFree(c->swap_accepts);
+    if (c->rung_hist) hipFree(c->rung_hist);
+    c->beta = nullptr; c->rung = nullptr; c->slot = nullptr; c->swap_attempts = nullptr; c->swap_accepts = nullptr; c->rung_hist = nullptr;
+    c->n_rungs = 0; c->swap_every = 0; c->ladder.clear();
+}
 
 static PasArgs chain_args(const ppde_chains* c) {
     const ppde_model* m = c->m;
@@ -1218,6 +1236,8 @@ static PasArgs chain_args(const ppde_chains* c) {
     a.err_flag = c->err_flag;
     a.dbg = c->dbg;
     a.allowed = c->allowed;
+    a.beta = c->beta; a.rung = c->rung; a.slot = c->slot; a.swap_attempts = c->swap_attempts; a.swap_accepts = c->swap_accepts;
+    a.rung_hist = c->rung_hist; a.n_rungs = c->n_rungs; a.swap_every = c->swap_every;
     return a;
 }
 
@@ -1272,6 +1292,14 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
                         else hipLaunchKernelGGL(K, dim3(n_sub), dim3(PPDE_BLOCK), lds, s, a); } while (0)
     with_gpt([&](auto G) {
         constexpr int GP = decltype(G)::value;
+        if (c->n_rungs > 0) {                        // tempering (reversible mode): general instantiations, rows and ratio on beta[b] * E
+            if (which == KP_PROPOSE) {
+                if (a.rng_mode == 0) { if (lib) PPDE_CL((k_propose_temp<GP, true, true>)); else PPDE_CL((k_propose_temp<GP, true, false>)); }
+                else { if (lib) PPDE_CL((k_propose_temp<GP, false, true>)); else PPDE_CL((k_propose_temp<GP, false, false>)); }
+            } else if (a.rng_mode == 1) { if (lib) PPDE_CL((k_accept_temp<GP, true, true>)); else PPDE_CL((k_accept_temp<GP, true, false>)); }
+            else { if (lib) PPDE_CL((k_accept_temp<GP, false, true>)); else PPDE_CL((k_accept_temp<GP, false, false>)); }
+            return;
+        }
         if (rev) {                                   // general instantiations only; the forward path keeps its kernels
             if (which == KP_ACCEPT_PROPOSE) { if (lib) PPDE_CL((k_accept_propose_rev<GP, true>)); else PPDE_CL((k_accept_propose_rev<GP, false>)); }
             else if (a.rng_mode == 1) { if (lib) PPDE_CL((k_accept_rev<GP, true, true>)); else PPDE_CL((k_accept_rev<GP, true, false>)); }
@@ -1307,6 +1335,7 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
 
 // `count` iterations of ppde.py:65-153 for sub-population k, enqueued on that sub-population's stream.
 // Re-evaluating mode: EG(x) P EG(y) A per iteration. Reuse mode: P, then EG(y) + fused [accept | next propose].
+// Tempering: [EG(x)] P EG(y) A S, never fused: the next proposal must see the post-swap beta, the swap the post-accept energy.
 static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int first_local, int count, const int* U,
                               const float* q, const float* u, int mu_cap = 0) {
     const ppde_model* m = c->m;
@@ -1315,7 +1344,8 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
     PasArgs a = chain_args(c);
     a.b_off = b_off; a.it_base = it_base; a.U_in = U; a.q_in = q; a.u_in = u;
     if (mu_cap > 0) a.mu_cap = mu_cap;              // caller-supplied noise holds only max_u[i] sub-steps of variates
-    const bool fuse = c->cfg.reuse_grad && c->cfg.rng_mode == 1;
+    const bool temper = c->n_rungs > 0;
+    const bool fuse = c->cfg.reuse_grad && c->cfg.rng_mode == 1 && !temper;
     int rc;
     for (int i = 0; i < count; ++i) {
         a.it_local = first_local + i;
@@ -1332,6 +1362,10 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
         if (rc) return rc;
         rc = launch_chain_kernel(c, (fuse && i + 1 < count) ? KP_ACCEPT_PROPOSE : KP_ACCEPT, a, n_sub, s);
         if (rc) return rc;
+        if (temper) {                                // (one stream: every chain of the object)
+            hipLaunchKernelGGL(k_swap, dim3((c->n + 255) / 256), dim3(256), 0, s, a);
+            HIPCHK(hipGetLastError());
+        }
     }
     return PPDE_OK;
 }
@@ -1496,6 +1530,7 @@ int ppde_chains_destroy(ppde_chains* c) {
     }
     for (void* p : c->allocs) hipFree(p);
     if (c->allowed) hipFree(c->allowed);
+    free_tempering(c);
     delete c->tfw;
     if (c->h_err) hipHostFree(c->h_err);
     for (hipStream_t st : c->streams) if (st) hipStreamDestroy(st);
@@ -1542,7 +1577,74 @@ int ppde_chains_set_reversible(ppde_chains* c, int on) {
     ARGCHK(!c->initialised, "ppde_chains_set_reversible: the mode must be set before ppde_chains_init (its graphs hold the kernel choice)");
     ARGCHK(!(on && c->cfg.paper_results), "ppde_chains_set_reversible: paper_results restarts a rejected chain from its initial state, "
                                           "which is no Metropolis step; the two cannot be combined");
+    ARGCHK(on || c->n_rungs == 0, "ppde_chains_set_reversible: tempering is set and needs reversible mode (clear it with "
+                                  "ppde_chains_set_tempering(c, 0, NULL, 0) first)");
     c->reversible = on != 0;
+    return PPDE_OK;
+}
+
+int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_host, int swap_every) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_tempering: the ladder must be set before ppde_chains_init (its graphs hold the kernel choice)");
+    HIPCHK(hipSetDevice(c->device));
+    if (n_rungs == 0 || !beta_host) {               // clear
+        free_tempering(c);
+        return PPDE_OK;
+    }
+    const int R = n_rungs;
+    ARGCHK(c->reversible, "ppde_chains_set_tempering: tempering needs reversible mode (ppde_chains_set_reversible): only there is the "
+                          "law at beta, exp(beta E)/Z, defined");
+    ARGCHK(R >= 1 && R <= 64, "ppde_chains_set_tempering: n_rungs must be in 1..64");
+    for (int r = 0; r < R; ++r) {
+        const float b = beta_host[r];
+        if (!(b > 0.f) || !(b < INFINITY))
+            return fail(PPDE_ERR_INVALID, "ppde_chains_set_tempering: beta[" + std::to_string(r) + "] must be finite and positive");
+        if (r > 0 && !(b < beta_host[r - 1]))
+            return fail(PPDE_ERR_INVALID, "ppde_chains_set_tempering: the ladder must be strictly decreasing (beta[" + std::to_string(r) +
+                                          "] >= beta[" + std::to_string(r - 1) + "])");
+    }
+    ARGCHK(swap_every >= 0, "ppde_chains_set_tempering: negative swap_every");
+    ARGCHK(c->n % R == 0, "ppde_chains_set_tempering: n_chains must be a multiple of n_rungs (ensembles of n_rungs consecutive chains)");
+    ARGCHK(c->cfg.chain_offset % (uint64_t)R == 0, "ppde_chains_set_tempering: chain_offset must be a multiple of n_rungs (an ensemble "
+                                                   "may not straddle two shards)");
+    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_tempering: n_streams > 1 is not supported (the swap couples "
+                                                            "the chains of an ensemble)");
+    // allocate everything first: a failure leaves the object as it was
+    const size_t n = c->n, pairs = (n / R) * (size_t)(R - 1);
+    ppde_chains t;                                   // (a holder for free_tempering on the error path)
+    hipError_t e = dalloc(&t.beta, n);
+    if (e == hipSuccess) e = dalloc(&t.rung, n);
+    if (e == hipSuccess) e = dalloc(&t.slot, n);
+    if (e == hipSuccess) e = dalloc(&t.swap_attempts, pairs);
+    if (e == hipSuccess) e = dalloc(&t.swap_accepts, pairs);
+    if (e == hipSuccess) e = dalloc(&t.rung_hist, ((size_t)c->T + 1) * n);
+    if (e != hipSuccess) {
+        free_tempering(&t);
+        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_tempering: device allocation: ") + hipGetErrorString(e));
+    }
+    free_tempering(c);
+    c->beta = t.beta; c->rung = t.rung; c->slot = t.slot; c->swap_attempts = t.swap_attempts; c->swap_accepts = t.swap_accepts;
+    c->rung_hist = t.rung_hist;
+    t.beta = nullptr; t.rung = nullptr; t.slot = nullptr; t.swap_attempts = nullptr; t.swap_accepts = nullptr; t.rung_hist = nullptr;
+    c->n_rungs = R; c->swap_every = swap_every;
+    c->ladder.assign(beta_host, beta_host + R);
+    return PPDE_OK;
+}
+
+// rungs, temperatures, slots and counters of a fresh start: chain g = chain_offset + b starts on rung g % R (chain_offset % R == 0)
+static int init_tempering(ppde_chains* c) {
+    const int R = c->n_rungs;
+    const size_t n = c->n, pairs = (n / R) * (size_t)(R - 1);
+    std::vector<float> hb(n);
+    std::vector<int> hr(n), hs(n);
+    std::vector<uint8_t> h8(n);
+    for (size_t b = 0; b < n; ++b) { hr[b] = (int)(b % R); hb[b] = c->ladder[hr[b]]; hs[b] = (int)b; h8[b] = (uint8_t)hr[b]; }
+    HIPCHK(hipMemcpy(c->beta, hb.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->rung, hr.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->slot, hs.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->rung_hist, h8.data(), n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(c->swap_attempts, 0, std::max<size_t>(pairs, 1) * sizeof(long long)));
+    HIPCHK(hipMemset(c->swap_accepts, 0, std::max<size_t>(pairs, 1) * sizeof(long long)));
     return PPDE_OK;
 }
 
@@ -1599,6 +1701,10 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(s));
+    if (c->n_rungs > 0) {
+        rc = init_tempering(c);
+        if (rc) return rc;
+    }
     c->steps_done = 0;
     c->initialised = true;
     rc = capture_segments(c);                       // (replayed by every later run; never captured inside one)
@@ -1729,6 +1835,28 @@ int ppde_chains_collect(ppde_chains* c, uint8_t* best_idx, float* best_energy, f
         ARGCHK(c->cfg.random_chain >= 0, "no random trajectory was recorded (random_chain = -1)");
         HIPCHK(hipMemcpy(random_traj, c->rtraj, rows * g.L, hipMemcpyDeviceToHost));
     }
+    return PPDE_OK;
+}
+
+int ppde_chains_tempering_state(ppde_chains* c, int32_t* rung, float* beta, int64_t* swap_attempts, int64_t* swap_accepts) {
+    ARGCHK(c && c->initialised, "chains not initialised");
+    ARGCHK(c->n_rungs > 0, "ppde_chains_tempering_state: no tempering was set (ppde_chains_set_tempering)");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    const size_t n = c->n, pairs = (n / c->n_rungs) * (size_t)(c->n_rungs - 1);
+    if (rung) HIPCHK(hipMemcpy(rung, c->rung, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (beta) HIPCHK(hipMemcpy(beta, c->beta, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (swap_attempts && pairs) HIPCHK(hipMemcpy(swap_attempts, c->swap_attempts, pairs * sizeof(long long), hipMemcpyDeviceToHost));
+    if (swap_accepts && pairs) HIPCHK(hipMemcpy(swap_accepts, c->swap_accepts, pairs * sizeof(long long), hipMemcpyDeviceToHost));
+    return PPDE_OK;
+}
+
+int ppde_chains_tempering_history(ppde_chains* c, uint8_t* rung_history) {
+    ARGCHK(c && c->initialised && rung_history, "chains not initialised, or null argument");
+    ARGCHK(c->n_rungs > 0, "ppde_chains_tempering_history: no tempering was set (ppde_chains_set_tempering)");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(rung_history, c->rung_hist, ((size_t)c->steps_done + 1) * c->n, hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 

@@ -30,6 +30,13 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         exp(energy) / Z over the library, with nmut_threshold as a constraint (dist < threshold) instead of a
                         reset. Such a run always has a library (all letters over [min_pos, max_pos] when none is given), so the
                         restriction is hard; paper_results and an initial population outside the library are refused.
+    ppde_betas          None (default), or a ladder of inverse temperatures beta[0] > beta[1] > ... > 0: parallel tempering of a
+                        reversible run (include/ppde_hip.h, ppde_chains_set_tempering). Consecutive chains form ensembles of
+                        len(ppde_betas); the chain on rung r samples exp(beta_r energy)/Z and neighbouring rungs propose to
+                        exchange temperatures every ppde_swap_every iterations (default 1; 0: never). Needs ppde_reversible; the
+                        population (and every shard boundary) must be a multiple of the ladder; not with ppde_streams > 1.
+                        Histories and best states stay on the untempered energy. After run(), `sampler.tempering` holds
+                        betas, rung_history [T+1, n], swap_attempts and swap_accepts [n / R, R - 1].
     ppde_shard          False (default). True with torch.distributed initialised: chains are split over ranks
                         and gathered at the end (one RCCL all_gather); every rank returns the full result.
 """
@@ -45,6 +52,20 @@ from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
 from .parallel import active as collectives_active, agree_from_rank0, all_gather_rows, broadcast_from, shard_range, world
+
+
+def check_ladder(betas):
+    """A tempering ladder as fp32 [R], or ValueError: 1..64 finite, positive, strictly decreasing inverse temperatures."""
+    b = np.asarray(betas, dtype=np.float32).reshape(-1)
+    if not 1 <= b.size <= 64:
+        raise ValueError(f"ppde_betas: a ladder has 1 to 64 rungs, got {b.size}")
+    if not np.isfinite(b).all():
+        raise ValueError("ppde_betas: every beta must be finite")
+    if not (b > 0).all():
+        raise ValueError("ppde_betas: every beta must be positive")
+    if not (b[1:] < b[:-1]).all():
+        raise ValueError("ppde_betas: the ladder must be strictly decreasing")
+    return np.ascontiguousarray(b)
 
 
 class Chains:
@@ -89,6 +110,32 @@ class Chains:
         path under the forward row function, so the chains sample exp(energy)/Z over the library. Only before init()."""
         _hip.check(self.lib.ppde_chains_set_reversible(self.handle, int(bool(on))))
         self.reversible = bool(on)
+
+    def set_tempering(self, betas, swap_every=1):
+        """Parallel tempering (include/ppde_hip.h, ppde_chains_set_tempering): a ladder betas[0] > betas[1] > ... > 0 over
+        ensembles of len(betas) consecutive chains, replica exchange every `swap_every` iterations (0: never). None or an
+        empty ladder clears it. Needs reversible mode; only before init()."""
+        ladder = None if betas is None or len(betas) == 0 else np.ascontiguousarray(np.asarray(betas, dtype=np.float32).reshape(-1))
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_set_tempering(self.handle, 0 if ladder is None else int(ladder.size), _hip.ptr(ladder),
+                                                          int(swap_every)))
+        self.betas, self.swap_every = ladder, int(swap_every)
+
+    def tempering_state(self):
+        """rung int32 [n] and beta fp32 [n] each chain holds now, swap_attempts / swap_accepts int64 [n / R, R - 1]."""
+        R = 0 if getattr(self, "betas", None) is None else int(self.betas.size)
+        pairs = (self.n // R, R - 1) if R else (0, 0)
+        out = dict(rung=np.empty(self.n, np.int32), beta=np.empty(self.n, np.float32),
+                   swap_attempts=np.zeros(pairs, np.int64), swap_accepts=np.zeros(pairs, np.int64))
+        _hip.check(self.lib.ppde_chains_tempering_state(self.handle, *[_hip.ptr(out[k]) for k in (
+            "rung", "beta", "swap_attempts", "swap_accepts")]))
+        return out
+
+    def tempering_history(self):
+        """uint8 [steps_done + 1, n]: the rung each chain held after every iteration (row 0: the start)."""
+        out = np.empty((self.steps_done + 1, self.n), np.uint8)
+        _hip.check(self.lib.ppde_chains_tempering_history(self.handle, _hip.ptr(out)))
+        return out
 
     def init(self, idx0):
         idx0 = idx0.to(self.model.device, torch.uint8).contiguous()
@@ -207,6 +254,17 @@ class PPDE_PAS(BaseSampler):
         if self.reversible and self.paper_results:
             raise ValueError("ppde_reversible: paper_results restarts a rejected chain from its initial state, which is no "
                              "Metropolis step; the two cannot be combined")
+        betas = getattr(args, "ppde_betas", None)
+        self.betas = None if betas is None or len(betas) == 0 else check_ladder(betas)
+        self.swap_every = int(getattr(args, "ppde_swap_every", 1))
+        self.tempering = None
+        if self.betas is not None:
+            if not self.reversible:
+                raise ValueError("ppde_betas: tempering needs ppde_reversible (only there is the law at beta, exp(beta energy)/Z, defined)")
+            if self.swap_every < 0:
+                raise ValueError("ppde_swap_every must be >= 0")
+            if int(self.n_streams) > 1:
+                raise ValueError("ppde_betas: ppde_streams > 1 is not supported (the swap couples the chains of an ensemble)")
         self.noise_bytes = getattr(args, "ppde_noise_bytes", 96 << 20)   # host->device noise is uploaded in chunks of about this size
         self.last_chains = None
         self.timings = {}       # seconds of the last run(): setup (chains + hipGraph capture), iterations, log path, collect
@@ -229,8 +287,16 @@ class PPDE_PAS(BaseSampler):
             lib = design_library.full_library(L) if self.library is None else design_library.as_words(self.library, L)
             lib_words = design_library.fold_range(lib, min_pos, max_pos)
             design_library.check_population(lib_words, initial_population.detach().argmax(-1).cpu().numpy())
+        R = 0 if self.betas is None else int(self.betas.size)
+        if R and n_global % R:
+            raise ValueError(f"ppde_betas: the population of {n_global} chains is no multiple of the {R} rungs of the ladder")
         random_idx = np.random.randint(0, n_global)                       # ppde.py:37 (same numpy RNG consumption)
         rank, ws = world() if self.shard else (0, 1)
+        if R:
+            for r in range(ws):
+                if shard_range(n_global, r, ws)[0] % R:
+                    raise ValueError(f"ppde_betas: the shard boundary at chain {shard_range(n_global, r, ws)[0]} (rank {r} of {ws}) "
+                                     f"cuts an ensemble of {R} chains")
         comm = self.shard and collectives_active()        # (ws > 1, or the one-rank rehearsal of the RCCL path)
         lo, hi = shard_range(n_global, rank, ws)
         n = hi - lo
@@ -261,10 +327,16 @@ class PPDE_PAS(BaseSampler):
             chains.set_library(lib_words)
         if self.reversible:
             chains.set_reversible(True)
+        if R:
+            chains.set_tempering(self.betas, self.swap_every)
         chains.init(idx0[lo:hi])
 
         def gathered(a):
             return all_gather_rows(torch.as_tensor(a), n_global).numpy() if comm else np.asarray(a)
+
+        def gathered_ensembles(a):
+            # (every shard boundary is a multiple of R, so the shards are equal and the n / R ensembles split the same way)
+            return all_gather_rows(torch.as_tensor(a), n_global // R).numpy() if comm and R > 1 else np.asarray(a)
 
         def log(i, first=False):
             pk = chains.peek()
@@ -283,6 +355,9 @@ class PPDE_PAS(BaseSampler):
                 print(f'[Iteration {i}] oracle 50% {gq[0]:.3f}, 90% {gq[1]:.3f}', flush=True)
                 print(f'   # accepted = {float(gathered(pk["accepted"]).sum())}')
                 print(f'   # dist = {float(gathered(pk["dist"]).astype(np.float32).mean())}')
+                if R:
+                    ts = chains.tempering_state()
+                    print(f'   # swaps accepted = {int(gathered_ensembles(ts["swap_accepts"]).sum())} / {int(gathered_ensembles(ts["swap_attempts"]).sum())}')
                 print('', flush=True)
 
         chains.sync()
@@ -330,6 +405,13 @@ class PPDE_PAS(BaseSampler):
             rtraj = res["random_traj"]
         random_traj = list(idx_to_onehot(rtraj, dtype=np.float32))     # T + 1 arrays [L, 20] (views of one expansion)
         best_e, best_f = gathered(res["best_energy"]), gathered(res["best_fitness"])
+        if R:
+            ts = chains.tempering_state()
+            rh = chains.tempering_history()
+            self.tempering = dict(
+                betas=self.betas.copy(),
+                rung_history=all_gather_rows(torch.from_numpy(rh), n_global, dim=1).numpy() if comm else rh,
+                swap_attempts=gathered_ensembles(ts["swap_attempts"]), swap_accepts=gathered_ensembles(ts["swap_accepts"]))
         if n_global == 1:
             # the reference's single-chain shapes (ppde.py:178-183; the ensemble's `.squeeze()`, nets.py:442, makes one chain's
             # fitness a scalar): fitness_history (T+1,) next to energy_history (T+1, 1); with ProteinSupervised the energy IS

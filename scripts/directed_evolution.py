@@ -11,7 +11,8 @@ the MSA-Transformer scoring are out of scope.
 
 Extra flags: --ppde_rng {torch,philox}, --ppde_seed, --ppde_reuse_grad {0,1}, --ppde_shard (with torchrun), --ppde_full_grad,
 --ppde_timing; design library (the letters the sampler may propose per residue): --ppde_sites, --ppde_exclude, --ppde_library;
---ppde_reversible (chains that sample exp(energy)/Z over the library).
+--ppde_reversible (chains that sample exp(energy)/Z over the library); --ppde_betas, --ppde_swap_every (parallel tempering of such
+a run: a ladder of inverse temperatures with replica exchange).
 """
 import argparse
 import datetime
@@ -200,6 +201,13 @@ def build_parser():
                          "the reverse move at the forward index): the chains sample exp(energy)/Z over the design library (all "
                          "letters of the window when none is given), --nmut_threshold becomes a constraint instead of a reset. "
                          "Not with --paper_results")
+    pp.add_argument("--ppde_betas", type=lambda t: [float(v) for v in t.split(",") if v.strip()], default=None,
+                    help="parallel tempering (needs --ppde_reversible): a strictly decreasing ladder of inverse temperatures, e.g. "
+                         "'1,0.7,0.5,0.35'. Consecutive chains form ensembles of one chain per rung, the chain on rung r samples "
+                         "exp(beta_r energy)/Z; --n_chains must be a multiple of the number of rungs")
+    pp.add_argument("--ppde_swap_every", type=int, default=1,
+                    help="with --ppde_betas: neighbouring rungs of an ensemble propose to exchange their temperatures every this "
+                         "many iterations (0: never)")
     return parser
 
 
