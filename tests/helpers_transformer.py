@@ -27,7 +27,11 @@ Rounding points of the half evaluation beyond EsmOracle's, each one the device's
   * the energy is the score minus the wild type's, subtracted in fp32 (stage E's `wt_score`).
 
 `mut` (a `Mut`) plants ONE fault of the kind a kernel could have into an evaluation; tests/test_transformer_stages_cpu.py
-shows that each lands far outside the bound the GPU tests apply."""
+shows that each lands far outside the bound the GPU tests apply.
+
+The last section restates the persistent GEMMs' tile walk (which output tile a workgroup computes as its first, second, ...)
+from the kernels' integer formulas, the GEMM shapes of one evaluation and the row padding: what
+tests/test_transformer_population_gpu.py chooses its chains from."""
 import collections
 import math
 
@@ -40,7 +44,7 @@ F64, F32 = torch.float64, torch.float32
 TAIL = 128            # rows from here on exist only in the 256-residue attention kernels
 MARGIN = 4.0          # bound = MARGIN x yardstick (2: the larger of two draws of the same rounding process; 2: margin)
 
-Mut = collections.namedtuple("Mut", "name head chain", defaults=(None, None))
+Mut = collections.namedtuple("Mut", "name head chain walk", defaults=(None, None, None))      # walk: a Walk, for faults of the tile walk
 
 
 def _h(t, half):
@@ -211,9 +215,27 @@ def attention(P, qkv, dtype=F64, half=False, mut=None):
     return _h(ctx, half).transpose(1, 2).reshape(n, L, D)
 
 
+def _lin_prev_tile_first_k(P, x, pre, dtype, half, w):
+    """_lin as a persistent GEMM would compute it whose first k tile (64 of K) of every later tile of its walk (ordinal >= 1
+    in the Walk `w`) still held the A rows of the workgroup's PREVIOUS output tile: rows beyond the chains (pad rows) are zero."""
+    n, L, K = x.shape
+    W = P.mat(pre + ".weight", dtype)
+    a = torch.zeros(w.M_pad, K, dtype=dtype)
+    a[: n * L] = _h(x, half).reshape(n * L, K)
+    y = a @ W.t()
+    for v in np.flatnonzero(w.ordinal >= 1):
+        m0, n0 = (int(v) // w.tiles_n) * w.tile_m, (int(v) % w.tiles_n) * w.tile_n
+        p0 = (int(w.prev[v]) // w.tiles_n) * w.tile_m
+        stale = a[p0:p0 + w.tile_m, :64] - a[m0:m0 + w.tile_m, :64]
+        y[m0:m0 + w.tile_m, n0:n0 + w.tile_n] += stale @ W[n0:n0 + w.tile_n, :64].t()
+    return _h(y[: n * L].reshape(n, L, -1) + P.vec(pre + ".bias", dtype), half)
+
+
 def stage_b(P, i, xin, qkv, dtype=F64, half=False, mut=None):
     """-> (ctx_i, xmid_i)."""
     ctx = attention(P, qkv, dtype, half, mut)
+    if mut is not None and mut.name == "prev_tile_first_k":
+        return ctx, _h(xin.to(dtype) + _lin_prev_tile_first_k(P, ctx, f"layers.{i}.self_attn.out_proj", dtype, half, mut.walk), half)
     return ctx, _h(xin.to(dtype) + _lin(P, ctx, f"layers.{i}.self_attn.out_proj", dtype, half), half)
 
 
@@ -344,3 +366,104 @@ def chains_like_the_parity_test(L, n, seed=3):
         pos = rng.choice(L, size=min(L, 3 * b), replace=False)
         idx[b, pos] = rng.integers(0, 20, len(pos))
     return wt, idx
+
+
+# ---- the persistent GEMMs' tile walk, restated on the CPU (tf.h: tf_gemm_nt, tf_gemm160, tf_gemm_big; tf_host.h: tf_gemm) -------
+# Per output tile v (N-fastest order): its ordinal in its workgroup's walk (ti // wpx), the XCD whose run it lies in, the
+# workgroup, the tile that workgroup computed before it (-1: none) and how many workgroups visit it.
+Walk = collections.namedtuple("Walk", "ordinal xcd block prev visits grid M_pad tiles_n tile_m tile_n")
+
+#              L   dim heads ffn  chains: the smallest shapes at which every GEMM with N >= 256 gives a workgroup a second tile
+POPULATIONS = {"P160": (104, 640, 20, 1280, 256),      # tf_gemm160 (every width a multiple of 160)
+               "P128": (237, 256, 8, 512, 198)}        # tf_gemm_nt (128-row tiles); 198 chains, not 192: with 192 the 14 tiles at
+#                                                        ordinal 4 of N = 768 (2.3 row tiles) hold no chain of 237 rows entirely
+
+
+def pad_rows(M, use160=True, big=False):
+    """tf_pad_rows: the token rows padded to whole row tiles of every GEMM kernel in use."""
+    g = (1280 if big else 640) if use160 else (256 if big else 128)
+    return (M + g - 1) // g * g
+
+
+def walk(M_pad, N, tile, cap=512):
+    """The kernels' integer formulas, workgroup by workgroup. tile: the edge of a square tile, or (rows, columns)."""
+    tile_m, tile_n = (tile, tile) if isinstance(tile, int) else tile
+    assert M_pad % tile_m == 0 and N % tile_n == 0
+    tiles_n = N // tile_n
+    tiles_total = (M_pad // tile_m) * tiles_n
+    tiles8 = (tiles_total + 7) & ~7
+    grid = min(tiles8, cap)                                          # (tf_host.h: the launch)
+    ordinal, xcd_of, block_of, prev = (np.full(tiles_total, -1, np.int64) for _ in range(4))
+    visits = np.zeros(tiles_total, np.int64)
+    wpx = grid >> 3
+    xq, xr = tiles_total >> 3, tiles_total & 7
+    for block in range(grid):
+        xcd, slot = block & 7, block >> 3
+        xbeg, xcnt = xcd * xq + min(xcd, xr), xq + (1 if xcd < xr else 0)
+        for ti in range(slot, xcnt, wpx):
+            v = xbeg + ti
+            visits[v] += 1
+            ordinal[v], xcd_of[v], block_of[v] = ti // wpx, xcd, block
+            prev[v] = v - wpx if ti - wpx >= slot else -1
+    return Walk(ordinal, xcd_of, block_of, prev, visits, grid, M_pad, tiles_n, tile_m, tile_n)
+
+
+def tile_walk(M_pad, N, tile, cap=512):
+    """For every output tile v (row tile m0 = v // tiles_n): its ordinal in its workgroup's walk."""
+    return walk(M_pad, N, tile, cap).ordinal
+
+
+def gemm_shapes(dim, ffn, M_pad, use160=True):
+    """Every GEMM an evaluation with the gradient launches (tf_eval_chunk), forward then backward, as
+    (name, N, K, tile, kernel): tf_gemm160 where M and N are multiples of 160 (and PPDE_TF_160 is not 0), else tf_gemm_nt."""
+    D, V = (dim + 127) // 128 * 128, 128
+    launches = [("qkv", 3 * D, D), ("out_proj", D, D), ("fc1", ffn, D), ("fc2", D, ffn), ("head_dense", D, D), ("logits", V, D),
+                ("logits.bwd", D, V), ("head_dense.bwd", D, D), ("fc2.bwd", ffn, D), ("fc1.bwd", D, ffn), ("out_proj.bwd", D, D),
+                ("qkv.bwd", D, 3 * D), ("embedding.bwd", V, D)]
+    out = []
+    for name, N, K in launches:
+        t160 = use160 and M_pad % 160 == 0 and N % 160 == 0
+        out.append((name, N, K, 160 if t160 else 128, "tf_gemm160" if t160 else "tf_gemm_nt"))
+    return out
+
+
+def _chain_row_tiles(w, L, c):
+    return range(c * L // w.tile_m, ((c + 1) * L - 1) // w.tile_m + 1)
+
+
+def select_chains(L, n, dim, ffn):
+    """The chains whose stages the population tests bound against fp64, chosen from the walk of the geometry's GEMM shapes:
+    chain 0, the last chain, for every shape (N, tile) and every ordinal >= 1 it reaches one chain whose rows lie wholly in
+    tiles of that ordinal, one chain holding the first row of a workgroup's second tile and one whose rows straddle two
+    XCDs' runs (both in the N = dim GEMM). -> (sorted chains, {chain: [reasons]}, [(N, tile, ordinal) without a chain])."""
+    M_pad = pad_rows(n * L)
+    D = (dim + 127) // 128 * 128
+    shapes = sorted({(N, tile) for _, N, _, tile, _ in gemm_shapes(dim, ffn, M_pad)}, key=lambda s: (s[0] != D, s[0]))
+    why, missing = {0: ["the wild type"]}, []
+    why.setdefault(n - 1, []).append("the last chain, beside the pad rows")
+    grids = {}
+    for N, tile in shapes:
+        w = walk(M_pad, N, tile)
+        o = w.ordinal.reshape(-1, w.tiles_n)
+        lo = np.array([min(o[r].min() for r in _chain_row_tiles(w, L, c)) for c in range(n)])
+        hi = np.array([max(o[r].max() for r in _chain_row_tiles(w, L, c)) for c in range(n)])
+        grids[(N, tile)] = (w, lo, hi)
+        for k in range(1, int(w.ordinal.max()) + 1):
+            fit = [c for c in range(n) if lo[c] == hi[c] == k]
+            if not fit:
+                missing.append((N, tile, k))
+                continue
+            c = next((c for c in fit if c not in why), fit[0])          # a chain of its own where there is one
+            why.setdefault(c, []).append(f"wholly in ordinal {k} of N = {N}, {tile}-tiles")
+    w, lo, hi = grids[shapes[0]]                                     # the N = dim GEMM
+    x = w.xcd.reshape(-1, w.tiles_n)
+    first2 = np.flatnonzero(w.ordinal == 1)
+    if len(first2):
+        c = (int(first2[0]) // w.tiles_n) * w.tile_m // L            # the chain that holds that tile's first row
+        if c < n:
+            why.setdefault(c, []).append(f"holds the first row of a workgroup's second tile (N = {shapes[0][0]})")
+    for c in range(n):
+        if len({int(t) for r in _chain_row_tiles(w, L, c) for t in x[r]}) > 1:
+            why.setdefault(c, []).append(f"straddles two XCDs' runs (N = {shapes[0][0]})")
+            break
+    return sorted(why), why, missing

@@ -147,3 +147,106 @@ def test_backward_mutants_land_outside_the_whole_model_bounds(label, L, mut, see
     print(f"[mutant] {label} (L = {L}, one layer): gradient {mult[0]:.1f}, d q|k|v {mult[1]:.1f} x yardstick")
     for j in seen_by:
         assert mult[j] >= 2 * ht.MARGIN
+
+
+# ---- the tile walk of the persistent GEMMs, and the population geometries that reach it ---------------------------------
+POP = [(g, layers) for g in ht.POPULATIONS for layers in (2, 1)]
+#             geometry  N    tile: tiles, tiles at ordinal >= 1, highest ordinal
+WALK_TABLE = {("P160", 640, 160): (672, 160, 1), ("P160", 1920, 160): (2016, 1504, 3), ("P160", 1280, 160): (1344, 832, 2),
+              ("P160", 128, 128): (210, 0, 0),
+              ("P128", 256, 128): (740, 228, 1), ("P128", 768, 128): (2220, 1708, 4), ("P128", 512, 128): (1480, 968, 2),
+              ("P128", 128, 128): (370, 0, 0)}
+
+
+@pytest.mark.parametrize("geom,layers", POP, ids=[f"{g}l{l}" for g, l in POP])
+def test_population_geometries_reach_later_tiles_of_every_gemm(geom, layers):
+    L, dim, heads, ffn, n = ht.POPULATIONS[geom]
+    M_pad = ht.pad_rows(n * L)
+    assert M_pad % 640 == 0 and 0 <= M_pad - n * L < 640
+    shapes = ht.gemm_shapes(dim, ffn, M_pad)
+    assert {s[0] for s in shapes} >= {"qkv", "qkv.bwd", "out_proj", "fc1", "fc1.bwd", "fc2", "fc2.bwd", "head_dense", "logits", "embedding.bwd"}
+    assert {s[4] for s in shapes if s[1] != 128} == {"tf_gemm160" if geom == "P160" else "tf_gemm_nt"}
+    assert {s[3:] for s in shapes if s[1] == 128} == {(128, "tf_gemm_nt")}
+    seen = set()
+    for name, N, K, tile, kernel in shapes:
+        w = ht.walk(M_pad, N, tile)
+        tiles = (M_pad // tile) * (N // tile)
+        assert w.grid == min((tiles + 7) & ~7, 512) and len(w.ordinal) == tiles
+        assert (w.visits == 1).all(), name                           # every tile exactly once
+        assert np.array_equal(w.ordinal, ht.tile_walk(M_pad, N, tile))
+        later = w.ordinal >= 1
+        assert np.array_equal(w.prev[later] >= 0, np.ones(later.sum(), bool)) and (w.prev[~later] == -1).all()
+        assert (w.block[w.prev[later]] == w.block[later]).all() and (w.ordinal[w.prev[later]] == w.ordinal[later] - 1).all()
+        assert (tiles, int(later.sum()), int(w.ordinal.max())) == WALK_TABLE[(geom, N, tile)], (name, N)
+        if N >= 256:
+            assert w.ordinal.max() >= 1, name
+        else:
+            assert w.ordinal.max() == 0                              # (the vocabulary GEMMs stay at one tile per workgroup)
+        seen.add(N)
+    assert int(ht.tile_walk(M_pad, 3 * dim, 160 if geom == "P160" else 128).max()) >= 3
+    chains, why, missing = ht.select_chains(L, n, dim, ffn)
+    assert not missing, missing
+    assert chains[0] == 0 and chains[-1] == n - 1 and 10 <= len(chains) <= 16
+    reasons = " / ".join(r for c in chains for r in why[c])
+    for name, N, K, tile, kernel in shapes:
+        for k in range(1, int(ht.tile_walk(M_pad, N, tile).max()) + 1):
+            assert f"wholly in ordinal {k} of N = {N}, {tile}-tiles" in reasons
+    assert "second tile" in reasons and "straddles" in reasons
+    print(f"[walk] {geom}: " + "; ".join(f"chain {c}: {', '.join(why[c])}" for c in chains))
+
+
+def test_walk_of_the_opt_in_256_row_tiles_and_of_one_workgroup_per_tile():
+    """The forms the population test runs in child processes: tf_gemm_big (256 x 128 tiles at P160's widths, at most 256
+    workgroups, rows padded to 256) walks too; a grid of one workgroup per tile does not."""
+    L, dim, heads, ffn, n = ht.POPULATIONS["P160"]
+    M_pad = ht.pad_rows(n * L, use160=False, big=True)
+    assert M_pad == n * L == 104 * 256
+    for N in (dim, 3 * dim, ffn):
+        w = ht.walk(M_pad, N, (256, 128 if N % 256 else 256), cap=256)
+        assert (w.visits == 1).all() and w.grid == 256 and w.ordinal.max() >= 1
+    M_pad = ht.pad_rows(n * L, use160=False)
+    for N in (dim, 3 * dim, ffn):
+        w = ht.walk(M_pad, N, 128, cap=1 << 30)
+        assert (w.visits == 1).all() and w.ordinal.max() == 0
+
+
+def test_a_stale_first_k_tile_in_later_tiles_lands_outside_stage_b_bound():
+    """Planted fault of the walk: in the later tiles of the N = dim GEMM the first k tile (64 of K) of the output projection
+    is multiplied from the rows of the workgroup's previous output tile (its LDS image not yet replaced). At P160's widths,
+    three chains (312 rows in 640: 4 x 4 tiles of 160) and a synthetic walk -- four workgroups, each walking one column of
+    tiles downwards, so the tiles' ordinal is their row tile -- stage B must see it at >= 2 x its bound. The fixed tolerances
+    of test_score_and_gradient_vs_oracle (restated here against the unmutated half-points evaluation, that test's reference)
+    are printed next to it."""
+    L, dim, heads, ffn, _ = ht.POPULATIONS["P160"]
+    n, layers = 3, 2
+    M_pad = ht.pad_rows(n * L)
+    tiles_n = dim // 160
+    v = np.arange((M_pad // 160) * tiles_n)
+    w = ht.Walk(v // tiles_n, v * 0, v % tiles_n, np.where(v >= tiles_n, v - tiles_n, -1), v * 0 + 1, tiles_n, M_pad, tiles_n, 160, 160)
+    mut = Mut("prev_tile_first_k", walk=w)
+    P, idx, ref, hm = _setup(L, layers, dim, heads, ffn, n)
+    rows_hit = np.zeros((n, L), bool).reshape(-1)
+    rows_hit[160:] = True                                            # rows of ordinal >= 1: part of chain 1, all of chain 2
+    rows_hit = torch.as_tensor(rows_hit.reshape(n, L))
+    mult = []
+    for i in range(layers):
+        xin, qkv = hm[f"xin{i}"], hm[f"qkv{i}"]
+        r = ht.stage_b(P, i, xin, qkv, F64)[1]
+        yard = ht.row_rel(ht.stage_b(P, i, xin, qkv, F32, True)[1], r)
+        got = ht.stage_b(P, i, xin, qkv, F32, True, mut)[1]
+        assert torch.equal(got[~rows_hit], hm[f"xmid{i}"][~rows_hit])            # rows of first tiles are untouched
+        mult.append(ht.row_rel(got, r) / yard)
+    print("[mutant] first k tile of the output projection from the previous tile's rows (P160 widths): "
+          + ", ".join(f"layer {i}: {m:.1f} x yardstick" for i, m in enumerate(mult)))
+    assert mult[0] >= 2 * ht.MARGIN and mult[1] > ht.MARGIN
+    # the whole-model parity test's tolerances on the same fault
+    mm = ht.model(P, idx, F32, half=True, mut=mut)
+    big = lambda t: float(t.abs().max())
+    fixed = {"xmid0": big(mm["xmid0"] - hm["xmid0"]) / (2e-2 * (1 + big(hm["xmid0"]))),
+             "xlast": big(mm["xlast"] - hm["xlast"]) / (2e-2 * (1 + big(hm["xlast"]))),
+             "logits": big(mm["logits"] - hm["logits"]) / (3e-2 * (1 + big(hm["logits"]))),
+             "score": float(((mm["score"] - hm["score"]).abs() / (2e-3 * (1 + hm["score"].abs()))).max()),
+             "grad": big(mm["grad"] - hm["grad"]) / (3e-2 * big(hm["grad"]))}
+    print("[mutant] ... against the fixed tolerances of test_score_and_gradient_vs_oracle: "
+          + ", ".join(f"{k} {r:.2f}" for k, r in fixed.items()))
+    assert min(fixed.values()) > 1.0                                # (stated, not required: the fixed tolerances see this one too)

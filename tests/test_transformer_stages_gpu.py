@@ -42,21 +42,29 @@ GEOMS = [(17, 128, 4, 256, 3),        # two key tiles, one row in the tail tile
 ALT_FORMS = [(129, 128, 4, 256, 3), (237, 96, 4, 256, 2)]     # run again under PPDE_TF_LN16=0 and under PPDE_TF_ATT_KO=0
 
 
-def device_buffers(L, layers, dim, heads, ffn, n):
-    """One evaluation with the gradient on the device; every buffer the checks read, pad columns included."""
-    from test_transformer_gpu import _model, _read
-    m, wt, _, _ = _model(L, layers, dim, heads, ffn)
-    wt2, idx = ht.chains_like_the_parity_test(L, n)
-    assert np.array_equal(wt, wt2)
-    e, _, g = m.energy_grad(torch.as_tensor(idx).cuda(), 4)
+def read_buffers(m, L, layers, dim, ffn, n):
+    """Every activation buffer the checks read, after an evaluation of n chains with the gradient; pad columns included."""
+    from test_transformer_gpu import _read
     dp = (dim + 127) // 128 * 128
-    b = dict(idx=idx, e=e.cpu().numpy(), grad=g.cpu().numpy(), wt_score=np.float64(m.transformer_wt_score))
+    b = {}
     for i in range(layers):
         b[f"xin{i}"], b[f"qkv{i}"] = _read(m, 0, i, (n, L, dp)), _read(m, 1, i, (n, L, 3, dp))
         b[f"xmid{i}"], b[f"gp{i}"] = _read(m, 3, i, (n, L, dp)), _read(m, 4, i, (n, L, ffn))
     for name, what, shape in (("xlast", 5, (n, L, dp)), ("logits", 6, (n, L, 128)), ("dlogits", 7, (n, L, 128)), ("demb", 8, (n, L, dp)),
                               ("dtok", 9, (n, L, 128)), ("ctx", 10, (n, L, dp)), ("dqkv0", 11, (n, L, 3, dp))):
         b[name] = _read(m, what, 0, shape)
+    return b
+
+
+def device_buffers(L, layers, dim, heads, ffn, n):
+    """One evaluation with the gradient on the device; every buffer the checks read, pad columns included."""
+    from test_transformer_gpu import _model
+    m, wt, _, _ = _model(L, layers, dim, heads, ffn)
+    wt2, idx = ht.chains_like_the_parity_test(L, n)
+    assert np.array_equal(wt, wt2)
+    e, _, g = m.energy_grad(torch.as_tensor(idx).cuda(), 4)
+    b = dict(idx=idx, e=e.cpu().numpy(), grad=g.cpu().numpy(), wt_score=np.float64(m.transformer_wt_score))
+    b.update(read_buffers(m, L, layers, dim, ffn, n))
     m.close()
     return b
 
@@ -76,9 +84,13 @@ def _strip_pads(b, dim, layers):
     return {k: (torch.as_tensor(v) if k not in ("idx", "wt_score") else v) for k, v in out.items()}
 
 
-def check_stages(tag, L, layers, dim, heads, ffn, raw, stages=True):
-    """Apply every check to one device evaluation; the assertion comes last so that a failure reports all of its ratios."""
+def check_stages(tag, L, layers, dim, heads, ffn, raw, stages=True, chains=None, family="tfstage"):
+    """Apply every check to one device evaluation; the assertion comes last so that a failure reports all of its ratios.
+    `chains`: check these chains of the evaluation only (every buffer, idx, e and grad sliced on the chain axis; the first
+    one must be the wild type); within them no row, head or stage is exempt."""
     P = ht.Params(synthetic.make_esm2_state(layers, dim, heads, ffn, seed=3), layers, dim, heads)
+    if chains is not None:
+        raw = {k: (v if k == "wt_score" else np.ascontiguousarray(np.asarray(v)[list(chains)])) for k, v in raw.items()}
     b = _strip_pads(raw, dim, layers)
     idx, D = b["idx"], dim
     ratios = {}
@@ -86,7 +98,7 @@ def check_stages(tag, L, layers, dim, heads, ffn, raw, stages=True):
     def bound(name, measure, got, ref, half):
         yard = measure(half, ref)
         assert yard > 0, name
-        ratios[name] = observed(f"tfstage:{tag}:{name}", measure(got, ref), ht.MARGIN * yard)
+        ratios[name] = observed(f"{family}:{tag}:{name}", measure(got, ref), ht.MARGIN * yard)
 
     thirds = lambda f: (lambda a, r: max(f(a[..., j * D:(j + 1) * D], r[..., j * D:(j + 1) * D]) for j in range(3)))
     if stages:
