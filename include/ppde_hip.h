@@ -273,6 +273,39 @@ int ppde_chains_tempering_state(ppde_chains* c, int32_t* rung, float* beta, int6
 /* rung_history host uint8 [steps_done + 1, n]: the rung each chain held after every iteration (row 0: the start). */
 int ppde_chains_tempering_history(ppde_chains* c, uint8_t* rung_history);
 
+/* Recorder (off by default): thinned samples of the population and per-site letter counts, written on the device inside the
+ * iteration loop (one more kernel behind the accept phase -- behind the swap, with tempering -- of every iteration of a recording
+ * run; no host round trip; valid under graph replay and eager issue alike). A run without a recorder enqueues nothing new.
+ *   recorded iterations: the state after t completed iterations when t > burn_in and (t - burn_in) % every == 0, into row
+ *     (t - burn_in) / every - 1; rows_cap = (max_steps - burn_in) / every; rows_done follows ppde_chains_steps_done;
+ *   slots: rung = -1: every chain is a slot (slot = local chain index); rung = r >= 0 (tempering only): one slot per ensemble,
+ *     filled by the chain that holds rung r AFTER that iteration's swap (the chain whose rung_history entry in row t is r);
+ *   a row holds, per slot, exactly what ppde_chains_peek returns after that iteration: idx from the current states (post-reset
+ *     in the default mode), energy / fitness = row t of the histories (untempered), chain = the local index of the chain;
+ *   site_counts[l][k] = number of recorded (row, slot) pairs with letter k at residue l, over all recorded rows, kept whether or
+ *     not samples are (keep_samples = 0: counts only, no per-row buffers). ppde_chains_init zeroes them.
+ * The recorder changes no other result: histories, best states, traces and Philox streams are those of the run without it.
+ * Valid between ppde_chains_create and ppde_chains_init (the graphs hold the pointers), after ppde_chains_set_tempering when
+ * rung >= 0; NULL clears it. PPDE_ERR_INVALID with a message, the object unchanged: after init; every < 1; burn_in < 0; no row
+ * would fit (rows_cap == 0); rung < -1; rung >= 0 without tempering or rung >= n_rungs; keep_samples not 0 or 1; n_streams > 1
+ * (the counters have one owner per launch). While a recorder with rung >= 0 is set, ppde_chains_set_tempering (to clear or to
+ * replace) is PPDE_ERR_INVALID. The buffers ([rows_cap][slots] rows of state bytes, energy, fitness, chain) belong to the
+ * chains; a failed allocation is PPDE_ERR_HIP and leaves no recorder half-set. */
+typedef struct {
+    int32_t burn_in;      /* >= 0 */
+    int32_t every;        /* >= 1 */
+    int32_t rung;         /* -1: every chain is a slot; r >= 0 (tempering only): one slot per ensemble = the chain holding rung r */
+    int32_t keep_samples; /* 1: keep states/energy/fitness/chain per row; 0: site counts only */
+} ppde_record_config;
+int ppde_chains_set_recorder(ppde_chains* c, const ppde_record_config* cfg /* NULL clears */);
+/* rows recorded so far, row capacity, slots per row. Any pointer may be NULL. PPDE_ERR_INVALID without a recorder. */
+int ppde_chains_recorder_shape(ppde_chains* c, int32_t* rows_done, int32_t* rows_cap, int32_t* slots);
+/* Rows [first_row, first_row + n_rows) to the host; site_counts covers ALL rows recorded so far. Synchronises; any pointer may
+ * be NULL. PPDE_ERR_INVALID: rows beyond rows_done; a sample pointer when keep_samples = 0. */
+int ppde_chains_recorder_read(ppde_chains* c, int first_row, int n_rows,
+                              uint8_t* idx /* [n_rows][slots][L] */, float* energy, float* fitness /* [n_rows][slots] */,
+                              int32_t* chain /* [n_rows][slots], local chain index */, uint64_t* site_counts /* [L][20] */);
+
 /* Start from idx0_dev [n, L] (ppde.py:35-47): evaluates the initial energies, fills history row 0. */
 int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev);
 

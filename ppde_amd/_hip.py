@@ -24,6 +24,11 @@ class ChainConfig(C.Structure):
         [("seed", C.c_uint64), ("chain_offset", C.c_uint64)]
 
 
+class RecordConfig(C.Structure):
+    """ppde_record_config (include/ppde_hip.h)."""
+    _fields_ = [(k, C.c_int32) for k in ("burn_in", "every", "rung", "keep_samples")]
+
+
 class TfWeights(C.Structure):
     """ppde_tf_weights (include/ppde_hip.h): host pointers to ESM-2's fp32 parameters."""
     _PER_LAYER = ("q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "o_w", "o_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b",
@@ -61,6 +66,9 @@ SIGNATURES = {
     "ppde_chains_set_tempering": (_i, [_p, _i, _p, _i]),
     "ppde_chains_tempering_state": (_i, [_p, _p, _p, _p, _p]),
     "ppde_chains_tempering_history": (_i, [_p, _p]),
+    "ppde_chains_set_recorder": (_i, [_p, C.POINTER(RecordConfig)]),
+    "ppde_chains_recorder_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ppde_chains_recorder_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
     "ppde_chains_init": (_i, [_p, _p]),
     "ppde_chains_run": (_i, [_p, _i, _p, _p, _p, _p]),
     "ppde_chains_sync": (_i, [_p]),

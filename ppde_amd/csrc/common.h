@@ -74,7 +74,7 @@ __device__ __forceinline__ void warm_kernargs() {
 struct Geom {
     int L;        // sequence length
     int N;        // L * 20
-    int Ls;       // byte stride of one chain's state row (multiple of 16)
+    int Ls;       // byte stride of one chain's state row (a multiple of 4 with an odd number of dwords: rows are 4-byte aligned only)
     int sh;       // state byte offset of residue 0 (makes the Potts window 4-byte aligned)
     int Lp;       // Potts window length (0 = no Potts expert)
     int i0;       // first residue of the window

@@ -16,6 +16,7 @@
 #include "potts.h"
 #include "cnn.h"
 #include "pas.h"
+#include "record.h"
 
 static thread_local std::string g_err;
 
@@ -1200,7 +1201,28 @@ struct ppde_chains {
     int *rung = nullptr, *slot = nullptr;        // [n], [n/R][R]
     long long *swap_attempts = nullptr, *swap_accepts = nullptr;   // [n/R][R-1]
     uint8_t* rung_hist = nullptr;                // [T+1][n]
+    // recorder (ppde_chains_set_recorder): owned here, allocated there; rec_on false = none
+    bool rec_on = false;
+    ppde_record_config rcfg{};
+    int rec_rows_cap = 0, rec_slots = 0;
+    uint8_t* rec_idx = nullptr;                  // [rows_cap][slots][Ls] (keep_samples)
+    float *rec_e = nullptr, *rec_f = nullptr;    // [rows_cap][slots]
+    int* rec_chain = nullptr;
+    unsigned long long* rec_counts = nullptr;    // [L][20]
 };
+
+static void free_recorder(ppde_chains* c) {
+    if (c->rec_idx) hipFree(c->rec_idx);
+    if (c->rec_e) hipFree(c->rec_e);
+    if (c->rec_f) hipFree(c->rec_f);
+    if (c->rec_chain) hipFree(c->rec_chain);
+    if (c->rec_counts) hipFree(c->rec_counts);
+    c->rec_idx = nullptr; c->rec_e = c->rec_f = nullptr; c->rec_chain = nullptr; c->rec_counts = nullptr;
+    c->rec_on = false; c->rcfg = ppde_record_config{}; c->rec_rows_cap = 0; c->rec_slots = 0;
+}
+static int recorder_rows_done(const ppde_chains* c) {
+    return c->steps_done > c->rcfg.burn_in ? (c->steps_done - c->rcfg.burn_in) / c->rcfg.every : 0;
+}
 
 static void free_tempering(ppde_chains* c) {
     if (c->beta) hipFree(c->beta);
@@ -1364,6 +1386,17 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
         if (rc) return rc;
         if (temper) {                                // (one stream: every chain of the object)
             hipLaunchKernelGGL(k_swap, dim3((c->n + 255) / 256), dim3(256), 0, s, a);
+            HIPCHK(hipGetLastError());
+        }
+        if (c->rec_on) {                             // (one stream: every chain of the object; reads cur, the history rows, slot)
+            const Geom& g = m->g;
+            RecArgs r{};
+            r.it_base = it_base; r.it_local = a.it_local;
+            r.n = c->n; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
+            r.burn_in = c->rcfg.burn_in; r.every = c->rcfg.every; r.rung = c->rcfg.rung; r.n_rungs = c->n_rungs; r.slots = c->rec_slots;
+            r.cur = c->cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist; r.slot = c->slot;
+            r.idx = c->rec_idx; r.energy = c->rec_e; r.fitness = c->rec_f; r.chain = c->rec_chain; r.counts = c->rec_counts;
+            hipLaunchKernelGGL(k_record, dim3(((g.Ls >> 2) + 3) / 4), dim3(REC_BLOCK), 0, s, r);
             HIPCHK(hipGetLastError());
         }
     }
@@ -1531,6 +1564,7 @@ int ppde_chains_destroy(ppde_chains* c) {
     for (void* p : c->allocs) hipFree(p);
     if (c->allowed) hipFree(c->allowed);
     free_tempering(c);
+    free_recorder(c);
     delete c->tfw;
     if (c->h_err) hipHostFree(c->h_err);
     for (hipStream_t st : c->streams) if (st) hipStreamDestroy(st);
@@ -1586,6 +1620,8 @@ int ppde_chains_set_reversible(ppde_chains* c, int on) {
 int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_host, int swap_every) {
     ARGCHK(c, "null argument");
     ARGCHK(!c->initialised, "ppde_chains_set_tempering: the ladder must be set before ppde_chains_init (its graphs hold the kernel choice)");
+    ARGCHK(!(c->rec_on && c->rcfg.rung >= 0), "ppde_chains_set_tempering: a recorder that follows a rung is set; clear it first "
+                                              "(ppde_chains_set_recorder(c, NULL))");
     HIPCHK(hipSetDevice(c->device));
     if (n_rungs == 0 || !beta_host) {               // clear
         free_tempering(c);
@@ -1705,6 +1741,7 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
         rc = init_tempering(c);
         if (rc) return rc;
     }
+    if (c->rec_on) HIPCHK(hipMemset(c->rec_counts, 0, (size_t)g.L * PPDE_A * sizeof(unsigned long long)));   // (a fresh start counts from zero)
     c->steps_done = 0;
     c->initialised = true;
     rc = capture_segments(c);                       // (replayed by every later run; never captured inside one)
@@ -1857,6 +1894,93 @@ int ppde_chains_tempering_history(ppde_chains* c, uint8_t* rung_history) {
     int rc = ppde_chains_sync(c);
     if (rc) return rc;
     HIPCHK(hipMemcpy(rung_history, c->rung_hist, ((size_t)c->steps_done + 1) * c->n, hipMemcpyDeviceToHost));
+    return PPDE_OK;
+}
+
+int ppde_chains_set_recorder(ppde_chains* c, const ppde_record_config* cfg) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_recorder: the recorder must be set before ppde_chains_init (its graphs hold the pointers)");
+    if (!cfg) {                                     // clear
+        HIPCHK(hipSetDevice(c->device));
+        free_recorder(c);
+        return PPDE_OK;
+    }
+    ARGCHK(cfg->every >= 1, "ppde_chains_set_recorder: every must be >= 1");
+    ARGCHK(cfg->burn_in >= 0, "ppde_chains_set_recorder: negative burn_in");
+    ARGCHK(cfg->rung >= -1, "ppde_chains_set_recorder: rung must be -1 (every chain) or a rung of the ladder");
+    ARGCHK(cfg->keep_samples == 0 || cfg->keep_samples == 1, "ppde_chains_set_recorder: keep_samples must be 0 or 1");
+    ARGCHK(cfg->rung < 0 || c->n_rungs > 0, "ppde_chains_set_recorder: following a rung needs tempering (ppde_chains_set_tempering first)");
+    ARGCHK(cfg->rung < c->n_rungs || cfg->rung < 0, "ppde_chains_set_recorder: rung beyond the ladder");
+    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_recorder: n_streams > 1 is not supported (the counters have one "
+                                                            "owner per launch)");
+    const int rows_cap = c->T > cfg->burn_in ? (c->T - cfg->burn_in) / cfg->every : 0;
+    ARGCHK(rows_cap >= 1, "ppde_chains_set_recorder: no iteration of max_steps would be recorded (burn_in + every > max_steps)");
+    HIPCHK(hipSetDevice(c->device));
+    // allocate everything first: a failure leaves the object as it was
+    const Geom& g = c->m->g;
+    const size_t slots = cfg->rung >= 0 ? (size_t)c->n / c->n_rungs : (size_t)c->n, cells = (size_t)rows_cap * slots;
+    const size_t n_counts = (size_t)g.L * PPDE_A;
+    ppde_chains t;                                   // (a holder for free_recorder on the error path)
+    hipError_t e = dalloc(&t.rec_counts, n_counts);
+    if (e == hipSuccess) e = hipMemset(t.rec_counts, 0, n_counts * sizeof(unsigned long long));
+    if (cfg->keep_samples) {
+        if (e == hipSuccess) e = dalloc(&t.rec_idx, cells * (size_t)g.Ls);
+        if (e == hipSuccess) e = hipMemset(t.rec_idx, 0, cells * (size_t)g.Ls);
+        if (e == hipSuccess) e = dalloc(&t.rec_e, cells);
+        if (e == hipSuccess) e = dalloc(&t.rec_f, cells);
+        if (e == hipSuccess) e = dalloc(&t.rec_chain, cells);
+    }
+    if (e != hipSuccess) {
+        free_recorder(&t);
+        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_recorder: device allocation: ") + hipGetErrorString(e));
+    }
+    free_recorder(c);
+    c->rec_counts = t.rec_counts; c->rec_idx = t.rec_idx; c->rec_e = t.rec_e; c->rec_f = t.rec_f; c->rec_chain = t.rec_chain;
+    t.rec_counts = nullptr; t.rec_idx = nullptr; t.rec_e = t.rec_f = nullptr; t.rec_chain = nullptr;
+    c->rec_on = true; c->rcfg = *cfg; c->rec_rows_cap = rows_cap; c->rec_slots = (int)slots;
+    return PPDE_OK;
+}
+
+int ppde_chains_recorder_shape(ppde_chains* c, int32_t* rows_done, int32_t* rows_cap, int32_t* slots) {
+    ARGCHK(c, "null argument");
+    ARGCHK(c->rec_on, "ppde_chains_recorder_shape: no recorder was set (ppde_chains_set_recorder)");
+    if (rows_done) *rows_done = c->initialised ? recorder_rows_done(c) : 0;
+    if (rows_cap) *rows_cap = c->rec_rows_cap;
+    if (slots) *slots = c->rec_slots;
+    return PPDE_OK;
+}
+
+int ppde_chains_recorder_read(ppde_chains* c, int first_row, int n_rows, uint8_t* idx, float* energy, float* fitness,
+                              int32_t* chain, uint64_t* site_counts) {
+    ARGCHK(c && c->initialised, "chains not initialised");
+    ARGCHK(c->rec_on, "ppde_chains_recorder_read: no recorder was set (ppde_chains_set_recorder)");
+    ARGCHK(first_row >= 0 && n_rows >= 0 && (long long)first_row + n_rows <= recorder_rows_done(c),
+           "ppde_chains_recorder_read: rows beyond those recorded so far (ppde_chains_recorder_shape: rows_done)");
+    ARGCHK(c->rcfg.keep_samples || !(idx || energy || fitness || chain),
+           "ppde_chains_recorder_read: the recorder keeps site counts only (keep_samples = 0): pass NULL for the samples");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    const Geom& g = c->m->g;
+    const size_t slots = c->rec_slots, cells = (size_t)n_rows * slots, o = (size_t)first_row * slots;
+    if (idx && cells) {
+        // unpack [rows][slots][Ls] -> [rows][slots][L] through a device buffer, a block of rows at a time (32-bit thread indices)
+        const size_t per_row = slots * (size_t)std::max(g.L, g.Ls);
+        const int block = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_rows, ((size_t)1 << 30) / per_row));
+        DevTmp tmp;
+        HIPCHK(tmp.alloc<uint8_t>((size_t)block * slots * g.L));
+        for (int r = 0; r < n_rows; r += block) {
+            const int nr = std::min(block, n_rows - r), rows_n = (int)((size_t)nr * slots);
+            hipLaunchKernelGGL(k_unpack_state, dim3((rows_n * g.L + 255) / 256), dim3(256), 0, c->stream,
+                               c->rec_idx + (o + (size_t)r * slots) * g.Ls, tmp.as<uint8_t>(), rows_n, g.L, g.Ls, g.sh);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(c->stream));
+            HIPCHK(hipMemcpy(idx + (size_t)r * slots * g.L, tmp.p, (size_t)rows_n * g.L, hipMemcpyDeviceToHost));
+        }
+    }
+    if (energy && cells) HIPCHK(hipMemcpy(energy, c->rec_e + o, cells * sizeof(float), hipMemcpyDeviceToHost));
+    if (fitness && cells) HIPCHK(hipMemcpy(fitness, c->rec_f + o, cells * sizeof(float), hipMemcpyDeviceToHost));
+    if (chain && cells) HIPCHK(hipMemcpy(chain, c->rec_chain + o, cells * sizeof(int), hipMemcpyDeviceToHost));
+    if (site_counts) HIPCHK(hipMemcpy(site_counts, c->rec_counts, (size_t)g.L * PPDE_A * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 

@@ -66,6 +66,18 @@ def broadcast_from(t, src):
     return t
 
 
+def sum_over_ranks(t):
+    """Element-wise sum of a tensor over the ranks, on every rank (the recorder's site counts)."""
+    if active():
+        home = t.device
+        if dist.get_backend() == "nccl" and t.device.type != "cuda":
+            t = t.cuda()
+        t = t.clone()
+        dist.all_reduce(t, op=dist.ReduceOp.SUM)
+        t = t.to(home)
+    return t
+
+
 def agree_from_rank0(values):
     """Rank 0's integers on every rank (random chain index, default seed): ranks that were seeded differently must
     still record the same chain and draw the same Philox stream."""

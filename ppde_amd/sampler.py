@@ -37,6 +37,14 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         population (and every shard boundary) must be a multiple of the ladder; not with ppde_streams > 1.
                         Histories and best states stay on the untempered energy. After run(), `sampler.tempering` holds
                         betas, rung_history [T+1, n], swap_attempts and swap_accepts [n / R, R - 1].
+    ppde_sample_every   0 (default): off. k > 0: the population after every k-th iteration (counted from ppde_sample_burn_in,
+                        default 0) is recorded on the device (include/ppde_hip.h, ppde_chains_set_recorder): no host round trip,
+                        nothing else of the run changes. With a ladder the recorder follows rung ppde_sample_rung (default 0, the
+                        beta[0] chain of every ensemble, wherever the swaps have moved it); without one every chain is a slot.
+                        ppde_sample_counts_only keeps the per-site letter counts only. After run(), `sampler.samples` holds idx
+                        uint8 [rows, slots, L], energy / fitness [rows, slots], chain int [rows, slots] (GLOBAL chain index),
+                        site_counts uint64 [L, 20] and rows; a sharded run gathers the slots in global order and sums the counts.
+                        Not with ppde_streams > 1.
     ppde_shard          False (default). True with torch.distributed initialised: chains are split over ranks
                         and gathered at the end (one RCCL all_gather); every rank returns the full result.
 """
@@ -51,7 +59,22 @@ from . import _hip, library as design_library
 from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
-from .parallel import active as collectives_active, agree_from_rank0, all_gather_rows, broadcast_from, shard_range, world
+from .parallel import active as collectives_active, agree_from_rank0, all_gather_rows, broadcast_from, shard_range, sum_over_ranks, world
+
+
+def recorder_rows(max_steps, burn_in, every):
+    """Row capacity of a recorder over max_steps iterations (include/ppde_hip.h): (max_steps - burn_in) / every."""
+    return (max_steps - burn_in) // every if max_steps > burn_in else 0
+
+
+def recorder_row_of(t, burn_in, every):
+    """Row that holds the state after t completed iterations, or None when that iteration is not recorded."""
+    d = t - burn_in
+    return d // every - 1 if d > 0 and d % every == 0 else None
+
+
+def recorder_rows_done(steps_done, burn_in, every):
+    return recorder_rows(steps_done, burn_in, every)
 
 
 def check_ladder(betas):
@@ -135,6 +158,48 @@ class Chains:
         """uint8 [steps_done + 1, n]: the rung each chain held after every iteration (row 0: the start)."""
         out = np.empty((self.steps_done + 1, self.n), np.uint8)
         _hip.check(self.lib.ppde_chains_tempering_history(self.handle, _hip.ptr(out)))
+        return out
+
+    def set_recorder(self, every, burn_in=0, rung=None, keep_samples=True):
+        """Recorder (include/ppde_hip.h, ppde_chains_set_recorder): the state after t completed iterations is recorded on the
+        device when t > burn_in and (t - burn_in) % every == 0. rung None: every chain is a slot; rung r (tempering, set before):
+        one slot per ensemble, the chain that holds rung r after that iteration's swap. keep_samples False: site counts only.
+        every None clears it. Only before init()."""
+        with torch.cuda.device(self.model.device):
+            if every is None:
+                _hip.check(self.lib.ppde_chains_set_recorder(self.handle, None))
+                self.recorder = None
+                return
+            cfg = _hip.RecordConfig(burn_in=int(burn_in), every=int(every), rung=-1 if rung is None else int(rung),
+                                    keep_samples=int(bool(keep_samples)))
+            _hip.check(self.lib.ppde_chains_set_recorder(self.handle, C.byref(cfg)))
+        self.recorder = dict(every=int(every), burn_in=int(burn_in), rung=None if rung is None else int(rung),
+                             keep_samples=bool(keep_samples))
+
+    def recorder_shape(self):
+        """(rows recorded so far, row capacity, slots per row)."""
+        d, cap, sl = C.c_int32(), C.c_int32(), C.c_int32()
+        _hip.check(self.lib.ppde_chains_recorder_shape(self.handle, C.byref(d), C.byref(cap), C.byref(sl)))
+        return d.value, cap.value, sl.value
+
+    def recorded(self, first=0, count=None):
+        """What the recorder holds: rows [first, first + count) (default: all recorded so far) as idx uint8 [count, slots, L],
+        energy / fitness fp32 [count, slots], chain int32 [count, slots] (local index of the chain that filled the slot) --
+        None for a counts-only recorder --, site_counts uint64 [L, 20] over ALL rows recorded so far, and rows = that number."""
+        done, _, slots = self.recorder_shape()
+        first = int(first)
+        count = done - first if count is None else int(count)
+        L = self.model.L
+        keep = self.recorder["keep_samples"]
+        out = dict(idx=np.empty((max(count, 0), slots, L), np.uint8) if keep else None,
+                   energy=np.empty((max(count, 0), slots), np.float32) if keep else None,
+                   fitness=np.empty((max(count, 0), slots), np.float32) if keep else None,
+                   chain=np.empty((max(count, 0), slots), np.int32) if keep else None,
+                   site_counts=np.zeros((L, 20), np.uint64))
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_recorder_read(self.handle, first, count, *[_hip.ptr(out[k]) for k in (
+                "idx", "energy", "fitness", "chain", "site_counts")]))
+        out["rows"] = done
         return out
 
     def init(self, idx0):
@@ -265,6 +330,27 @@ class PPDE_PAS(BaseSampler):
                 raise ValueError("ppde_swap_every must be >= 0")
             if int(self.n_streams) > 1:
                 raise ValueError("ppde_betas: ppde_streams > 1 is not supported (the swap couples the chains of an ensemble)")
+        self.sample_every = int(getattr(args, "ppde_sample_every", 0) or 0)
+        self.sample_burn_in = int(getattr(args, "ppde_sample_burn_in", 0) or 0)
+        self.sample_rung = getattr(args, "ppde_sample_rung", None)
+        self.sample_counts_only = bool(getattr(args, "ppde_sample_counts_only", False))
+        self.samples = None
+        if self.sample_every < 0:
+            raise ValueError("ppde_sample_every must be >= 0 (0: no recorder)")
+        if self.sample_every == 0 and (self.sample_burn_in or self.sample_rung is not None or self.sample_counts_only):
+            raise ValueError("ppde_sample_burn_in / ppde_sample_rung / ppde_sample_counts_only need ppde_sample_every > 0")
+        if self.sample_every:
+            if self.sample_burn_in < 0:
+                raise ValueError("ppde_sample_burn_in must be >= 0")
+            if int(self.n_streams) > 1:
+                raise ValueError("ppde_sample_every: ppde_streams > 1 is not supported (the recorder's counters have one owner per launch)")
+            if self.betas is None:
+                if self.sample_rung is not None:
+                    raise ValueError("ppde_sample_rung: following a rung needs a ladder (ppde_betas)")
+            else:
+                self.sample_rung = 0 if self.sample_rung is None else int(self.sample_rung)
+                if not 0 <= self.sample_rung < self.betas.size:
+                    raise ValueError(f"ppde_sample_rung must be a rung of the ladder, 0..{self.betas.size - 1}")
         self.noise_bytes = getattr(args, "ppde_noise_bytes", 96 << 20)   # host->device noise is uploaded in chunks of about this size
         self.last_chains = None
         self.timings = {}       # seconds of the last run(): setup (chains + hipGraph capture), iterations, log path, collect
@@ -290,6 +376,9 @@ class PPDE_PAS(BaseSampler):
         R = 0 if self.betas is None else int(self.betas.size)
         if R and n_global % R:
             raise ValueError(f"ppde_betas: the population of {n_global} chains is no multiple of the {R} rungs of the ladder")
+        if self.sample_every and recorder_rows(int(num_steps), self.sample_burn_in, self.sample_every) == 0:
+            raise ValueError(f"ppde_sample_every: no iteration of {int(num_steps)} would be recorded (burn-in {self.sample_burn_in}, "
+                             f"every {self.sample_every})")
         random_idx = np.random.randint(0, n_global)                       # ppde.py:37 (same numpy RNG consumption)
         rank, ws = world() if self.shard else (0, 1)
         if R:
@@ -329,6 +418,8 @@ class PPDE_PAS(BaseSampler):
             chains.set_reversible(True)
         if R:
             chains.set_tempering(self.betas, self.swap_every)
+        if self.sample_every:
+            chains.set_recorder(self.sample_every, self.sample_burn_in, self.sample_rung, not self.sample_counts_only)
         chains.init(idx0[lo:hi])
 
         def gathered(a):
@@ -412,6 +503,23 @@ class PPDE_PAS(BaseSampler):
                 betas=self.betas.copy(),
                 rung_history=all_gather_rows(torch.from_numpy(rh), n_global, dim=1).numpy() if comm else rh,
                 swap_attempts=gathered_ensembles(ts["swap_attempts"]), swap_accepts=gathered_ensembles(ts["swap_accepts"]))
+        self.samples = None
+        if self.sample_every:
+            rec = chains.recorded()
+            n_slots = n_global // R if R else n_global                 # (shard boundaries are multiples of R: equal slot blocks)
+
+            def slots_gathered(a):
+                return all_gather_rows(torch.from_numpy(a), n_slots, dim=1).numpy() if comm else a
+
+            counts = rec["site_counts"]
+            if comm:
+                total = torch.from_numpy(counts.astype(np.int64))
+                counts = sum_over_ranks(total).numpy().astype(np.uint64)
+            self.samples = dict(rows=rec["rows"], site_counts=counts, idx=None, energy=None, fitness=None, chain=None)
+            if not self.sample_counts_only:
+                self.samples.update(idx=slots_gathered(rec["idx"]), energy=slots_gathered(rec["energy"]),
+                                    fitness=slots_gathered(rec["fitness"]),
+                                    chain=slots_gathered(rec["chain"].astype(np.int64) + lo))
         if n_global == 1:
             # the reference's single-chain shapes (ppde.py:178-183; the ensemble's `.squeeze()`, nets.py:442, makes one chain's
             # fitness a scalar): fitness_history (T+1,) next to energy_history (T+1, 1); with ProteinSupervised the energy IS

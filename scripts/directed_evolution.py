@@ -12,7 +12,10 @@ the MSA-Transformer scoring are out of scope.
 Extra flags: --ppde_rng {torch,philox}, --ppde_seed, --ppde_reuse_grad {0,1}, --ppde_shard (with torchrun), --ppde_full_grad,
 --ppde_timing; design library (the letters the sampler may propose per residue): --ppde_sites, --ppde_exclude, --ppde_library;
 --ppde_reversible (chains that sample exp(energy)/Z over the library); --ppde_betas, --ppde_swap_every (parallel tempering of such
-a run: a ladder of inverse temperatures with replica exchange).
+a run: a ladder of inverse temperatures with replica exchange); --ppde_sample_every, --ppde_sample_burn_in, --ppde_sample_rung,
+--ppde_sample_counts_only (thinned samples of the population and per-site letter counts, recorded on the device: samples.npy
+[rows, slots, L] uint8, sample_energy.npy, sample_fitness.npy, sample_chain.npy [rows, slots], site_counts.npy [L, 20]). A run with
+a ladder also writes rung_history.npy [T+1, n], swap_attempts.npy and swap_accepts.npy [n / R, R - 1].
 """
 import argparse
 import datetime
@@ -128,6 +131,18 @@ def main(args):
         np.save(results_path / "energy_scores.npy", best_energy)
         np.save(results_path / "energy_history.npy", energy_history)
         np.save(results_path / "fitness_history.npy", fitness_history)
+        tempering = getattr(sampler, "tempering", None)
+        if tempering is not None:
+            for name in ("rung_history", "swap_attempts", "swap_accepts"):
+                np.save(results_path / f"{name}.npy", tempering[name])
+        samples = getattr(sampler, "samples", None)
+        if samples is not None:
+            np.save(results_path / "site_counts.npy", samples["site_counts"])
+            if samples["idx"] is not None:
+                np.save(results_path / "samples.npy", samples["idx"])
+                np.save(results_path / "sample_energy.npy", samples["energy"])
+                np.save(results_path / "sample_fitness.npy", samples["fitness"])
+                np.save(results_path / "sample_chain.npy", samples["chain"])
 
     if not args.disable_MSA_transformer_scoring:
         print("MSA-Transformer scoring is not part of this build (needs the ESM-MSA-1b weights); skipped")
@@ -208,6 +223,15 @@ def build_parser():
     pp.add_argument("--ppde_swap_every", type=int, default=1,
                     help="with --ppde_betas: neighbouring rungs of an ensemble propose to exchange their temperatures every this "
                          "many iterations (0: never)")
+    pp.add_argument("--ppde_sample_every", type=int, default=0,
+                    help="record the population on the device after every this many iterations (0: off): samples.npy, "
+                         "sample_energy.npy, sample_fitness.npy, sample_chain.npy and site_counts.npy next to the other results. "
+                         "Works with either --ppde_rng")
+    pp.add_argument("--ppde_sample_burn_in", type=int, default=0, help="iterations before the first recorded one is counted from")
+    pp.add_argument("--ppde_sample_rung", type=int, default=None,
+                    help="with --ppde_betas: the rung whose chain is recorded in every ensemble, followed through the swaps "
+                         "(default 0, the beta[0] sample)")
+    pp.add_argument("--ppde_sample_counts_only", action="store_true", help="keep site_counts.npy only, no per-row samples")
     return parser
 
 
