@@ -306,6 +306,29 @@ int ppde_chains_recorder_read(ppde_chains* c, int first_row, int n_rows,
                               uint8_t* idx /* [n_rows][slots][L] */, float* energy, float* fitness /* [n_rows][slots] */,
                               int32_t* chain /* [n_rows][slots], local chain index */, uint64_t* site_counts /* [L][20] */);
 
+/* Pair counts (off by default): the second moment next to the recorder's first, counted on the device by one more kernel directly
+ * behind the recorder's in every iteration (ppde_amd/csrc/pairs.h); a run without them enqueues nothing new.
+ *   pair_counts[i][a][j][b] = number of recorded (row, slot) pairs with letter a at residue sites[i] and letter b at residue
+ *     sites[j]: the same recorded iterations and slots as site_counts (the recorder's burn_in, every and rung), read from the
+ *     current states, so kept whether or not samples are. As a matrix [S 20][S 20] it is the Gram matrix of the one-hot rows of
+ *     the recorded samples restricted to `sites`: symmetric, diagonal blocks diag(site_counts[sites[i]]). ppde_chains_init zeroes it.
+ *   sites: S strictly increasing residues of the full sequence, 0-based; n_sites = 0 with sites = NULL selects every residue.
+ *     The list is copied.
+ * Valid with a recorder set and before ppde_chains_init (the graphs hold the pointers); NULL clears them. PPDE_ERR_INVALID with a
+ * message, the object unchanged: no recorder; after init; n_sites < 0 or > L; n_sites > 0 with sites = NULL; n_sites = 0 with a
+ * list; a site outside [0, L); sites not strictly increasing. While pair counts are set, ppde_chains_set_recorder (to clear or to
+ * replace) is PPDE_ERR_INVALID: clear the pair counts first. The chains own the buffers; a failed allocation is PPDE_ERR_HIP and
+ * leaves nothing half-set. */
+typedef struct {
+    int32_t n_sites;       /* 0 (with sites = NULL): every residue */
+    const int32_t* sites;  /* [n_sites], strictly increasing, each in [0, L) */
+} ppde_pair_config;
+int ppde_chains_set_pair_counts(ppde_chains* c, const ppde_pair_config* cfg /* NULL clears */);
+/* Number of sites and the list itself. Any pointer may be NULL. PPDE_ERR_INVALID without pair counts. */
+int ppde_chains_pair_counts_shape(ppde_chains* c, int32_t* n_sites, int32_t* sites /* [S] or NULL */);
+/* The counts over ALL rows recorded so far, full and symmetric. Synchronises. PPDE_ERR_INVALID without pair counts or before init. */
+int ppde_chains_pair_counts_read(ppde_chains* c, uint64_t* pair_counts /* [S][20][S][20] */);
+
 /* Start from idx0_dev [n, L] (ppde.py:35-47): evaluates the initial energies, fills history row 0. */
 int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev);
 

@@ -17,6 +17,7 @@
 #include "cnn.h"
 #include "pas.h"
 #include "record.h"
+#include "pairs.h"
 
 static thread_local std::string g_err;
 
@@ -1209,6 +1210,12 @@ struct ppde_chains {
     float *rec_e = nullptr, *rec_f = nullptr;    // [rows_cap][slots]
     int* rec_chain = nullptr;
     unsigned long long* rec_counts = nullptr;    // [L][20]
+    // pair counts (ppde_chains_set_pair_counts): owned here, allocated there; pair_on false = none
+    bool pair_on = false;
+    std::vector<int32_t> pair_sites;             // [S] residues, strictly increasing
+    int pair_nt = 0;                             // tiles per side (pairs.h)
+    int* pair_sites_dev = nullptr;               // [pair_nt * PAIR_TS], padded with -1
+    unsigned long long* pair_counts = nullptr;   // [pair_nt (pair_nt + 1) / 2][PAIR_TILE]
 };
 
 static void free_recorder(ppde_chains* c) {
@@ -1220,6 +1227,13 @@ static void free_recorder(ppde_chains* c) {
     c->rec_idx = nullptr; c->rec_e = c->rec_f = nullptr; c->rec_chain = nullptr; c->rec_counts = nullptr;
     c->rec_on = false; c->rcfg = ppde_record_config{}; c->rec_rows_cap = 0; c->rec_slots = 0;
 }
+static void free_pairs(ppde_chains* c) {
+    if (c->pair_sites_dev) hipFree(c->pair_sites_dev);
+    if (c->pair_counts) hipFree(c->pair_counts);
+    c->pair_sites_dev = nullptr; c->pair_counts = nullptr;
+    c->pair_on = false; c->pair_sites.clear(); c->pair_nt = 0;
+}
+static size_t pair_tiles(const ppde_chains* c) { return (size_t)c->pair_nt * ((size_t)c->pair_nt + 1) / 2; }
 static int recorder_rows_done(const ppde_chains* c) {
     return c->steps_done > c->rcfg.burn_in ? (c->steps_done - c->rcfg.burn_in) / c->rcfg.every : 0;
 }
@@ -1398,6 +1412,14 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
             r.idx = c->rec_idx; r.energy = c->rec_e; r.fitness = c->rec_f; r.chain = c->rec_chain; r.counts = c->rec_counts;
             hipLaunchKernelGGL(k_record, dim3(((g.Ls >> 2) + 3) / 4), dim3(REC_BLOCK), 0, s, r);
             HIPCHK(hipGetLastError());
+            if (c->pair_on) {                        // (the same schedule and slots; reads cur and slot only)
+                PairArgs p{};
+                p.it_base = it_base; p.it_local = a.it_local; p.Ls = g.Ls; p.sh = g.sh;
+                p.burn_in = r.burn_in; p.every = r.every; p.rung = r.rung; p.n_rungs = r.n_rungs; p.slots = r.slots;
+                p.nt = c->pair_nt; p.cur = c->cur; p.slot = c->slot; p.sites = c->pair_sites_dev; p.counts = c->pair_counts;
+                hipLaunchKernelGGL(k_record_pairs, dim3((unsigned)pair_tiles(c)), dim3(PAIR_BLOCK), 0, s, p);
+                HIPCHK(hipGetLastError());
+            }
         }
     }
     return PPDE_OK;
@@ -1565,6 +1587,7 @@ int ppde_chains_destroy(ppde_chains* c) {
     if (c->allowed) hipFree(c->allowed);
     free_tempering(c);
     free_recorder(c);
+    free_pairs(c);
     delete c->tfw;
     if (c->h_err) hipHostFree(c->h_err);
     for (hipStream_t st : c->streams) if (st) hipStreamDestroy(st);
@@ -1742,6 +1765,7 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
         if (rc) return rc;
     }
     if (c->rec_on) HIPCHK(hipMemset(c->rec_counts, 0, (size_t)g.L * PPDE_A * sizeof(unsigned long long)));   // (a fresh start counts from zero)
+    if (c->pair_on) HIPCHK(hipMemset(c->pair_counts, 0, pair_tiles(c) * PAIR_TILE * sizeof(unsigned long long)));
     c->steps_done = 0;
     c->initialised = true;
     rc = capture_segments(c);                       // (replayed by every later run; never captured inside one)
@@ -1900,6 +1924,8 @@ int ppde_chains_tempering_history(ppde_chains* c, uint8_t* rung_history) {
 int ppde_chains_set_recorder(ppde_chains* c, const ppde_record_config* cfg) {
     ARGCHK(c, "null argument");
     ARGCHK(!c->initialised, "ppde_chains_set_recorder: the recorder must be set before ppde_chains_init (its graphs hold the pointers)");
+    ARGCHK(!c->pair_on, "ppde_chains_set_recorder: pair counts are set and follow this recorder's schedule; clear the pair counts first "
+                        "(ppde_chains_set_pair_counts(c, NULL))");
     if (!cfg) {                                     // clear
         HIPCHK(hipSetDevice(c->device));
         free_recorder(c);
@@ -1981,6 +2007,93 @@ int ppde_chains_recorder_read(ppde_chains* c, int first_row, int n_rows, uint8_t
     if (fitness && cells) HIPCHK(hipMemcpy(fitness, c->rec_f + o, cells * sizeof(float), hipMemcpyDeviceToHost));
     if (chain && cells) HIPCHK(hipMemcpy(chain, c->rec_chain + o, cells * sizeof(int), hipMemcpyDeviceToHost));
     if (site_counts) HIPCHK(hipMemcpy(site_counts, c->rec_counts, (size_t)g.L * PPDE_A * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PPDE_OK;
+}
+
+int ppde_chains_set_pair_counts(ppde_chains* c, const ppde_pair_config* cfg) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_pair_counts: pair counts must be set before ppde_chains_init (its graphs hold the pointers)");
+    if (!cfg) {                                     // clear
+        HIPCHK(hipSetDevice(c->device));
+        free_pairs(c);
+        return PPDE_OK;
+    }
+    ARGCHK(c->rec_on, "ppde_chains_set_pair_counts: no recorder was set (pair counts follow its schedule and slots: "
+                      "ppde_chains_set_recorder first)");
+    const int L = c->m->g.L;
+    ARGCHK(cfg->n_sites >= 0 && cfg->n_sites <= L, "ppde_chains_set_pair_counts: n_sites must be in 0..L (0: every residue)");
+    ARGCHK(cfg->n_sites == 0 || cfg->sites, "ppde_chains_set_pair_counts: n_sites > 0 needs a site list");
+    ARGCHK(cfg->n_sites > 0 || !cfg->sites, "ppde_chains_set_pair_counts: a site list with n_sites = 0 (0 with NULL selects every residue)");
+    const int S = cfg->n_sites ? cfg->n_sites : L;
+    for (int i = 0; i < cfg->n_sites; ++i) {
+        if (cfg->sites[i] < 0 || cfg->sites[i] >= L)
+            return fail(PPDE_ERR_INVALID, "ppde_chains_set_pair_counts: sites[" + std::to_string(i) + "] = " + std::to_string(cfg->sites[i]) +
+                                          " lies outside the sequence 0.." + std::to_string(L - 1));
+        if (i > 0 && cfg->sites[i] <= cfg->sites[i - 1])
+            return fail(PPDE_ERR_INVALID, "ppde_chains_set_pair_counts: the sites must be strictly increasing (sites[" + std::to_string(i) +
+                                          "] <= sites[" + std::to_string(i - 1) + "])");
+    }
+    HIPCHK(hipSetDevice(c->device));
+    // allocate everything first: a failure leaves the object as it was
+    ppde_chains t;                                   // (a holder for free_pairs on the error path)
+    t.pair_nt = (S + PAIR_TS - 1) / PAIR_TS;
+    std::vector<int32_t> padded((size_t)t.pair_nt * PAIR_TS, -1);
+    for (int i = 0; i < S; ++i) padded[i] = cfg->n_sites ? cfg->sites[i] : i;
+    const size_t n_counts = pair_tiles(&t) * PAIR_TILE;
+    hipError_t e = dalloc(&t.pair_sites_dev, padded.size());
+    if (e == hipSuccess) e = hipMemcpy(t.pair_sites_dev, padded.data(), padded.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dalloc(&t.pair_counts, n_counts);
+    if (e == hipSuccess) e = hipMemset(t.pair_counts, 0, n_counts * sizeof(unsigned long long));
+    if (e != hipSuccess) {
+        free_pairs(&t);
+        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_pair_counts: device allocation: ") + hipGetErrorString(e));
+    }
+    free_pairs(c);
+    c->pair_sites_dev = t.pair_sites_dev; c->pair_counts = t.pair_counts; c->pair_nt = t.pair_nt;
+    t.pair_sites_dev = nullptr; t.pair_counts = nullptr;
+    c->pair_sites.assign(padded.begin(), padded.begin() + S);
+    c->pair_on = true;
+    return PPDE_OK;
+}
+
+int ppde_chains_pair_counts_shape(ppde_chains* c, int32_t* n_sites, int32_t* sites) {
+    ARGCHK(c, "null argument");
+    ARGCHK(c->pair_on, "ppde_chains_pair_counts_shape: no pair counts were set (ppde_chains_set_pair_counts)");
+    if (n_sites) *n_sites = (int32_t)c->pair_sites.size();
+    if (sites) std::copy(c->pair_sites.begin(), c->pair_sites.end(), sites);
+    return PPDE_OK;
+}
+
+int ppde_chains_pair_counts_read(ppde_chains* c, uint64_t* pair_counts) {
+    ARGCHK(c && c->initialised, "chains not initialised");
+    ARGCHK(c->pair_on, "ppde_chains_pair_counts_read: no pair counts were set (ppde_chains_set_pair_counts)");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    if (!pair_counts) return PPDE_OK;
+    // the device keeps the upper block triangle, tile by tile (pairs.h): one row of tiles at a time to the host, mirrored here
+    const size_t S = c->pair_sites.size(), W = S * PPDE_A;
+    const int nt = c->pair_nt;
+    std::vector<unsigned long long> rowbuf((size_t)nt * PAIR_TILE);
+    size_t first = 0;
+    for (int ti = 0; ti < nt; ++ti) {
+        const size_t tiles = (size_t)(nt - ti);
+        HIPCHK(hipMemcpy(rowbuf.data(), c->pair_counts + first * PAIR_TILE, tiles * PAIR_TILE * sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost));
+        first += tiles;
+        for (int tj = ti; tj < nt; ++tj)
+            for (int p = 0; p < PAIR_TS; ++p)
+                for (int q = 0; q < PAIR_TS; ++q) {
+                    const size_t i = (size_t)ti * PAIR_TS + p, j = (size_t)tj * PAIR_TS + q;
+                    if (i >= S || j >= S) continue;
+                    const unsigned long long* bins = rowbuf.data() + ((size_t)(tj - ti) * PAIR_TS * PAIR_TS + p * PAIR_TS + q) * PAIR_BINS;
+                    for (int x = 0; x < PPDE_A; ++x)
+                        for (int y = 0; y < PPDE_A; ++y) {
+                            const uint64_t v = bins[x * PPDE_A + y];
+                            pair_counts[(i * PPDE_A + x) * W + j * PPDE_A + y] = v;
+                            if (tj != ti) pair_counts[(j * PPDE_A + y) * W + i * PPDE_A + x] = v;
+                        }
+                }
+    }
     return PPDE_OK;
 }
 

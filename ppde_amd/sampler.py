@@ -45,6 +45,12 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         uint8 [rows, slots, L], energy / fitness [rows, slots], chain int [rows, slots] (GLOBAL chain index),
                         site_counts uint64 [L, 20] and rows; a sharded run gathers the slots in global order and sums the counts.
                         Not with ppde_streams > 1.
+    ppde_sample_pairs   None or '' (default): off. With ppde_sample_every > 0: pairwise letter co-occurrence counts of the same
+                        recorded rows and slots (include/ppde_hip.h, ppde_chains_set_pair_counts), kept with
+                        ppde_sample_counts_only too. 'all': every residue; 'open': the open residues of the run's library
+                        (without one: min_pos..max_pos); a site list in library.parse_sites syntax ('8-20,33') or a strictly
+                        increasing sequence of 0-based residues. After run(), `sampler.samples` also holds pair_counts uint64
+                        [S, 20, S, 20] and pair_sites int32 [S] (both None when off); a sharded run sums the counts.
     ppde_shard          False (default). True with torch.distributed initialised: chains are split over ranks
                         and gathered at the end (one RCCL all_gather); every rank returns the full result.
 """
@@ -75,6 +81,50 @@ def recorder_row_of(t, burn_in, every):
 
 def recorder_rows_done(steps_done, burn_in, every):
     return recorder_rows(steps_done, burn_in, every)
+
+
+def check_pair_spec(spec):
+    """ppde_sample_pairs as None (off), 'all', 'open', a site-list string, or a strictly increasing tuple of residues; ValueError
+    otherwise. Whether the residues lie inside the sequence is checked by pair_sites_of, once its length is known."""
+    if spec is None or (isinstance(spec, str) and spec.strip() == ""):
+        return None
+    if isinstance(spec, str):
+        word = spec.strip()
+        if word.lower() in ("all", "open"):
+            return word.lower()
+        try:
+            design_library.parse_sites(word, 1 << 30)         # (syntax only)
+        except ValueError as e:
+            raise ValueError(f"ppde_sample_pairs: {e} (or 'all', 'open')") from None
+        return word
+    try:
+        sites = tuple(int(v) for v in spec)
+        exact = all(float(v) == int(v) for v in spec)
+    except (TypeError, ValueError):
+        raise ValueError(f"ppde_sample_pairs: expected 'all', 'open', a site list like '8-20,33' or a sequence of residues, got {spec!r}") from None
+    if not exact or not sites:
+        raise ValueError(f"ppde_sample_pairs: a sequence of residues must hold at least one whole number, got {spec!r}")
+    if sites[0] < 0 or any(b <= a for a, b in zip(sites, sites[1:])):
+        raise ValueError(f"ppde_sample_pairs: residues must be >= 0 and strictly increasing, got {spec!r}")
+    return sites
+
+
+def pair_sites_of(spec, L, min_pos, max_pos, lib_words=None):
+    """The residues a checked ppde_sample_pairs selects in a sequence of L: None for every residue, else int32 [S]."""
+    if spec == "all":
+        return None
+    if spec == "open":
+        if lib_words is not None:
+            return design_library.open_sites(lib_words).astype(np.int32)
+        return np.arange(int(min_pos), int(max_pos) + 1, dtype=np.int32)
+    if isinstance(spec, str):
+        try:
+            return np.asarray(design_library.parse_sites(spec, L), np.int32)
+        except ValueError as e:
+            raise ValueError(f"ppde_sample_pairs: {e}") from None
+    if spec[-1] >= L:
+        raise ValueError(f"ppde_sample_pairs: residue {spec[-1]} lies outside the sequence 0..{L - 1}")
+    return np.asarray(spec, np.int32)
 
 
 def check_ladder(betas):
@@ -201,6 +251,32 @@ class Chains:
                 "idx", "energy", "fitness", "chain", "site_counts")]))
         out["rows"] = done
         return out
+
+    def set_pair_counts(self, sites=None):
+        """Pair counts (include/ppde_hip.h, ppde_chains_set_pair_counts): letter co-occurrence counts over the recorder's rows and
+        slots at `sites`, a strictly increasing list of 0-based residues (None: every residue). Needs a recorder; only before
+        init()."""
+        arr = None if sites is None else np.ascontiguousarray(np.asarray(sites, dtype=np.int32).reshape(-1))
+        cfg = _hip.PairConfig(n_sites=0 if arr is None else int(arr.size),
+                              sites=None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_int32)))
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_set_pair_counts(self.handle, C.byref(cfg)))
+
+    def clear_pair_counts(self):
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_set_pair_counts(self.handle, None))
+
+    def pair_counts(self):
+        """(counts uint64 [S, 20, S, 20] over ALL rows recorded so far, sites int32 [S]): counts[i, a, j, b] = recorded (row, slot)
+        pairs with letter a at residue sites[i] and letter b at residue sites[j]."""
+        S = C.c_int32()
+        _hip.check(self.lib.ppde_chains_pair_counts_shape(self.handle, C.byref(S), None))
+        sites = np.empty(S.value, np.int32)
+        _hip.check(self.lib.ppde_chains_pair_counts_shape(self.handle, None, _hip.ptr(sites)))
+        counts = np.zeros((S.value, 20, S.value, 20), np.uint64)
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_pair_counts_read(self.handle, _hip.ptr(counts)))
+        return counts, sites
 
     def init(self, idx0):
         idx0 = idx0.to(self.model.device, torch.uint8).contiguous()
@@ -335,6 +411,9 @@ class PPDE_PAS(BaseSampler):
         self.sample_rung = getattr(args, "ppde_sample_rung", None)
         self.sample_counts_only = bool(getattr(args, "ppde_sample_counts_only", False))
         self.samples = None
+        self.sample_pairs = check_pair_spec(getattr(args, "ppde_sample_pairs", None))
+        if self.sample_pairs is not None and self.sample_every <= 0:
+            raise ValueError("ppde_sample_pairs needs ppde_sample_every > 0 (pair counts follow the recorder's schedule)")
         if self.sample_every < 0:
             raise ValueError("ppde_sample_every must be >= 0 (0: no recorder)")
         if self.sample_every == 0 and (self.sample_burn_in or self.sample_rung is not None or self.sample_counts_only):
@@ -379,6 +458,14 @@ class PPDE_PAS(BaseSampler):
         if self.sample_every and recorder_rows(int(num_steps), self.sample_burn_in, self.sample_every) == 0:
             raise ValueError(f"ppde_sample_every: no iteration of {int(num_steps)} would be recorded (burn-in {self.sample_burn_in}, "
                              f"every {self.sample_every})")
+        pair_on, pair_sites = self.sample_pairs is not None, None
+        if pair_on:                                     # (host only: the library's words as the chains will get them)
+            words = lib_words
+            if words is None and self.library is not None:
+                words = design_library.fold_range(design_library.as_words(self.library, L), min_pos, max_pos)
+            pair_sites = pair_sites_of(self.sample_pairs, L, min_pos, max_pos, words)
+            if pair_sites is not None and pair_sites.size == 0:
+                raise ValueError("ppde_sample_pairs: the selection holds no residue")
         random_idx = np.random.randint(0, n_global)                       # ppde.py:37 (same numpy RNG consumption)
         rank, ws = world() if self.shard else (0, 1)
         if R:
@@ -420,6 +507,8 @@ class PPDE_PAS(BaseSampler):
             chains.set_tempering(self.betas, self.swap_every)
         if self.sample_every:
             chains.set_recorder(self.sample_every, self.sample_burn_in, self.sample_rung, not self.sample_counts_only)
+        if pair_on:
+            chains.set_pair_counts(pair_sites)
         chains.init(idx0[lo:hi])
 
         def gathered(a):
@@ -515,7 +604,13 @@ class PPDE_PAS(BaseSampler):
             if comm:
                 total = torch.from_numpy(counts.astype(np.int64))
                 counts = sum_over_ranks(total).numpy().astype(np.uint64)
-            self.samples = dict(rows=rec["rows"], site_counts=counts, idx=None, energy=None, fitness=None, chain=None)
+            self.samples = dict(rows=rec["rows"], site_counts=counts, idx=None, energy=None, fitness=None, chain=None,
+                                pair_counts=None, pair_sites=None)
+            if pair_on:
+                pc, ps = chains.pair_counts()
+                if comm:
+                    pc = sum_over_ranks(torch.from_numpy(pc.astype(np.int64))).numpy().astype(np.uint64)
+                self.samples.update(pair_counts=pc, pair_sites=ps)
             if not self.sample_counts_only:
                 self.samples.update(idx=slots_gathered(rec["idx"]), energy=slots_gathered(rec["energy"]),
                                     fitness=slots_gathered(rec["fitness"]),

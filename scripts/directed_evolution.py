@@ -13,7 +13,7 @@ Extra flags: --ppde_rng {torch,philox}, --ppde_seed, --ppde_reuse_grad {0,1}, --
 --ppde_timing; design library (the letters the sampler may propose per residue): --ppde_sites, --ppde_exclude, --ppde_library;
 --ppde_reversible (chains that sample exp(energy)/Z over the library); --ppde_betas, --ppde_swap_every (parallel tempering of such
 a run: a ladder of inverse temperatures with replica exchange); --ppde_sample_every, --ppde_sample_burn_in, --ppde_sample_rung,
---ppde_sample_counts_only (thinned samples of the population and per-site letter counts, recorded on the device: samples.npy
+--ppde_sample_counts_only, --ppde_sample_pairs (thinned samples of the population and per-site letter counts, recorded on the device: samples.npy
 [rows, slots, L] uint8, sample_energy.npy, sample_fitness.npy, sample_chain.npy [rows, slots], site_counts.npy [L, 20]). A run with
 a ladder also writes rung_history.npy [T+1, n], swap_attempts.npy and swap_accepts.npy [n / R, R - 1].
 """
@@ -138,6 +138,9 @@ def main(args):
         samples = getattr(sampler, "samples", None)
         if samples is not None:
             np.save(results_path / "site_counts.npy", samples["site_counts"])
+            if samples.get("pair_counts") is not None:
+                np.save(results_path / "pair_counts.npy", samples["pair_counts"])
+                np.save(results_path / "pair_sites.npy", samples["pair_sites"])
             if samples["idx"] is not None:
                 np.save(results_path / "samples.npy", samples["idx"])
                 np.save(results_path / "sample_energy.npy", samples["energy"])
@@ -232,6 +235,12 @@ def build_parser():
                     help="with --ppde_betas: the rung whose chain is recorded in every ensemble, followed through the swaps "
                          "(default 0, the beta[0] sample)")
     pp.add_argument("--ppde_sample_counts_only", action="store_true", help="keep site_counts.npy only, no per-row samples")
+    pp.add_argument("--ppde_sample_pairs", metavar="SPEC", type=str, default=None,
+                    help="with --ppde_sample_every: also count, on the device, how often letter a at residue i and letter b at "
+                         "residue j occur together in the recorded samples: pair_counts.npy uint64 [S, 20, S, 20] and "
+                         "pair_sites.npy int32 [S]. SPEC is 'all' (every residue), 'open' (the open residues of the design "
+                         "library; without one the window the sampler moves in) or a site list in --ppde_sites syntax. The file "
+                         "holds (20 S)^2 * 8 bytes: 29 MB at 96 sites. Kept with --ppde_sample_counts_only too")
     return parser
 
 
