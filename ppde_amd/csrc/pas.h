@@ -613,9 +613,11 @@ __device__ __forceinline__ void reverse_rows(const PasArgs& a, const RowLds& lds
 //  * a fixed softmax reference for all rows of the path, as in propose_body_dev: half the largest spread of a residue's 20
 //    gradient entries bounds every reverse logit (the default mode takes no masks on the way back; reversible mode's masks
 //    only send entries to -inf), so no maximum is reduced per row;
-//  * the rows of a path differ only at the residues the path moves: a wave none of whose lanes holds such a residue
-//    evaluates its exponentials ONCE and uses them for every row (the clamp and the row sums still run per row: the
-//    normalisation differs).
+//  * the rows of a path differ only at the residues the path moves: a wave evaluates the exponentials of the pass's first row
+//    and, after that, of a row only when one of its lanes holds the residue that row's sub-step moved; every other row is a copy
+//    of the row before it -- the same inputs through the same operations, so the same bits (the clamp and the row sums still run
+//    per row: the normalisation differs). A wave that holds no residue of the path evaluates ONE row, a wave that holds the
+//    residue of sub-step j the rows 0 and j.
 template <int GPT, int NR, bool REV = false, bool LIB = false, bool TEMP = false>
 __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds& lds, RowRegs<GPT>& R, int s0, const float mref,
                                                  const float e0ref, float& log_ratio, RevPath& rp, float beta = 1.f) {
@@ -625,7 +627,7 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
     int ls[NR], ks[NR];
     int ro[NR];                                      // REV: the letter each sub-step replaced
     bool rc[NR];                                     //      and whether the state behind it sits at the mutation cap
-    bool mine = false, anycap = false;
+    bool mine[NR], anycap = false;                   // mine[j]: this lane holds the residue sub-step s0 + j moves
     uint32_t ok4[GPT];
 #pragma unroll
     for (int r = 0; r < GPT; ++r) {
@@ -634,6 +636,7 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
     }
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
+        mine[j] = false;
         const int ent = lds.mv[s0 + j];
         const int win = REV ? (ent & 0xffff) : ent;
         ls[j] = win / 20; ks[j] = win - 20 * ls[j];
@@ -644,11 +647,8 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
             anycap |= rc[j];
         }
 #pragma unroll
-        for (int r = 0; r < GPT; ++r) mine |= R.valid[r] & (R.l[r] == ls[j]);
+        for (int r = 0; r < GPT; ++r) mine[j] |= R.valid[r] & (R.l[r] == ls[j]);
     }
-    // REV: the cap's mask changes every entry of a row, so the shared evaluation below holds only while no row of the pass is capped
-    bool split = __any(mine);
-    if constexpr (REV) split = split || anycap;
     float4 e[NR][GPT];
     float sw[NR];
     auto row_exp = [&](int j) {
@@ -670,21 +670,19 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
         }
         sw[j] = wave_sum(sm);
     };
-    if (split) {
 #pragma unroll
-        for (int j = 0; j < NR; ++j) {
+    for (int j = 0; j < NR; ++j) {
 #pragma unroll
-            for (int r = 0; r < GPT; ++r)
-                if (R.l[r] == ls[j]) R.cur[r] = ks[j];          // state after sub-step s0 + j
-            row_exp(j);
-        }
-    } else {                                                     // (no lane's residue moves: one evaluation for all rows)
-        row_exp(0);
+        for (int r = 0; r < GPT; ++r)
+            if (R.l[r] == ls[j]) R.cur[r] = ks[j];              // state after sub-step s0 + j
+        // REV: the cap's mask changes every entry of a row, so a copy holds only while no row of the pass is capped
+        bool fresh = j == 0 || __any(mine[j]);
+        if constexpr (REV) fresh = fresh || anycap;
+        if (fresh) row_exp(j);
+        else {                                                   // (no lane's letters differ from the row before: its bits)
+            sw[j] = sw[j > 0 ? j - 1 : 0];
 #pragma unroll
-        for (int j = 1; j < NR; ++j) {
-            sw[j] = sw[0];
-#pragma unroll
-            for (int r = 0; r < GPT; ++r) e[j][r] = e[0][r];
+            for (int r = 0; r < GPT; ++r) e[j][r] = e[j > 0 ? j - 1 : 0][r];
         }
     }
     if (lane == 0) {
@@ -1179,6 +1177,7 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
             float vw;
             const int wl = wave_argmax_lane(bv, bl, vw);
             const int ls = min(__builtin_amdgcn_readlane(bl, wl), g.L - 1);
+            PPDE_STAMP(a.dbg, s > 0 ? 15 : 20, stamp);
             // (d) the letter inside the winning residue (lane = letter)
             const int kl = min(lane, PPDE_A - 1);
             float pk = __builtin_amdgcn_fmed3f(E[ls * PPDE_A + kl] * c, PPDE_EPS, 1.0f - PPDE_EPS);

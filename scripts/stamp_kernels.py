@@ -31,9 +31,10 @@ lib.ppde_debug_read_stamps.restype = C.c_int
 lib.ppde_debug_read_stamps.argtypes = [C.c_void_p, C.c_void_p]
 NAMES = {0: "potts entry", 1: "potts DMAs issued", 2: "potts states landed+barrier", 3: "potts gather done",
          4: "potts part sums exchanged", 5: "potts end",
-         8: "propose entry", 9: "propose row staged", 10: "propose s0 logits", 11: "propose s0 max/sumexp merged",
-         12: "propose s0 race merged", 13: "propose s0 end", 14: "propose s>=1 logits", 15: "propose s>=1 merged1",
-         16: "propose s>=1 merged2", 17: "propose s>=1 end", 18: "propose loop done", 19: "propose end",
+         8: "propose entry", 9: "propose row staged", 10: "propose pass 1 starts", 11: "propose pass 1 in LDS (barrier)",
+         20: "propose s0 residue race", 12: "propose s0 letter race", 13: "propose s0 move applied",
+         14: "propose s>=1 part (a): residue re-evaluated, S1", 15: "propose s>=1 residue race", 16: "propose s>=1 letter race",
+         17: "propose s>=1 move applied", 18: "propose records written, closing barrier", 19: "propose end",
          24: "accept entry", 25: "accept row staged", 26: "accept loop done", 27: "accept decision", 28: "accept count done",
          29: "accept end", 30: "accept row loads issued", 31: "accept prefetch issued", 32: "accept path staged",
          33: "accept row committed", 40: "cnn entry", 41: "cnn letters staged", 42: "cnn h1 built", 43: "cnn forward contraction + max",
@@ -46,7 +47,7 @@ for rep in range(20):
     out = np.zeros(128, dtype=np.uint64)
     _hip.check(lib.ppde_debug_read_stamps(ch.handle, out.ctypes.data))
     st = out.reshape(64, 2)
-    for grp in ((0, 1, 2, 3, 4, 5), (8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19), (24, 30, 31, 32, 33, 25, 26, 27, 28, 29), (40, 41, 42, 52, 53, 54, 55, 56, 43, 44, 60, 61, 62, 63, 45, 46, 47, 48, 49), (50, 51, 52, 53, 54, 55, 56, 57, 58, 59)):
+    for grp in ((0, 1, 2, 3, 4, 5), (8, 9, 10, 11, 20, 12, 13, 14, 15, 16, 17, 18, 19), (24, 30, 31, 32, 33, 25, 26, 27, 28, 29), (40, 41, 42, 52, 53, 54, 55, 56, 43, 44, 60, 61, 62, 63, 45, 46, 47, 48, 49), (50, 51, 52, 53, 54, 55, 56, 57, 58, 59)):
         prev = None
         for k in grp:
             if st[k, 0] == 0:
@@ -77,4 +78,4 @@ for (a, b), v in acc.items():
     if a == "total":
         print(f"TOTAL group {b}: {cyc:.0f} cycles = {rt / 100:.2f} us  (clock {cyc / max(rt, 1) * 100:.0f} MHz)")
     else:
-        print(f"  {NAMES.get(a, NAMES.get(a - 10, '?') + ' (last wg)'):34s} -> {NAMES.get(b, NAMES.get(b - 10, '?') + ' (last wg)'):34s}: {cyc:7.0f} cycles  {rt / 100:6.2f} us")
+        print(f"  {NAMES.get(a, NAMES.get(a - 10, '?') + ' (last wg)'):48s} -> {NAMES.get(b, NAMES.get(b - 10, '?') + ' (last wg)'):48s}: {cyc:7.0f} cycles  {rt / 100:6.2f} us")
