@@ -60,7 +60,13 @@ typedef enum {
     PPDE_ERR_INVALID = -1,     /* bad argument / shape / state */
     PPDE_ERR_HIP = -2,         /* a HIP runtime call failed */
     PPDE_ERR_NOT_ONEHOT = -3,  /* an input row is not a one-hot vector */
-    PPDE_ERR_NUMERIC = -4      /* a proposal row had no finite logit (the reference raises ValueError there) */
+    PPDE_ERR_NUMERIC = -4      /* a proposal row had no usable mass: every move masked out or forbidden (the reference raises
+                                * ValueError there), a non-finite gradient, or -- device RNG only, whose rows take exp(z - mref)
+                                * against a fixed reference mref = min(beta * spread / 2, 64) of the launch -- every admissible
+                                * logit 86.6 or more below mref (the normaliser falls below 2^-125: a chain at the mutation cap or
+                                * a state outside the library whose best admissible move lies ~23 or more below the current
+                                * letters once the gradient's spread reaches 128) or a logit more than 88.7 above it (a spread
+                                * beyond 2 * (64 + 88)); the reference, which reduces a maximum per row, carries on there */
 } ppde_status;
 
 typedef struct ppde_model ppde_model;
@@ -341,7 +347,7 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev);
 int ppde_chains_run(ppde_chains* c, int steps, const int32_t* U_dev, const float* q_dev,
                     const float* u_dev, const int32_t* max_u);
 
-/* Block until enqueued work is done; reports PPDE_ERR_NUMERIC if a proposal row degenerated. */
+/* Block until enqueued work is done; reports PPDE_ERR_NUMERIC if a proposal row degenerated (see the code's comment above). */
 int ppde_chains_sync(ppde_chains* c);
 
 int ppde_chains_steps_done(ppde_chains* c);

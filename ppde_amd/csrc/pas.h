@@ -123,6 +123,11 @@ struct RowLds {
     float* qv;      // reciprocal race variates of PAS_QS sub-steps [PAS_QS][LQ]     (two-level draw, device RNG)
     uint32_t* Al;   // design library words [L]: only the *_lib kernels are launched with room for them (pas_lib_lds_bytes)
 };
+// Smallest normaliser S1 = sum exp(z - mref) the device-RNG rows divide by: at or above 2^-125 S1 is a normal number and 1 / S1 is
+// finite. Below it -- every admissible logit more than 86.6 below the fixed reference: a capped or library-restricted row under a
+// reference of 64 -- S1 is denormal and 1 / S1 = inf would turn every admissible entry into 1 - 2^-23 (logits 88.7 to 104 below),
+// or S1 is 0 (beyond 104). Such a row is flagged PPDE_ERR_NUMERIC like a non-finite one (include/ppde_hip.h).
+#define PAS_S1_MIN 2.350988701644575e-38f   // 2^-125
 // sub-steps of race variates parked in LDS at a time (two-level draw); row = 4*ceil(L/4) residue entries + 20 letter entries
 #define PAS_QS 4
 __host__ __device__ inline int pas_rb(int L) { return (L + 3) >> 2; }
@@ -482,6 +487,7 @@ __device__ __forceinline__ void row_max_sumexp_batch(const RowLds& lds, const fl
 struct RevPath {
     int dist;        // mutation count of the state the next reverse row belongs to (x_{s+1} once sub-step s is consumed)
     bool forbid;     // some reverse move of the path has probability exactly 0
+    float s1max;     // device RNG, default mode: inf once a reverse row of the path had a non-finite sum (overflow, NaN): accept_body flags it
 };
 // Reversible mode: the path's entries in lds.mv become  flat move | old letter << 16 | (change of the mutation count + 1) << 24.
 // old_s is x's letter at l_s unless an earlier move of the same path wrote that residue; one thread per sub-step scans back.
@@ -651,8 +657,10 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
     }
     float4 e[NR][GPT];
     float sw[NR];
+    bool adm[NR];                                    // REV: some lane of this wave holds an admissible entry (logit > -inf) of row j
     auto row_exp = [&](int j) {
         float sm = 0.f;
+        bool ad = false;
 #pragma unroll
         for (int r = 0; r < GPT; ++r) {
             e[j][r] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -660,6 +668,7 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
             if constexpr (REV) {
                 const float4 z = forward_logits<LIB, TEMP>(a, G, R.gv[r], R.l[r], R.kb[r], R.cur[r], R.wt[r], rc[j], ok4[r], beta);
                 e[j][r].x = expf(z.x - mref); e[j][r].y = expf(z.y - mref); e[j][r].z = expf(z.z - mref); e[j][r].w = expf(z.w - mref);
+                ad |= (z.x > -INFINITY) | (z.y > -INFINITY) | (z.z > -INFINITY) | (z.w > -INFINITY);
             } else {
                 const float gc = G[R.l[r] * 20 + R.cur[r]];
                 const float4 gv = R.gv[r];
@@ -669,6 +678,7 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
             sm += e[j][r].x; sm += e[j][r].y; sm += e[j][r].z; sm += e[j][r].w;
         }
         sw[j] = wave_sum(sm);
+        adm[j] = REV ? (bool)__any(ad) : true;
     };
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
@@ -681,13 +691,17 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
         if (fresh) row_exp(j);
         else {                                                   // (no lane's letters differ from the row before: its bits)
             sw[j] = sw[j > 0 ? j - 1 : 0];
+            adm[j] = adm[j > 0 ? j - 1 : 0];
 #pragma unroll
             for (int r = 0; r < GPT; ++r) e[j][r] = e[j > 0 ? j - 1 : 0][r];
         }
     }
     if (lane == 0) {
 #pragma unroll
-        for (int j = 0; j < NR; ++j) lds.xa[wave * PAS_SB + j] = sw[j];
+        for (int j = 0; j < NR; ++j) {
+            lds.xa[wave * PAS_SB + j] = sw[j];
+            if constexpr (REV) lds.xa[PPDE_NW * PAS_SB + wave * PAS_SB + j] = adm[j] ? 1.f : 0.f;   // (exchange A holds 8 NW floats)
+        }
     }
     __syncthreads();
     float inv[NR], s3w[NR];
@@ -695,10 +709,20 @@ __device__ __forceinline__ void reverse_rows_dev(const PasArgs& a, const RowLds&
     for (int j = 0; j < NR; ++j) {
         float S1 = row8_sum(lane < PPDE_NW ? lds.xa[(lane & (PPDE_NW - 1)) * PAS_SB + j] : 0.f);
         if constexpr (REV) {
-            // no admissible entry: nothing leads back. Also reached, silently, when every admissible entry of a capped or
-            // library-restricted row underflows against the fixed reference (mref spans ALL residues, up to 64, and is kept by
-            // design): such a path is rejected, where the forward path would flag PPDE_ERR_NUMERIC
-            if (!(S1 > 0.f && S1 < INFINITY)) { rp.forbid = true; S1 = 1.f; }
+            // No admissible entry at all: nothing leads back, the path is rejected (the reference agrees). A row that HAS admissible
+            // entries but no usable sum against the fixed reference (mref spans ALL residues of g_y, up to 64, and is kept by
+            // design) -- every one of them 86.6 or more below it: S1 below 2^-125, denormal with 1 / S1 = inf from 88.7, exactly 0
+            // from 104 -- or a non-finite sum is rejected AND flagged PPDE_ERR_NUMERIC, as the forward path flags it
+            if (!(S1 >= PAS_S1_MIN && S1 < INFINITY)) {
+                const float any = row8_max(lane < PPDE_NW ? lds.xa[PPDE_NW * PAS_SB + (lane & (PPDE_NW - 1)) * PAS_SB + j] : 0.f);
+                if ((any > 0.f || S1 != 0.f) && tid == 0) flag_error(a.err_flag, 1);
+                rp.forbid = true; S1 = 1.f;
+            }
+        } else {
+            // no masks on the way back, so a current letter's logit 0 always keeps S1 >= exp(-64); a logit more than 88.7 above the
+            // reference (the spread of g_y beyond 2 (64 + 88)) makes it inf: inv = 0 would put every entry on the clamp's floor
+            // (gathered with one select per row and flagged once, behind the accept decision: a branch per row showed in the fused launch)
+            rp.s1max = (S1 < INFINITY) ? rp.s1max : INFINITY;        // (a select, not fmaxf: a NaN sum counts too)
         }
         inv[j] = 1.0f / S1;
         float s3 = 0.f;
@@ -1138,7 +1162,7 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
             }
             PPDE_STAMP(a.dbg, 14, stamp && s > 0);
             float S1c = S1;
-            if (!(S1c > 0.f && S1c < INFINITY)) {     // no admissible move (or a non-finite gradient): the reference raises here
+            if (!(S1c >= PAS_S1_MIN && S1c < INFINITY)) {   // no admissible move with mass against mref (or a non-finite gradient)
                 if (lane == 0) flag_error(a.err_flag, 1);
                 S1c = 1.f;
             }
@@ -1407,7 +1431,7 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
     PPDE_STAMP(a.dbg, 25, stamp);
     float log_ratio = 0.f;
     RevPath rp;
-    rp.dist = d_cur; rp.forbid = false;
+    rp.dist = d_cur; rp.forbid = false; rp.s1max = 0.f;
     if constexpr (REV) rev_annotate_path(lds, Ub);
     // The reverse rows of a path are independent of each other (gradient at y, states along the recorded path), so
     // up to PAS_SB of them are evaluated per pass: two barriers per pass instead of two per sub-step.
@@ -1473,6 +1497,7 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
         rc->acc_last = acc ? 1 : 0;
         rc->dist_cur = reset ? 0 : dist;
         if (a.tr_acc) { a.tr_acc[(size_t)it * a.n + b] = acc ? 1 : 0; a.tr_logacc[(size_t)it * a.n + b] = log_acc; }
+        if constexpr (DEV && !REV) { if (!(rp.s1max < INFINITY)) flag_error(a.err_flag, 1); }   // a reverse row overflowed against mref
         if (a.reuse) {                               // energy / fitness of the state the chain continues from
             if (reset) { rc->cur_e = a.wt_e; rc->cur_f = a.wt_f; }
             else if (acc) { rc->cur_e = e_y; rc->cur_f = f_y; }

@@ -1840,7 +1840,7 @@ int ppde_chains_sync(ppde_chains* c) {
     HIPCHK(q);
     const int err = *(volatile int*)c->h_err;
     if (err & 2) return fail(PPDE_ERR_INVALID, "a supplied path length U exceeds the max_u of its iteration (the noise block holds only max_u sub-steps)");
-    if (err) return fail(PPDE_ERR_NUMERIC, "a proposal row had no finite logit (every move masked out): the categorical is undefined");
+    if (err) return fail(PPDE_ERR_NUMERIC, "a proposal row had no usable mass (every move masked out, or every admissible logit 86.6 or more below / one 88.7 above the softmax reference): the categorical is undefined");
     return PPDE_OK;
 }
 
