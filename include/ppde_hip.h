@@ -335,6 +335,43 @@ int ppde_chains_pair_counts_shape(ppde_chains* c, int32_t* n_sites, int32_t* sit
 /* The counts over ALL rows recorded so far, full and symmetric. Synchronises. PPDE_ERR_INVALID without pair counts or before init. */
 int ppde_chains_pair_counts_read(ppde_chains* c, uint64_t* pair_counts /* [S][20][S][20] */);
 
+/* Archive (off by default): each chain's K best DISTINCT sequences, each with its own energy, kept on the device in n K L bytes
+ * whatever the run length, by one more kernel (ppde_amd/csrc/archive.h) behind the accept phase -- behind the swap, with tempering,
+ * and behind the recorder's kernels -- of every iteration of an archiving run: no host round trip, valid under graph replay and
+ * eager issue alike. A run without an archive enqueues nothing new and makes no additional runtime call.
+ *   candidate: chain b after t completed iterations offers what ppde_chains_peek would return: the letters of its current state
+ *     with row t of the two histories (untempered, as everywhere). ppde_chains_init offers t = 0, every iteration `it` of every
+ *     ppde_chains_run offers t = it + 1.
+ *   skipped, decided before anything else: a chain whose mutation count is 0 (what peek returns as dist): the wild type is never
+ *     archived; and an energy that is not finite. In the default mode a mutation-cap reset leaves the wild type in the current
+ *     state while row t still holds the energy of the state that was reset away: that pair is skipped, never mislabelled, and the
+ *     state that triggered the reset is not archived either -- the archive holds only states the chain continued from. In the
+ *     default mode with a cap every entry therefore has 1 <= dist < nmut_threshold, and best_idx (ppde_chains_collect) may hold
+ *     a state AT the cap that the archive lacks.
+ *   online rule, in this order: 1. an archived entry of this chain has the same L letters: nothing happens, the entry keeps its
+ *     first energy and step; 2. else count < K: inserted with step = t; 3. else m = the entry of lowest energy, among entries of
+ *     equal energy the one with the latest step: replaced when e > energy[m] (strict, like the running best), else nothing.
+ *     An entry that was evicted and is visited again re-enters under rule 2 / 3 with its later step.
+ * The archive changes no other result: histories, best states, traces, recorder rows and Philox streams are those of the run
+ * without it. It holds in the default, library, reversible and tempering modes (the chains of every rung are archived), for every
+ * `which`, both gradient policies and both rng_modes. It is independent of the recorder and the pair counts.
+ * Valid between ppde_chains_create and ppde_chains_init (the graphs hold the pointers); NULL clears it. PPDE_ERR_INVALID with a
+ * message, the object unchanged: after init; k outside 1..32; paper_results (after a rejection its history row holds the energy of
+ * the state that was left while the chain continues from its initial state: a mismatched pair with no flag to see it by);
+ * n_streams > 1. The chains own the buffers; a failed allocation is PPDE_ERR_HIP and leaves nothing half-set. ppde_chains_init
+ * empties the archive (a second init too). */
+typedef struct {
+    int32_t k;   /* entries per chain, 1..32 */
+} ppde_archive_config;
+int ppde_chains_set_archive(ppde_chains* c, const ppde_archive_config* cfg /* NULL clears */);
+/* Entries per chain. The pointer may be NULL. PPDE_ERR_INVALID without an archive. */
+int ppde_chains_archive_shape(ppde_chains* c, int32_t* k);
+/* Every chain's entries sorted by (energy descending, step ascending; steps are unique within a chain); slots beyond count[b] hold
+ * idx 255, energy -inf, fitness 0, step -1. Synchronises; any pointer may be NULL. PPDE_ERR_INVALID without an archive or before
+ * init. */
+int ppde_chains_archive_read(ppde_chains* c, uint8_t* idx /* [n][K][L] */, float* energy, float* fitness /* [n][K] */,
+                             int32_t* step /* [n][K] */, int32_t* count /* [n] */);
+
 /* Start from idx0_dev [n, L] (ppde.py:35-47): evaluates the initial energies, fills history row 0. */
 int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev);
 

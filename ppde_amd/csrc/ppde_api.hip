@@ -18,6 +18,7 @@
 #include "pas.h"
 #include "record.h"
 #include "pairs.h"
+#include "archive.h"
 
 static thread_local std::string g_err;
 
@@ -1216,6 +1217,12 @@ struct ppde_chains {
     int pair_nt = 0;                             // tiles per side (pairs.h)
     int* pair_sites_dev = nullptr;               // [pair_nt * PAIR_TS], padded with -1
     unsigned long long* pair_counts = nullptr;   // [pair_nt (pair_nt + 1) / 2][PAIR_TILE]
+    // archive (ppde_chains_set_archive): owned here, allocated there; arch_k 0 = none
+    int arch_k = 0;
+    uint8_t* arch_idx = nullptr;                 // [n][K][Ls]
+    float *arch_e = nullptr, *arch_f = nullptr;  // [n][K]
+    int *arch_step = nullptr, *arch_count = nullptr;   // [n][K], [n]
+    unsigned int* arch_hash = nullptr;           // [n][K] fingerprints (archive.h)
 };
 
 static void free_recorder(ppde_chains* c) {
@@ -1232,6 +1239,16 @@ static void free_pairs(ppde_chains* c) {
     if (c->pair_counts) hipFree(c->pair_counts);
     c->pair_sites_dev = nullptr; c->pair_counts = nullptr;
     c->pair_on = false; c->pair_sites.clear(); c->pair_nt = 0;
+}
+static void free_archive(ppde_chains* c) {
+    if (c->arch_idx) hipFree(c->arch_idx);
+    if (c->arch_e) hipFree(c->arch_e);
+    if (c->arch_f) hipFree(c->arch_f);
+    if (c->arch_step) hipFree(c->arch_step);
+    if (c->arch_count) hipFree(c->arch_count);
+    if (c->arch_hash) hipFree(c->arch_hash);
+    c->arch_idx = nullptr; c->arch_e = c->arch_f = nullptr; c->arch_step = c->arch_count = nullptr; c->arch_hash = nullptr;
+    c->arch_k = 0;
 }
 static size_t pair_tiles(const ppde_chains* c) { return (size_t)c->pair_nt * ((size_t)c->pair_nt + 1) / 2; }
 static int recorder_rows_done(const ppde_chains* c) {
@@ -1275,6 +1292,20 @@ static PasArgs chain_args(const ppde_chains* c) {
     a.beta = c->beta; a.rung = c->rung; a.slot = c->slot; a.swap_attempts = c->swap_attempts; a.swap_accepts = c->swap_accepts;
     a.rung_hist = c->rung_hist; a.n_rungs = c->n_rungs; a.swap_every = c->swap_every;
     return a;
+}
+
+// the archive's kernel for the state after it_base + it_local + 1 completed iterations (archive.h): every chain of the object
+static int launch_archive(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
+    const Geom& g = c->m->g;
+    ArchArgs r{};
+    r.it_base = it_base; r.it_local = it_local;
+    r.n = c->n; r.K = c->arch_k; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
+    r.rec = c->rec; r.rec_stride = c->rec_stride; r.cur = c->cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist;
+    r.idx = c->arch_idx; r.energy = c->arch_e; r.fitness = c->arch_f; r.step = c->arch_step; r.count = c->arch_count;
+    r.hash = c->arch_hash;
+    hipLaunchKernelGGL(k_archive, dim3((c->n + ARCH_BLOCK / 64 - 1) / (ARCH_BLOCK / 64)), dim3(ARCH_BLOCK), 0, s, r);
+    HIPCHK(hipGetLastError());
+    return PPDE_OK;
 }
 
 static States cur_states(const ppde_chains* c) { return States{c->cur, c->curT, c->n_pad}; }
@@ -1420,6 +1451,10 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
                 hipLaunchKernelGGL(k_record_pairs, dim3((unsigned)pair_tiles(c)), dim3(PAIR_BLOCK), 0, s, p);
                 HIPCHK(hipGetLastError());
             }
+        }
+        if (c->arch_k) {                             // (one stream: every chain of the object; reads cur, the history rows, dist_cur)
+            rc = launch_archive(c, it_base, a.it_local, s);
+            if (rc) return rc;
         }
     }
     return PPDE_OK;
@@ -1588,6 +1623,7 @@ int ppde_chains_destroy(ppde_chains* c) {
     free_tempering(c);
     free_recorder(c);
     free_pairs(c);
+    free_archive(c);
     delete c->tfw;
     if (c->h_err) hipHostFree(c->h_err);
     for (hipStream_t st : c->streams) if (st) hipStreamDestroy(st);
@@ -1766,6 +1802,12 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
     }
     if (c->rec_on) HIPCHK(hipMemset(c->rec_counts, 0, (size_t)g.L * PPDE_A * sizeof(unsigned long long)));   // (a fresh start counts from zero)
     if (c->pair_on) HIPCHK(hipMemset(c->pair_counts, 0, pair_tiles(c) * PAIR_TILE * sizeof(unsigned long long)));
+    if (c->arch_k) {                                // (a fresh start: an empty archive, then the initial population as t = 0)
+        HIPCHK(hipMemsetAsync(c->arch_count, 0, (size_t)n * sizeof(int), s));
+        rc = launch_archive(c, nullptr, -1, s);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(s));
+    }
     c->steps_done = 0;
     c->initialised = true;
     rc = capture_segments(c);                       // (replayed by every later run; never captured inside one)
@@ -2007,6 +2049,106 @@ int ppde_chains_recorder_read(ppde_chains* c, int first_row, int n_rows, uint8_t
     if (fitness && cells) HIPCHK(hipMemcpy(fitness, c->rec_f + o, cells * sizeof(float), hipMemcpyDeviceToHost));
     if (chain && cells) HIPCHK(hipMemcpy(chain, c->rec_chain + o, cells * sizeof(int), hipMemcpyDeviceToHost));
     if (site_counts) HIPCHK(hipMemcpy(site_counts, c->rec_counts, (size_t)g.L * PPDE_A * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return PPDE_OK;
+}
+
+int ppde_chains_set_archive(ppde_chains* c, const ppde_archive_config* cfg) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_archive: the archive must be set before ppde_chains_init (its graphs hold the pointers)");
+    if (!cfg) {                                     // clear
+        HIPCHK(hipSetDevice(c->device));
+        free_archive(c);
+        return PPDE_OK;
+    }
+    ARGCHK(cfg->k >= 1 && cfg->k <= ARCH_KMAX, "ppde_chains_set_archive: k must be in 1..32");
+    ARGCHK(!c->cfg.paper_results, "ppde_chains_set_archive: paper_results is not supported (after a rejection its history row holds the "
+                                  "energy of the state that was left while the chain continues from its initial state: a mismatched pair)");
+    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_archive: n_streams > 1 is not supported (one launch archives "
+                                                            "every chain of the object)");
+    HIPCHK(hipSetDevice(c->device));
+    // allocate everything first: a failure leaves the object as it was
+    const Geom& g = c->m->g;
+    const size_t n = c->n, cells = n * (size_t)cfg->k;
+    ppde_chains t;                                   // (a holder for free_archive on the error path)
+    hipError_t e = dalloc(&t.arch_idx, cells * (size_t)g.Ls);
+    if (e == hipSuccess) e = hipMemset(t.arch_idx, 0, cells * (size_t)g.Ls);
+    if (e == hipSuccess) e = dalloc(&t.arch_e, cells);
+    if (e == hipSuccess) e = dalloc(&t.arch_f, cells);
+    if (e == hipSuccess) e = dalloc(&t.arch_step, cells);
+    if (e == hipSuccess) e = dalloc(&t.arch_hash, cells);
+    if (e == hipSuccess) e = dalloc(&t.arch_count, n);
+    if (e == hipSuccess) e = hipMemset(t.arch_count, 0, n * sizeof(int));
+    if (e != hipSuccess) {
+        free_archive(&t);
+        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_archive: device allocation: ") + hipGetErrorString(e));
+    }
+    free_archive(c);
+    c->arch_idx = t.arch_idx; c->arch_e = t.arch_e; c->arch_f = t.arch_f; c->arch_step = t.arch_step; c->arch_count = t.arch_count;
+    c->arch_hash = t.arch_hash;
+    t.arch_idx = nullptr; t.arch_e = t.arch_f = nullptr; t.arch_step = t.arch_count = nullptr; t.arch_hash = nullptr;
+    c->arch_k = cfg->k;
+    return PPDE_OK;
+}
+
+int ppde_chains_archive_shape(ppde_chains* c, int32_t* k) {
+    ARGCHK(c, "null argument");
+    ARGCHK(c->arch_k, "ppde_chains_archive_shape: no archive was set (ppde_chains_set_archive)");
+    if (k) *k = c->arch_k;
+    return PPDE_OK;
+}
+
+int ppde_chains_archive_read(ppde_chains* c, uint8_t* idx, float* energy, float* fitness, int32_t* step, int32_t* count) {
+    ARGCHK(c && c->arch_k, "ppde_chains_archive_read: no archive was set (ppde_chains_set_archive)");
+    ARGCHK(c->initialised, "chains not initialised");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    const Geom& g = c->m->g;
+    const size_t n = c->n, K = c->arch_k, cells = n * K, L = g.L;
+    std::vector<float> he(cells), hf(cells);
+    std::vector<int> hs(cells), hc(n);
+    HIPCHK(hipMemcpy(he.data(), c->arch_e, cells * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hf.data(), c->arch_f, cells * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hs.data(), c->arch_step, cells * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hc.data(), c->arch_count, n * sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<uint8_t> hi;
+    if (idx) {
+        // unpack [n][K][Ls] -> [n][K][L] through a device buffer, a block of chains at a time (32-bit thread indices)
+        hi.resize(cells * L);
+        const size_t per_chain = K * (size_t)std::max(g.L, g.Ls);
+        const size_t block = std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / per_chain));
+        DevTmp tmp;
+        HIPCHK(tmp.alloc<uint8_t>(block * K * L));
+        for (size_t b = 0; b < n; b += block) {
+            const int rows_n = (int)(std::min(block, n - b) * K);
+            hipLaunchKernelGGL(k_unpack_state, dim3((rows_n * g.L + 255) / 256), dim3(256), 0, c->stream,
+                               c->arch_idx + b * K * g.Ls, tmp.as<uint8_t>(), rows_n, g.L, g.Ls, g.sh);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipStreamSynchronize(c->stream));
+            HIPCHK(hipMemcpy(hi.data() + b * K * L, tmp.p, (size_t)rows_n * L, hipMemcpyDeviceToHost));
+        }
+    }
+    // each chain's entries by (energy descending, step ascending); the slots beyond count filled
+    std::vector<int> order(K);
+    for (size_t b = 0; b < n; ++b) {
+        const int cnt = std::max(0, std::min(hc[b], (int)K));
+        const size_t o = b * K;
+        for (int j = 0; j < cnt; ++j) order[j] = j;
+        std::sort(order.begin(), order.begin() + cnt, [&](int x, int y) {
+            return he[o + x] > he[o + y] || (he[o + x] == he[o + y] && hs[o + x] < hs[o + y]);
+        });
+        for (size_t j = 0; j < K; ++j) {
+            const bool live = (int)j < cnt;
+            const size_t src = o + (live ? order[j] : 0);
+            if (energy) energy[o + j] = live ? he[src] : -INFINITY;
+            if (fitness) fitness[o + j] = live ? hf[src] : 0.f;
+            if (step) step[o + j] = live ? hs[src] : -1;
+            if (idx) {
+                if (live) memcpy(idx + (o + j) * L, hi.data() + src * L, L);
+                else memset(idx + (o + j) * L, 255, L);
+            }
+        }
+        if (count) count[b] = cnt;
+    }
     return PPDE_OK;
 }
 

@@ -51,6 +51,14 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         (without one: min_pos..max_pos); a site list in library.parse_sites syntax ('8-20,33') or a strictly
                         increasing sequence of 0-based residues. After run(), `sampler.samples` also holds pair_counts uint64
                         [S, 20, S, 20] and pair_sites int32 [S] (both None when off); a sharded run sums the counts.
+    ppde_archive        None or 0 (default): off. K in 1..32: every chain keeps, on the device, the K best distinct sequences it
+                        visited, each with its own energy (include/ppde_hip.h, ppde_chains_set_archive): n K L bytes whatever the
+                        run length, no host round trip, nothing else of the run changes. The wild type is never archived. After
+                        run(), `sampler.archive` holds idx uint8 [n, K, L] (255 beyond count), energy / fitness [n, K], step
+                        [n, K], count [n], chain [n] (GLOBAL chain index) and `candidates`, the population's distinct sequences
+                        merged from them (ppde_amd/archive.py: idx, energy, fitness, chain, step, n_chains; best first). A sharded
+                        run gathers the per-chain archives in global chain order and merges on every rank. Not with
+                        paper_results, not with ppde_streams > 1.
     ppde_shard          False (default). True with torch.distributed initialised: chains are split over ranks
                         and gathered at the end (one RCCL all_gather); every rank returns the full result.
 """
@@ -61,7 +69,7 @@ import time
 import numpy as np
 import torch
 
-from . import _hip, library as design_library
+from . import _hip, archive as chain_archive, library as design_library
 from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
@@ -125,6 +133,24 @@ def pair_sites_of(spec, L, min_pos, max_pos, lib_words=None):
     if spec[-1] >= L:
         raise ValueError(f"ppde_sample_pairs: residue {spec[-1]} lies outside the sequence 0..{L - 1}")
     return np.asarray(spec, np.int32)
+
+
+def check_archive(k, paper_results=False, n_streams=1):
+    """ppde_archive as 0 (off: None or 0) or K in 1..32; ValueError otherwise, and for what an archive cannot be combined with."""
+    if k is None or (not isinstance(k, bool) and k == 0):
+        return 0
+    try:
+        whole = not isinstance(k, bool) and float(k) == int(k) and 1 <= int(k) <= 32
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise ValueError(f"ppde_archive: K must be a whole number in 1..32 (None or 0: off), got {k!r}")
+    if paper_results:
+        raise ValueError("ppde_archive: paper_results is not supported (after a rejection its history row holds the energy of the "
+                         "state that was left while the chain continues from its initial state)")
+    if int(n_streams) > 1:
+        raise ValueError("ppde_archive: ppde_streams > 1 is not supported (one launch archives every chain)")
+    return int(k)
 
 
 def check_ladder(betas):
@@ -278,6 +304,29 @@ class Chains:
             _hip.check(self.lib.ppde_chains_pair_counts_read(self.handle, _hip.ptr(counts)))
         return counts, sites
 
+    def set_archive(self, k):
+        """Archive (include/ppde_hip.h, ppde_chains_set_archive): every chain keeps the k best distinct non-wild-type states it
+        visited, 1 <= k <= 32. None clears it. Only before init()."""
+        with torch.cuda.device(self.model.device):
+            if k is None:
+                _hip.check(self.lib.ppde_chains_set_archive(self.handle, None))
+                return
+            cfg = _hip.ArchiveConfig(k=int(k))
+            _hip.check(self.lib.ppde_chains_set_archive(self.handle, C.byref(cfg)))
+
+    def archive(self):
+        """What the archive holds: idx uint8 [n, K, L], energy / fitness fp32 [n, K], step int32 [n, K], count int32 [n]; every
+        chain's entries by (energy descending, step ascending), the slots beyond count filled with 255, -inf, 0, -1."""
+        K = C.c_int32()
+        _hip.check(self.lib.ppde_chains_archive_shape(self.handle, C.byref(K)))
+        n, k, L = self.n, K.value, self.model.L
+        out = dict(idx=np.empty((n, k, L), np.uint8), energy=np.empty((n, k), np.float32), fitness=np.empty((n, k), np.float32),
+                   step=np.empty((n, k), np.int32), count=np.empty(n, np.int32))
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_archive_read(self.handle, *[_hip.ptr(out[k_]) for k_ in (
+                "idx", "energy", "fitness", "step", "count")]))
+        return out
+
     def init(self, idx0):
         idx0 = idx0.to(self.model.device, torch.uint8).contiguous()
         if tuple(idx0.shape) != (self.n, self.model.L):
@@ -430,6 +479,8 @@ class PPDE_PAS(BaseSampler):
                 self.sample_rung = 0 if self.sample_rung is None else int(self.sample_rung)
                 if not 0 <= self.sample_rung < self.betas.size:
                     raise ValueError(f"ppde_sample_rung must be a rung of the ladder, 0..{self.betas.size - 1}")
+        self.archive_k = check_archive(getattr(args, "ppde_archive", None), self.paper_results, self.n_streams)
+        self.archive = None
         self.noise_bytes = getattr(args, "ppde_noise_bytes", 96 << 20)   # host->device noise is uploaded in chunks of about this size
         self.last_chains = None
         self.timings = {}       # seconds of the last run(): setup (chains + hipGraph capture), iterations, log path, collect
@@ -509,6 +560,8 @@ class PPDE_PAS(BaseSampler):
             chains.set_recorder(self.sample_every, self.sample_burn_in, self.sample_rung, not self.sample_counts_only)
         if pair_on:
             chains.set_pair_counts(pair_sites)
+        if self.archive_k:
+            chains.set_archive(self.archive_k)
         chains.init(idx0[lo:hi])
 
         def gathered(a):
@@ -615,6 +668,12 @@ class PPDE_PAS(BaseSampler):
                 self.samples.update(idx=slots_gathered(rec["idx"]), energy=slots_gathered(rec["energy"]),
                                     fitness=slots_gathered(rec["fitness"]),
                                     chain=slots_gathered(rec["chain"].astype(np.int64) + lo))
+        self.archive = None
+        if self.archive_k:
+            arc = {k: gathered(v) for k, v in chains.archive().items()}      # (global chain order)
+            arc["chain"] = np.arange(n_global, dtype=np.int64)
+            arc["candidates"] = chain_archive.merge(arc["idx"], arc["energy"], arc["fitness"], arc["step"], arc["count"])
+            self.archive = arc
         if n_global == 1:
             # the reference's single-chain shapes (ppde.py:178-183; the ensemble's `.squeeze()`, nets.py:442, makes one chain's
             # fitness a scalar): fitness_history (T+1,) next to energy_history (T+1, 1); with ProteinSupervised the energy IS

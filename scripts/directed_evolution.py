@@ -146,6 +146,15 @@ def main(args):
                 np.save(results_path / "sample_energy.npy", samples["energy"])
                 np.save(results_path / "sample_fitness.npy", samples["fitness"])
                 np.save(results_path / "sample_chain.npy", samples["chain"])
+        archive = getattr(sampler, "archive", None)
+        if archive is not None:
+            np.save(results_path / "archive.npy", archive["idx"])
+            for name in ("energy", "fitness", "step", "count"):
+                np.save(results_path / f"archive_{name}.npy", archive[name])
+            cand = archive["candidates"]
+            np.save(results_path / "candidates.npy", cand["idx"])
+            for name, key in (("energy", "energy"), ("fitness", "fitness"), ("chain", "chain"), ("step", "step"), ("nchains", "n_chains")):
+                np.save(results_path / f"candidates_{name}.npy", cand[key])
 
     if not args.disable_MSA_transformer_scoring:
         print("MSA-Transformer scoring is not part of this build (needs the ESM-MSA-1b weights); skipped")
@@ -241,6 +250,12 @@ def build_parser():
                          "pair_sites.npy int32 [S]. SPEC is 'all' (every residue), 'open' (the open residues of the design "
                          "library; without one the window the sampler moves in) or a site list in --ppde_sites syntax. The file "
                          "holds (20 S)^2 * 8 bytes: 29 MB at 96 sites. Kept with --ppde_sample_counts_only too")
+    pp.add_argument("--ppde_archive", metavar="K", type=int, default=0,
+                    help="keep, on the device, each chain's K best distinct sequences with their energies (1..32; 0: off): "
+                         "archive.npy uint8 [n, K, L] with archive_energy / _fitness / _step [n, K] and archive_count [n], and the "
+                         "population's distinct candidates merged from them: candidates.npy uint8 [M, L] with candidates_energy, "
+                         "_fitness, _chain, _step and _nchains [M], best first. Works with either --ppde_rng; not with "
+                         "--paper_results")
     return parser
 
 
