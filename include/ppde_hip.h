@@ -372,6 +372,46 @@ int ppde_chains_archive_shape(ppde_chains* c, int32_t* k);
 int ppde_chains_archive_read(ppde_chains* c, uint8_t* idx /* [n][K][L] */, float* energy, float* fitness /* [n][K] */,
                              int32_t* step /* [n][K] */, int32_t* count /* [n] */);
 
+/* Move statistics (off by default): how often the chains accept, how far an accepted path carries them, how acceptance falls with
+ * the path length, which residues ever change -- counted on the device by one more small kernel (ppde_amd/csrc/stats.h) behind the
+ * accept phase of every iteration of such a run, last behind the swap, the recorder's kernels and the archive's: no host round trip,
+ * valid under graph replay and eager issue alike. A run without statistics enqueues nothing new and makes no additional runtime call.
+ *   notation: n chains, R' = max(n_rungs, 1), M = mu_max = 2 pas_length - 1; for iteration `it` (0-based), t = it + 1.
+ *   x_t[b], d_t[b]: the letters and `dist` ppde_chains_peek returns for chain b after t completed iterations (after a mutation-cap
+ *     reset; under paper_results after the fall-back to the initial state). A_it[b]: the accept bit of iteration it, what peek's
+ *     `accepted` shows after it and what a trace run's accepted[it][b] holds (an explicit rejection of reversible mode is 0).
+ *     U_it[b]: the path length the iteration used, as a trace run's U[it][b], after the clamp min(max(U, 1), min(mu_max, max_u)).
+ *     r = r_it[b]: the rung chain b held while it ran iteration it = rung_history[it][b] (row it: before that iteration's swap);
+ *     0 without tempering. h = number of residues l with x_{t-1}[b][l] != x_t[b][l].
+ *   counters, all int64, zeroed by ppde_chains_init (a second init too), cumulative over every ppde_chains_run since; iteration it adds
+ *     iters        [n][R']  1                          accepts      [n][R']  A_it[b]
+ *     moved        [n][R']  h > 0                      jump_sum     [n][R']  h
+ *     dist_sum     [n][R']  d_t[b]                     wt_returns   [n][R']  d_{t-1}[b] > 0 && d_t[b] == 0
+ *     len_attempts [R'][M]  1 at [r][U_it[b] - 1]      len_accepts  [R'][M]  A_it[b] at [r][U_it[b] - 1]
+ *     site_changes [R'][L]  1 at [r][l] for every changed residue l of chain b (only with per_site = 1)
+ *   so sum_r iters[b][r] = steps_done; sum_b iters[.][r] = sum_u len_attempts[r][u] (accepts alike); sum_l site_changes[r][l] =
+ *   sum_b jump_sum[b][r]; and without paper_results moved <= accepts elementwise (an accepted path may undo itself: h may be 0, and
+ *   h <= U). Everything is an integer: the results do not depend on any summation order.
+ * The statistics change no other result: histories, best states, traces, recorder rows, pair counts, archive and Philox streams are
+ * those of the run without them. They hold in the default, library, reversible and tempering modes and with paper_results, for every
+ * `which`, both gradient policies and both rng_modes. They are independent of recorder, pair counts and archive.
+ * Valid between ppde_chains_create and ppde_chains_init (the graphs hold the pointers), and after ppde_chains_set_tempering when
+ * there is a ladder (R' is fixed at the set call); NULL clears them. PPDE_ERR_INVALID with a message, the object unchanged: after
+ * init; per_site not 0 or 1; n_streams > 1. While statistics are set, ppde_chains_set_tempering (to clear or to replace) is
+ * PPDE_ERR_INVALID. The chains own the buffers; a failed allocation is PPDE_ERR_HIP and leaves nothing half-set. */
+typedef struct {
+    int32_t per_site;   /* 1: keep site_changes; 0: not */
+} ppde_stats_config;
+int ppde_chains_set_stats(ppde_chains* c, const ppde_stats_config* cfg /* NULL clears */);
+/* R', M and per_site. Any pointer may be NULL. PPDE_ERR_INVALID without statistics. */
+int ppde_chains_stats_shape(ppde_chains* c, int32_t* n_rungs /* R' */, int32_t* n_lengths /* M */, int32_t* per_site);
+/* The counters so far. Synchronises; any pointer may be NULL. PPDE_ERR_INVALID without statistics, before init, or with
+ * site_changes when per_site = 0. */
+int ppde_chains_stats_read(ppde_chains* c, int64_t* iters, int64_t* accepts, int64_t* moved, int64_t* jump_sum,
+                           int64_t* dist_sum, int64_t* wt_returns,            /* [n][R'] each */
+                           int64_t* len_attempts, int64_t* len_accepts,        /* [R'][M] */
+                           int64_t* site_changes);                             /* [R'][L] */
+
 /* Start from idx0_dev [n, L] (ppde.py:35-47): evaluates the initial energies, fills history row 0. */
 int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev);
 

@@ -39,6 +39,11 @@ class ArchiveConfig(C.Structure):
     _fields_ = [("k", C.c_int32)]
 
 
+class StatsConfig(C.Structure):
+    """ppde_stats_config (include/ppde_hip.h)."""
+    _fields_ = [("per_site", C.c_int32)]
+
+
 class TfWeights(C.Structure):
     """ppde_tf_weights (include/ppde_hip.h): host pointers to ESM-2's fp32 parameters."""
     _PER_LAYER = ("q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "o_w", "o_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b",
@@ -85,6 +90,9 @@ SIGNATURES = {
     "ppde_chains_set_archive": (_i, [_p, C.POINTER(ArchiveConfig)]),
     "ppde_chains_archive_shape": (_i, [_p, C.POINTER(C.c_int32)]),
     "ppde_chains_archive_read": (_i, [_p, _p, _p, _p, _p, _p]),
+    "ppde_chains_set_stats": (_i, [_p, C.POINTER(StatsConfig)]),
+    "ppde_chains_stats_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ppde_chains_stats_read": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ppde_chains_init": (_i, [_p, _p]),
     "ppde_chains_run": (_i, [_p, _i, _p, _p, _p, _p]),
     "ppde_chains_sync": (_i, [_p]),

@@ -19,6 +19,7 @@
 #include "record.h"
 #include "pairs.h"
 #include "archive.h"
+#include "stats.h"
 
 static thread_local std::string g_err;
 
@@ -1223,6 +1224,12 @@ struct ppde_chains {
     float *arch_e = nullptr, *arch_f = nullptr;  // [n][K]
     int *arch_step = nullptr, *arch_count = nullptr;   // [n][K], [n]
     unsigned int* arch_hash = nullptr;           // [n][K] fingerprints (archive.h)
+    // move statistics (ppde_chains_set_stats): owned here, allocated there; stat_on false = none
+    bool stat_on = false;
+    int stat_per_site = 0, stat_R = 1;           // R' = max(n_rungs, 1) at the set call
+    long long* stat_cnt = nullptr;               // six [n][R'], two [R'][M], then [R'][L] with per_site (stat_counter)
+    uint8_t* stat_prev = nullptr;                // [2][n][Ls] the state the last counted iteration left, read and written in turns (stats.h)
+    int* stat_dist = nullptr;                    // [n]     its mutation count
 };
 
 static void free_recorder(ppde_chains* c) {
@@ -1249,6 +1256,29 @@ static void free_archive(ppde_chains* c) {
     if (c->arch_hash) hipFree(c->arch_hash);
     c->arch_idx = nullptr; c->arch_e = c->arch_f = nullptr; c->arch_step = c->arch_count = nullptr; c->arch_hash = nullptr;
     c->arch_k = 0;
+}
+static void free_stats(ppde_chains* c) {
+    if (c->stat_cnt) hipFree(c->stat_cnt);
+    if (c->stat_prev) hipFree(c->stat_prev);
+    if (c->stat_dist) hipFree(c->stat_dist);
+    c->stat_cnt = nullptr; c->stat_prev = nullptr; c->stat_dist = nullptr;
+    c->stat_on = false; c->stat_per_site = 0; c->stat_R = 1;
+}
+// the statistics' counters in one allocation: k = 0..5 iters, accepts, moved, jump_sum, dist_sum, wt_returns [n][R'];
+// 6, 7 len_attempts, len_accepts [R'][M]; 8 site_changes [R'][L]
+static size_t stat_cells(const ppde_chains* c, int k) {
+    const size_t R = c->stat_R;
+    return k < 6 ? (size_t)c->n * R : k < 8 ? R * (size_t)c->mu_max : c->stat_per_site ? R * (size_t)c->m->g.L : 0;
+}
+static long long* stat_counter(const ppde_chains* c, int k) {
+    size_t o = 0;
+    for (int j = 0; j < k; ++j) o += stat_cells(c, j);
+    return c->stat_cnt + o;
+}
+static size_t stat_cells_total(const ppde_chains* c) {
+    size_t o = 0;
+    for (int j = 0; j < 9; ++j) o += stat_cells(c, j);
+    return o;
 }
 static size_t pair_tiles(const ppde_chains* c) { return (size_t)c->pair_nt * ((size_t)c->pair_nt + 1) / 2; }
 static int recorder_rows_done(const ppde_chains* c) {
@@ -1304,6 +1334,28 @@ static int launch_archive(ppde_chains* c, const int* it_base, int it_local, hipS
     r.idx = c->arch_idx; r.energy = c->arch_e; r.fitness = c->arch_f; r.step = c->arch_step; r.count = c->arch_count;
     r.hash = c->arch_hash;
     hipLaunchKernelGGL(k_archive, dim3((c->n + ARCH_BLOCK / 64 - 1) / (ARCH_BLOCK / 64)), dim3(ARCH_BLOCK), 0, s, r);
+    HIPCHK(hipGetLastError());
+    return PPDE_OK;
+}
+
+// the statistics' kernel for iteration it_base + it_local (stats.h): every chain of the object. U / mu_cap: the caller-supplied
+// path lengths of that iteration and the sub-steps its noise covers (rng_mode 0)
+static int launch_stats(ppde_chains* c, const int* it_base, int it_local, const int* U, int mu_cap, hipStream_t s) {
+    const Geom& g = c->m->g;
+    StatArgs r{};
+    r.it_base = it_base; r.it_local = it_local;
+    r.n = c->n; r.R = c->stat_R; r.M = c->mu_max; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
+    r.rng_mode = c->cfg.rng_mode; r.pas = c->cfg.pas_length; r.mu_cap = mu_cap > 0 ? mu_cap : c->mu_max;
+    r.key = chain_args(c).key;
+    r.rec = c->rec; r.rec_stride = c->rec_stride; r.cur = c->cur; r.rung_hist = c->n_rungs > 0 ? c->rung_hist : nullptr; r.U_in = U;
+    r.prev = c->stat_prev; r.pdist = c->stat_dist;
+    r.iters = stat_counter(c, 0); r.accepts = stat_counter(c, 1); r.moved = stat_counter(c, 2); r.jump_sum = stat_counter(c, 3);
+    r.dist_sum = stat_counter(c, 4); r.wt_returns = stat_counter(c, 5);
+    r.len_attempts = stat_counter(c, 6); r.len_accepts = stat_counter(c, 7);
+    r.site_changes = c->stat_per_site ? stat_counter(c, 8) : nullptr;
+    r.site_blocks = c->stat_per_site ? ((g.Ls >> 2) + 3) / 4 : 0;
+    const size_t lds = std::max(2 * (size_t)r.M, (size_t)16) * r.R * sizeof(unsigned int);   // (at most 64 x 127 x 2 cells: 65 024 bytes)
+    hipLaunchKernelGGL(k_stats, dim3(r.site_blocks + (c->n + STAT_NW - 1) / STAT_NW + 1), dim3(STAT_BLOCK), lds, s, r);
     HIPCHK(hipGetLastError());
     return PPDE_OK;
 }
@@ -1454,6 +1506,10 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
         }
         if (c->arch_k) {                             // (one stream: every chain of the object; reads cur, the history rows, dist_cur)
             rc = launch_archive(c, it_base, a.it_local, s);
+            if (rc) return rc;
+        }
+        if (c->stat_on) {                            // (one stream: every chain of the object; reads cur, the records, rung_hist)
+            rc = launch_stats(c, it_base, a.it_local, U, mu_cap, s);
             if (rc) return rc;
         }
     }
@@ -1624,6 +1680,7 @@ int ppde_chains_destroy(ppde_chains* c) {
     free_recorder(c);
     free_pairs(c);
     free_archive(c);
+    free_stats(c);
     delete c->tfw;
     if (c->h_err) hipHostFree(c->h_err);
     for (hipStream_t st : c->streams) if (st) hipStreamDestroy(st);
@@ -1681,6 +1738,8 @@ int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_hos
     ARGCHK(!c->initialised, "ppde_chains_set_tempering: the ladder must be set before ppde_chains_init (its graphs hold the kernel choice)");
     ARGCHK(!(c->rec_on && c->rcfg.rung >= 0), "ppde_chains_set_tempering: a recorder that follows a rung is set; clear it first "
                                               "(ppde_chains_set_recorder(c, NULL))");
+    ARGCHK(!c->stat_on, "ppde_chains_set_tempering: move statistics are set and were shaped by the ladder there was; clear them first "
+                        "(ppde_chains_set_stats(c, NULL))");
     HIPCHK(hipSetDevice(c->device));
     if (n_rungs == 0 || !beta_host) {               // clear
         free_tempering(c);
@@ -1806,6 +1865,13 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
         HIPCHK(hipMemsetAsync(c->arch_count, 0, (size_t)n * sizeof(int), s));
         rc = launch_archive(c, nullptr, -1, s);
         if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    if (c->stat_on) {                               // (a fresh start: zero counters, the initial population as the state before iteration 0)
+        HIPCHK(hipMemsetAsync(c->stat_cnt, 0, stat_cells_total(c) * sizeof(long long), s));
+        HIPCHK(hipMemcpyAsync(c->stat_prev, c->cur, (size_t)n * g.Ls, hipMemcpyDeviceToDevice, s));   // (buffer 0: iteration 0 reads it)
+        hipLaunchKernelGGL(k_stats_init, dim3((n + 255) / 256), dim3(256), 0, s, c->rec, c->rec_stride, c->stat_dist, n);
+        HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
     }
     c->steps_done = 0;
@@ -2149,6 +2215,66 @@ int ppde_chains_archive_read(ppde_chains* c, uint8_t* idx, float* energy, float*
         }
         if (count) count[b] = cnt;
     }
+    return PPDE_OK;
+}
+
+int ppde_chains_set_stats(ppde_chains* c, const ppde_stats_config* cfg) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_stats: the statistics must be set before ppde_chains_init (its graphs hold the pointers)");
+    if (!cfg) {                                     // clear
+        HIPCHK(hipSetDevice(c->device));
+        free_stats(c);
+        return PPDE_OK;
+    }
+    ARGCHK(cfg->per_site == 0 || cfg->per_site == 1, "ppde_chains_set_stats: per_site must be 0 or 1");
+    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_stats: n_streams > 1 is not supported (the counters have one "
+                                                            "owner per launch)");
+    HIPCHK(hipSetDevice(c->device));
+    // allocate everything first: a failure leaves the object as it was
+    const Geom& g = c->m->g;
+    const size_t n = c->n;
+    ppde_chains t;                                   // (a holder for free_stats on the error path)
+    t.m = c->m; t.n = c->n; t.mu_max = c->mu_max;
+    t.stat_R = std::max(c->n_rungs, 1); t.stat_per_site = cfg->per_site;
+    const size_t cells = stat_cells_total(&t);
+    hipError_t e = dalloc(&t.stat_cnt, cells);
+    if (e == hipSuccess) e = hipMemset(t.stat_cnt, 0, cells * sizeof(long long));
+    if (e == hipSuccess) e = dalloc(&t.stat_prev, 2 * n * (size_t)g.Ls);
+    if (e == hipSuccess) e = hipMemset(t.stat_prev, 0, 2 * n * (size_t)g.Ls);
+    if (e == hipSuccess) e = dalloc(&t.stat_dist, n);
+    if (e == hipSuccess) e = hipMemset(t.stat_dist, 0, n * sizeof(int));
+    if (e != hipSuccess) {
+        free_stats(&t);
+        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_stats: device allocation: ") + hipGetErrorString(e));
+    }
+    free_stats(c);
+    c->stat_cnt = t.stat_cnt; c->stat_prev = t.stat_prev; c->stat_dist = t.stat_dist;
+    t.stat_cnt = nullptr; t.stat_prev = nullptr; t.stat_dist = nullptr;
+    c->stat_on = true; c->stat_per_site = cfg->per_site; c->stat_R = t.stat_R;
+    return PPDE_OK;
+}
+
+int ppde_chains_stats_shape(ppde_chains* c, int32_t* n_rungs, int32_t* n_lengths, int32_t* per_site) {
+    ARGCHK(c, "null argument");
+    ARGCHK(c->stat_on, "ppde_chains_stats_shape: no statistics were set (ppde_chains_set_stats)");
+    if (n_rungs) *n_rungs = c->stat_R;
+    if (n_lengths) *n_lengths = c->mu_max;
+    if (per_site) *per_site = c->stat_per_site;
+    return PPDE_OK;
+}
+
+int ppde_chains_stats_read(ppde_chains* c, int64_t* iters, int64_t* accepts, int64_t* moved, int64_t* jump_sum, int64_t* dist_sum,
+                           int64_t* wt_returns, int64_t* len_attempts, int64_t* len_accepts, int64_t* site_changes) {
+    ARGCHK(c && c->stat_on, "ppde_chains_stats_read: no statistics were set (ppde_chains_set_stats)");
+    ARGCHK(c->initialised, "chains not initialised");
+    ARGCHK(c->stat_per_site || !site_changes, "ppde_chains_stats_read: the statistics keep no per-site counts (per_site = 0): pass NULL "
+                                              "for site_changes");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    int64_t* out[9] = {iters, accepts, moved, jump_sum, dist_sum, wt_returns, len_attempts, len_accepts, site_changes};
+    for (int k = 0; k < 9; ++k)
+        if (out[k] && stat_cells(c, k))
+            HIPCHK(hipMemcpy(out[k], stat_counter(c, k), stat_cells(c, k) * sizeof(long long), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 

@@ -59,6 +59,13 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         merged from them (ppde_amd/archive.py: idx, energy, fitness, chain, step, n_chains; best first). A sharded
                         run gathers the per-chain archives in global chain order and merges on every rank. Not with
                         paper_results, not with ppde_streams > 1.
+    ppde_stats          None or False (default): off. True: move statistics counted on the device (include/ppde_hip.h,
+                        ppde_chains_set_stats): acceptances, jump distances, mutation counts and wild-type returns per (chain,
+                        rung), attempts and acceptances per (rung, path length), changes per (rung, residue); no host round trip,
+                        nothing else of the run changes. 'no-sites' leaves the per-residue counts out. After run(),
+                        `sampler.stats` holds the raw int64 arrays (ppde_amd/stats.py: KEYS), chain [n] (GLOBAL chain index), betas
+                        and `summary` (stats.summarise). A sharded run gathers the per-chain arrays in global chain order and sums
+                        the others; the periodic log gains one line. Not with ppde_streams > 1.
     ppde_shard          False (default). True with torch.distributed initialised: chains are split over ranks
                         and gathered at the end (one RCCL all_gather); every rank returns the full result.
 """
@@ -69,7 +76,7 @@ import time
 import numpy as np
 import torch
 
-from . import _hip, archive as chain_archive, library as design_library
+from . import _hip, archive as chain_archive, library as design_library, stats as chain_stats
 from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
@@ -151,6 +158,18 @@ def check_archive(k, paper_results=False, n_streams=1):
     if int(n_streams) > 1:
         raise ValueError("ppde_archive: ppde_streams > 1 is not supported (one launch archives every chain)")
     return int(k)
+
+
+def check_stats(spec, n_streams=1):
+    """ppde_stats as None (off: None or False), True, or 'no-sites'; ValueError otherwise, and for what statistics cannot be
+    combined with."""
+    if spec is None or spec is False:
+        return None
+    if spec is not True and spec != "no-sites":
+        raise ValueError(f"ppde_stats: expected None / False (off), True or 'no-sites', got {spec!r}")
+    if int(n_streams) > 1:
+        raise ValueError("ppde_stats: ppde_streams > 1 is not supported (the counters have one owner per launch)")
+    return spec
 
 
 def check_ladder(betas):
@@ -327,6 +346,29 @@ class Chains:
                 "idx", "energy", "fitness", "step", "count")]))
         return out
 
+    def set_stats(self, per_site=True):
+        """Move statistics (include/ppde_hip.h, ppde_chains_set_stats): acceptances, jump distances, mutation counts and wild-type
+        returns per (chain, rung), attempts and acceptances per (rung, path length) and, with per_site, changes per (rung,
+        residue), counted on the device. None clears them. Only before init(), and after set_tempering() when there is a ladder."""
+        with torch.cuda.device(self.model.device):
+            if per_site is None:
+                _hip.check(self.lib.ppde_chains_set_stats(self.handle, None))
+                return
+            cfg = _hip.StatsConfig(per_site=int(bool(per_site)))
+            _hip.check(self.lib.ppde_chains_set_stats(self.handle, C.byref(cfg)))
+
+    def stats(self):
+        """The counters so far, int64: iters, accepts, moved, jump_sum, dist_sum, wt_returns [n, R'], len_attempts, len_accepts
+        [R', M], site_changes [R', L] (None when per_site is off); R' = max(rungs, 1), M = 2 pas_length - 1."""
+        R, M, ps = C.c_int32(), C.c_int32(), C.c_int32()
+        _hip.check(self.lib.ppde_chains_stats_shape(self.handle, C.byref(R), C.byref(M), C.byref(ps)))
+        out = {k: np.zeros((self.n, R.value), np.int64) for k in chain_stats.PER_CHAIN}
+        out.update({k: np.zeros((R.value, M.value), np.int64) for k in chain_stats.PER_LENGTH})
+        out["site_changes"] = np.zeros((R.value, self.model.L), np.int64) if ps.value else None
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_stats_read(self.handle, *[_hip.ptr(out[k]) for k in chain_stats.KEYS]))
+        return out
+
     def init(self, idx0):
         idx0 = idx0.to(self.model.device, torch.uint8).contiguous()
         if tuple(idx0.shape) != (self.n, self.model.L):
@@ -481,6 +523,8 @@ class PPDE_PAS(BaseSampler):
                     raise ValueError(f"ppde_sample_rung must be a rung of the ladder, 0..{self.betas.size - 1}")
         self.archive_k = check_archive(getattr(args, "ppde_archive", None), self.paper_results, self.n_streams)
         self.archive = None
+        self.stats_spec = check_stats(getattr(args, "ppde_stats", None), self.n_streams)
+        self.stats = None
         self.noise_bytes = getattr(args, "ppde_noise_bytes", 96 << 20)   # host->device noise is uploaded in chunks of about this size
         self.last_chains = None
         self.timings = {}       # seconds of the last run(): setup (chains + hipGraph capture), iterations, log path, collect
@@ -562,6 +606,8 @@ class PPDE_PAS(BaseSampler):
             chains.set_pair_counts(pair_sites)
         if self.archive_k:
             chains.set_archive(self.archive_k)
+        if self.stats_spec is not None:
+            chains.set_stats(self.stats_spec is True)
         chains.init(idx0[lo:hi])
 
         def gathered(a):
@@ -570,6 +616,13 @@ class PPDE_PAS(BaseSampler):
         def gathered_ensembles(a):
             # (every shard boundary is a multiple of R, so the shards are equal and the n / R ensembles split the same way)
             return all_gather_rows(torch.as_tensor(a), n_global // R).numpy() if comm and R > 1 else np.asarray(a)
+
+        def stats_gathered(raw):
+            # (per-chain arrays in global chain order, the others summed: every rank ends with the full result)
+            out = {k: gathered(raw[k]) for k in chain_stats.PER_CHAIN}
+            for k in chain_stats.PER_LENGTH + ("site_changes",):
+                out[k] = raw[k] if raw[k] is None or not comm else sum_over_ranks(torch.from_numpy(raw[k])).numpy()
+            return out
 
         def log(i, first=False):
             pk = chains.peek()
@@ -591,6 +644,8 @@ class PPDE_PAS(BaseSampler):
                 if R:
                     ts = chains.tempering_state()
                     print(f'   # swaps accepted = {int(gathered_ensembles(ts["swap_accepts"]).sum())} / {int(gathered_ensembles(ts["swap_attempts"]).sum())}')
+                if self.stats_spec is not None:
+                    print(chain_stats.log_line(stats_gathered(chains.stats())))
                 print('', flush=True)
 
         chains.sync()
@@ -674,6 +729,13 @@ class PPDE_PAS(BaseSampler):
             arc["chain"] = np.arange(n_global, dtype=np.int64)
             arc["candidates"] = chain_archive.merge(arc["idx"], arc["energy"], arc["fitness"], arc["step"], arc["count"])
             self.archive = arc
+        self.stats = None
+        if self.stats_spec is not None:
+            st = stats_gathered(chains.stats())
+            st["chain"] = np.arange(n_global, dtype=np.int64)
+            st["betas"] = None if self.betas is None else self.betas.copy()
+            st["summary"] = chain_stats.summarise(st, st["betas"])
+            self.stats = st
         if n_global == 1:
             # the reference's single-chain shapes (ppde.py:178-183; the ensemble's `.squeeze()`, nets.py:442, makes one chain's
             # fitness a scalar): fitness_history (T+1,) next to energy_history (T+1, 1); with ProteinSupervised the energy IS

@@ -42,7 +42,9 @@ from ppde_amd.sampler import PPDE_PAS  # noqa: E402
 def get_sampler(args, library=None):
     if args.sampler == "PPDE":
         # (a copy: the namespace itself is what config.txt records, and a mask is no JSON)
-        return PPDE_PAS(argparse.Namespace(**{**vars(args), "ppde_library": library}))
+        # (--ppde_stats_no_sites alone switches the statistics on, without their per-residue counts)
+        stats = "no-sites" if getattr(args, "ppde_stats_no_sites", False) else bool(getattr(args, "ppde_stats", False))
+        return PPDE_PAS(argparse.Namespace(**{**vars(args), "ppde_library": library, "ppde_stats": stats}))
     raise NotImplementedError(f"--sampler {args.sampler}: only PPDE is implemented on the MI355X path "
                               "(simulated_annealing / MALA-approx / CMAES / Random are the paper's baselines)")
 
@@ -155,6 +157,11 @@ def main(args):
             np.save(results_path / "candidates.npy", cand["idx"])
             for name, key in (("energy", "energy"), ("fitness", "fitness"), ("chain", "chain"), ("step", "step"), ("nchains", "n_chains")):
                 np.save(results_path / f"candidates_{name}.npy", cand[key])
+        stats = getattr(sampler, "stats", None)
+        if stats is not None:
+            for name in ("iters", "accepts", "moved", "jump_sum", "dist_sum", "wt_returns", "len_attempts", "len_accepts", "site_changes"):
+                if stats[name] is not None:
+                    np.save(results_path / f"stats_{name}.npy", stats[name])
 
     if not args.disable_MSA_transformer_scoring:
         print("MSA-Transformer scoring is not part of this build (needs the ESM-MSA-1b weights); skipped")
@@ -256,6 +263,12 @@ def build_parser():
                          "population's distinct candidates merged from them: candidates.npy uint8 [M, L] with candidates_energy, "
                          "_fitness, _chain, _step and _nchains [M], best first. Works with either --ppde_rng; not with "
                          "--paper_results")
+    pp.add_argument("--ppde_stats", action="store_true",
+                    help="count, on the device, how the chains move: stats_iters, _accepts, _moved, _jump_sum, _dist_sum and "
+                         "_wt_returns.npy int64 [n, R] per (chain, rung), stats_len_attempts and _len_accepts.npy [R, 2 pas - 1] per "
+                         "(rung, path length), stats_site_changes.npy [R, L] per (rung, residue), R = rungs of the ladder or 1; the "
+                         "periodic log gains an 'acceptance so far' line. Works with either --ppde_rng")
+    pp.add_argument("--ppde_stats_no_sites", action="store_true", help="the statistics without stats_site_changes.npy")
     return parser
 
 
