@@ -279,6 +279,66 @@ int ppde_chains_tempering_state(ppde_chains* c, int32_t* rung, float* beta, int6
 /* rung_history host uint8 [steps_done + 1, n]: the rung each chain held after every iteration (row 0: the start). */
 int ppde_chains_tempering_history(ppde_chains* c, uint8_t* rung_history);
 
+/* Population annealing (off by default; needs reversible mode, as tempering does, and excludes it): all chains of a DEME share one
+ * inverse temperature, which climbs a schedule, and at every step of the schedule the deme is resampled with weights
+ * exp(dbeta E) (Hukushima & Iba; Machta): a sequential Monte Carlo sampler with a defined target, exp(beta[s] E)/Z, at every stage.
+ *   demes: D chains with consecutive GLOBAL indices g = chain_offset + local index; chain g belongs to deme g / D;
+ *   schedule: beta[0] <= beta[1] <= ... <= beta[S], S = n_stages, every entry finite and positive, equal neighbours allowed;
+ *   run: every chain starts at beta[0] and runs the reversible iteration of tempering on beta * E, by the same kernels: the same
+ *     Philox counters and variates are consumed. Histories, best states, peek and collect hold the UNTEMPERED energy and fitness;
+ *   events: behind the accept phase of iteration `it` (0-based) when (it + 1) % every == 0 and s = (it + 1) / every - 1 < S.
+ *     Stage s resamples every deme and then moves every chain from beta[s] to beta[s + 1]. Past the schedule nothing happens and
+ *     beta stays at beta[S]. events_cap = min(S, max_steps / every);
+ *   plan of one deme at an event, in fp64 on the fp32 inputs: e_i = the post-accept energy of the deme's chain i (history row
+ *     it + 1); dbeta = (double)beta[s + 1] - (double)beta[s]; a non-finite e_i has weight 0; E_max = the largest finite energy;
+ *     w_i = exp(dbeta ((double)e_i - E_max)); C_i = the inclusive prefix sum in index order, W = C_{D-1}; u = the uniform of
+ *     Philox word .x at counter (global index of the deme's first chain, it, 0x40000001, 0), a stream nothing else draws from;
+ *     tau_j = (j + u) (W / D), j = 0..D-1; ancestor a_j = #{i : C_i <= tau_j}, clamped to the last i with w_i > 0; n_i = the
+ *     number of j with a_j = i (systematic resampling: n_i is floor or ceil of D w_i / W). A deme without a finite energy keeps
+ *     the identity and records log_mean_w = -inf, ess = 0;
+ *   slot rule: a chain with n_i >= 1 keeps its slot, parent[i] = i. The dead slots (n_i = 0), in increasing order, receive the
+ *     surplus list in order: every i in increasing order, repeated n_i - 1 times. Copies therefore read only rows nobody writes;
+ *     a survivor's slot, archive and best state go on undisturbed;
+ *   a replaced slot d takes from p = parent[d] everything the next iteration and the observers read for a chain: the state (and
+ *     its transposed copy for the Potts kernel), the energy, fitness and mutation count it continues from, its gradient row under
+ *     gradient reuse, row it + 1 of both histories, and row it + 1 of the random trajectory when d is the recorded chain. Row
+ *     it + 1 thereby describes the population AFTER selection, which is what ppde_chains_peek returns. The running best of slot d
+ *     follows the accept phase's strict rule: if the copied energy exceeds best_e, then best_e, best_f, best_t = it + 1 and
+ *     best_state follow it. The last accept bit and the traces stay the slot's own Metropolis result;
+ *   recorded per event, [events_cap] rows: parent int32 [n] (LOCAL index of the ancestor; the identity where nothing was
+ *     replaced); pre_energy fp32 [n], the energies the plan saw (the history row is rewritten: this is the only place they
+ *     survive, and what a pilot run's next schedule is designed from); log_mean_w fp64 [n / D] = log(W / D) + dbeta E_max, whose
+ *     sum over the events is the deme's estimate of log(Z_{beta[S]} / Z_{beta[0]}); ess fp64 [n / D] = W^2 / sum w_i^2;
+ *   observers: recorder, pair counts, archive and move statistics are defined by what ppde_chains_peek returns; their kernels run
+ *     behind the selection and hold unchanged -- except that the statistics' moved <= accepts no longer follows: a replaced
+ *     slot jumps without accepting;
+ *   a schedule of equal betas all 1 gives, bit for bit, the histories, states, bests and traces of the reversible run; results do
+ *     not depend on the sharding.
+ * An annealing run enqueues propose, experts, accept and two selection kernels (ppde_amd/csrc/anneal.h) per iteration, unfused,
+ * valid under graph replay and eager issue alike; on an iteration without an event both return at once. A run without annealing
+ * enqueues nothing new and makes no additional runtime call. Valid between ppde_chains_create and ppde_chains_init; NULL clears it.
+ * PPDE_ERR_INVALID with a message, the object unchanged: after init; reversible mode not on; tempering set; deme outside 2..1024;
+ * n_chains or chain_offset no multiple of deme; every < 1; n_stages outside 1..4096; events_cap == 0; a beta that is not finite
+ * and positive, or a decreasing pair; n_streams > 1. While it is set, ppde_chains_set_tempering and ppde_chains_set_reversible(c, 0)
+ * are PPDE_ERR_INVALID. The schedule is copied; the chains own the device arrays; a failed allocation is PPDE_ERR_HIP and leaves
+ * nothing half-set. */
+typedef struct {
+    int32_t deme;        /* D, 2..1024 */
+    int32_t every;       /* >= 1 */
+    int32_t n_stages;    /* S, 1..4096 */
+    const float* beta;   /* [S + 1] */
+} ppde_anneal_config;
+int ppde_chains_set_annealing(ppde_chains* c, const ppde_anneal_config* cfg /* NULL clears */);
+/* Deme size, event capacity and the events that have happened (follows ppde_chains_steps_done). Any pointer may be NULL.
+ * PPDE_ERR_INVALID without annealing. */
+int ppde_chains_annealing_shape(ppde_chains* c, int32_t* deme, int32_t* events_cap, int32_t* events_done);
+/* Events [first_event, first_event + n_events) to the host, and the inverse temperature each chain holds now. Synchronises; any
+ * pointer may be NULL. PPDE_ERR_INVALID without annealing, before init, or for events beyond events_done. */
+int ppde_chains_annealing_read(ppde_chains* c, int first_event, int n_events,
+                               int32_t* parent /* [n_events][n] */, float* pre_energy /* [n_events][n] */,
+                               double* log_mean_w /* [n_events][n / D] */, double* ess /* [n_events][n / D] */,
+                               float* beta_now /* [n] */);
+
 /* Recorder (off by default): thinned samples of the population and per-site letter counts, written on the device inside the
  * iteration loop (one more kernel behind the accept phase -- behind the swap, with tempering -- of every iteration of a recording
  * run; no host round trip; valid under graph replay and eager issue alike). A run without a recorder enqueues nothing new.
@@ -391,7 +451,7 @@ int ppde_chains_archive_read(ppde_chains* c, uint8_t* idx /* [n][K][L] */, float
  *     site_changes [R'][L]  1 at [r][l] for every changed residue l of chain b (only with per_site = 1)
  *   so sum_r iters[b][r] = steps_done; sum_b iters[.][r] = sum_u len_attempts[r][u] (accepts alike); sum_l site_changes[r][l] =
  *   sum_b jump_sum[b][r]; and without paper_results moved <= accepts elementwise (an accepted path may undo itself: h may be 0, and
- *   h <= U). Everything is an integer: the results do not depend on any summation order.
+ *   h <= U) -- except in an annealing run, where a slot replaced by the selection jumps (h up to L) without accepting. Everything is an integer: the results do not depend on any summation order.
  * The statistics change no other result: histories, best states, traces, recorder rows, pair counts, archive and Philox streams are
  * those of the run without them. They hold in the default, library, reversible and tempering modes and with paper_results, for every
  * `which`, both gradient policies and both rng_modes. They are independent of recorder, pair counts and archive.

@@ -44,6 +44,11 @@ class StatsConfig(C.Structure):
     _fields_ = [("per_site", C.c_int32)]
 
 
+class AnnealConfig(C.Structure):
+    """ppde_anneal_config (include/ppde_hip.h)."""
+    _fields_ = [("deme", C.c_int32), ("every", C.c_int32), ("n_stages", C.c_int32), ("beta", C.POINTER(C.c_float))]
+
+
 class TfWeights(C.Structure):
     """ppde_tf_weights (include/ppde_hip.h): host pointers to ESM-2's fp32 parameters."""
     _PER_LAYER = ("q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "o_w", "o_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b",
@@ -81,6 +86,9 @@ SIGNATURES = {
     "ppde_chains_set_tempering": (_i, [_p, _i, _p, _i]),
     "ppde_chains_tempering_state": (_i, [_p, _p, _p, _p, _p]),
     "ppde_chains_tempering_history": (_i, [_p, _p]),
+    "ppde_chains_set_annealing": (_i, [_p, C.POINTER(AnnealConfig)]),
+    "ppde_chains_annealing_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ppde_chains_annealing_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
     "ppde_chains_set_recorder": (_i, [_p, C.POINTER(RecordConfig)]),
     "ppde_chains_recorder_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ppde_chains_recorder_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),

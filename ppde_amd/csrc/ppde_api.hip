@@ -20,6 +20,7 @@
 #include "pairs.h"
 #include "archive.h"
 #include "stats.h"
+#include "anneal.h"
 
 static thread_local std::string g_err;
 
@@ -1204,6 +1205,13 @@ struct ppde_chains {
     int *rung = nullptr, *slot = nullptr;        // [n], [n/R][R]
     long long *swap_attempts = nullptr, *swap_accepts = nullptr;   // [n/R][R-1]
     uint8_t* rung_hist = nullptr;                // [T+1][n]
+    // population annealing (ppde_chains_set_annealing): owned here, allocated there; an_on false = none
+    bool an_on = false;
+    int an_D = 0, an_every = 0, an_S = 0, an_cap = 0;   // deme size, iterations per stage, stages, events_cap
+    std::vector<float> an_sched;                 // beta[0] <= ... <= beta[S]
+    float *an_sched_dev = nullptr, *an_beta = nullptr, *an_pre = nullptr;   // [S+1], [n], [events_cap][n]
+    int* an_parent = nullptr;                    // [events_cap][n]
+    double *an_lmw = nullptr, *an_ess = nullptr; // [events_cap][n/D]
     // recorder (ppde_chains_set_recorder): owned here, allocated there; rec_on false = none
     bool rec_on = false;
     ppde_record_config rcfg{};
@@ -1296,6 +1304,18 @@ static void free_tempering(ppde_chains* c) {
     c->n_rungs = 0; c->swap_every = 0; c->ladder.clear();
 }
 
+static void free_annealing(ppde_chains* c) {
+    if (c->an_sched_dev) hipFree(c->an_sched_dev);
+    if (c->an_beta) hipFree(c->an_beta);
+    if (c->an_pre) hipFree(c->an_pre);
+    if (c->an_parent) hipFree(c->an_parent);
+    if (c->an_lmw) hipFree(c->an_lmw);
+    if (c->an_ess) hipFree(c->an_ess);
+    c->an_sched_dev = c->an_beta = c->an_pre = nullptr; c->an_parent = nullptr; c->an_lmw = c->an_ess = nullptr;
+    c->an_on = false; c->an_D = c->an_every = c->an_S = c->an_cap = 0; c->an_sched.clear();
+}
+static int annealing_events_done(const ppde_chains* c) { return std::min(c->an_cap, c->steps_done / c->an_every); }
+
 static PasArgs chain_args(const ppde_chains* c) {
     const ppde_model* m = c->m;
     PasArgs a = base_pas_args(m, c->cfg.which, c->n);
@@ -1319,7 +1339,7 @@ static PasArgs chain_args(const ppde_chains* c) {
     a.err_flag = c->err_flag;
     a.dbg = c->dbg;
     a.allowed = c->allowed;
-    a.beta = c->beta; a.rung = c->rung; a.slot = c->slot; a.swap_attempts = c->swap_attempts; a.swap_accepts = c->swap_accepts;
+    a.beta = c->an_on ? c->an_beta : c->beta; a.rung = c->rung; a.slot = c->slot; a.swap_attempts = c->swap_attempts; a.swap_accepts = c->swap_accepts;
     a.rung_hist = c->rung_hist; a.n_rungs = c->n_rungs; a.swap_every = c->swap_every;
     return a;
 }
@@ -1356,6 +1376,24 @@ static int launch_stats(ppde_chains* c, const int* it_base, int it_local, const 
     r.site_blocks = c->stat_per_site ? ((g.Ls >> 2) + 3) / 4 : 0;
     const size_t lds = std::max(2 * (size_t)r.M, (size_t)16) * r.R * sizeof(unsigned int);   // (at most 64 x 127 x 2 cells: 65 024 bytes)
     hipLaunchKernelGGL(k_stats, dim3(r.site_blocks + (c->n + STAT_NW - 1) / STAT_NW + 1), dim3(STAT_BLOCK), lds, s, r);
+    HIPCHK(hipGetLastError());
+    return PPDE_OK;
+}
+
+// the two selection kernels behind the accept phase of iteration it_base + it_local (anneal.h): every chain of the object
+static int launch_select(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
+    const PasArgs p = chain_args(c);
+    AnnealArgs r{};
+    r.it_base = it_base; r.it_local = it_local;
+    r.n = c->n; r.D = c->an_D; r.every = c->an_every; r.S = c->an_S;
+    r.g = p.g; r.n_pad = c->n_pad; r.key = p.key;
+    r.rec_stride = c->rec_stride; r.random_chain = c->cfg.random_chain; r.reuse = c->cfg.reuse_grad;
+    r.sched = c->an_sched_dev; r.beta = c->an_beta; r.rec = c->rec; r.cur = c->cur; r.curT = (uint8_t*)c->curT;
+    r.grad_cur = c->grad_cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist; r.best_state = c->best_state; r.rtraj = c->rtraj;
+    r.parent = c->an_parent; r.pre_energy = c->an_pre; r.log_mean_w = c->an_lmw; r.ess = c->an_ess;
+    hipLaunchKernelGGL(k_select_plan, dim3(c->n / c->an_D), dim3(ANNEAL_BLOCK), 0, s, r);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_select_copy, dim3(c->n), dim3(ANNEAL_BLOCK), 0, s, r);
     HIPCHK(hipGetLastError());
     return PPDE_OK;
 }
@@ -1411,7 +1449,7 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
                         else hipLaunchKernelGGL(K, dim3(n_sub), dim3(PPDE_BLOCK), lds, s, a); } while (0)
     with_gpt([&](auto G) {
         constexpr int GP = decltype(G)::value;
-        if (c->n_rungs > 0) {                        // tempering (reversible mode): general instantiations, rows and ratio on beta[b] * E
+        if (c->n_rungs > 0 || c->an_on) {            // tempering, annealing (reversible mode): general instantiations, rows and ratio on beta[b] * E
             if (which == KP_PROPOSE) {
                 if (a.rng_mode == 0) { if (lib) PPDE_CL((k_propose_temp<GP, true, true>)); else PPDE_CL((k_propose_temp<GP, true, false>)); }
                 else { if (lib) PPDE_CL((k_propose_temp<GP, false, true>)); else PPDE_CL((k_propose_temp<GP, false, false>)); }
@@ -1455,6 +1493,7 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
 // `count` iterations of ppde.py:65-153 for sub-population k, enqueued on that sub-population's stream.
 // Re-evaluating mode: EG(x) P EG(y) A per iteration. Reuse mode: P, then EG(y) + fused [accept | next propose].
 // Tempering: [EG(x)] P EG(y) A S, never fused: the next proposal must see the post-swap beta, the swap the post-accept energy.
+// Annealing: the same flow with the two selection kernels in the swap's place.
 static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int first_local, int count, const int* U,
                               const float* q, const float* u, int mu_cap = 0) {
     const ppde_model* m = c->m;
@@ -1464,7 +1503,7 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
     a.b_off = b_off; a.it_base = it_base; a.U_in = U; a.q_in = q; a.u_in = u;
     if (mu_cap > 0) a.mu_cap = mu_cap;              // caller-supplied noise holds only max_u[i] sub-steps of variates
     const bool temper = c->n_rungs > 0;
-    const bool fuse = c->cfg.reuse_grad && c->cfg.rng_mode == 1 && !temper;
+    const bool fuse = c->cfg.reuse_grad && c->cfg.rng_mode == 1 && !temper && !c->an_on;
     int rc;
     for (int i = 0; i < count; ++i) {
         a.it_local = first_local + i;
@@ -1484,6 +1523,10 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
         if (temper) {                                // (one stream: every chain of the object)
             hipLaunchKernelGGL(k_swap, dim3((c->n + 255) / 256), dim3(256), 0, s, a);
             HIPCHK(hipGetLastError());
+        }
+        if (c->an_on) {                              // (one stream: every chain of the object; the observers below see the selected population)
+            rc = launch_select(c, it_base, a.it_local, s);
+            if (rc) return rc;
         }
         if (c->rec_on) {                             // (one stream: every chain of the object; reads cur, the history rows, slot)
             const Geom& g = m->g;
@@ -1677,6 +1720,7 @@ int ppde_chains_destroy(ppde_chains* c) {
     for (void* p : c->allocs) hipFree(p);
     if (c->allowed) hipFree(c->allowed);
     free_tempering(c);
+    free_annealing(c);
     free_recorder(c);
     free_pairs(c);
     free_archive(c);
@@ -1729,6 +1773,8 @@ int ppde_chains_set_reversible(ppde_chains* c, int on) {
                                           "which is no Metropolis step; the two cannot be combined");
     ARGCHK(on || c->n_rungs == 0, "ppde_chains_set_reversible: tempering is set and needs reversible mode (clear it with "
                                   "ppde_chains_set_tempering(c, 0, NULL, 0) first)");
+    ARGCHK(on || !c->an_on, "ppde_chains_set_reversible: annealing is set and needs reversible mode (clear it with "
+                            "ppde_chains_set_annealing(c, NULL) first)");
     c->reversible = on != 0;
     return PPDE_OK;
 }
@@ -1740,6 +1786,8 @@ int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_hos
                                               "(ppde_chains_set_recorder(c, NULL))");
     ARGCHK(!c->stat_on, "ppde_chains_set_tempering: move statistics are set and were shaped by the ladder there was; clear them first "
                         "(ppde_chains_set_stats(c, NULL))");
+    ARGCHK(!c->an_on, "ppde_chains_set_tempering: annealing is set (a schedule and a ladder cannot be combined); clear it first "
+                      "(ppde_chains_set_annealing(c, NULL))");
     HIPCHK(hipSetDevice(c->device));
     if (n_rungs == 0 || !beta_host) {               // clear
         free_tempering(c);
@@ -1782,6 +1830,87 @@ int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_hos
     t.beta = nullptr; t.rung = nullptr; t.slot = nullptr; t.swap_attempts = nullptr; t.swap_accepts = nullptr; t.rung_hist = nullptr;
     c->n_rungs = R; c->swap_every = swap_every;
     c->ladder.assign(beta_host, beta_host + R);
+    return PPDE_OK;
+}
+
+int ppde_chains_set_annealing(ppde_chains* c, const ppde_anneal_config* cfg) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_annealing: the schedule must be set before ppde_chains_init (its graphs hold the kernel choice)");
+    if (!cfg) {                                     // clear
+        HIPCHK(hipSetDevice(c->device));
+        free_annealing(c);
+        return PPDE_OK;
+    }
+    ARGCHK(c->reversible, "ppde_chains_set_annealing: annealing needs reversible mode (ppde_chains_set_reversible): only there is the "
+                          "law at beta, exp(beta E)/Z, defined");
+    ARGCHK(c->n_rungs == 0, "ppde_chains_set_annealing: tempering is set (a schedule and a ladder cannot be combined); clear it first "
+                            "(ppde_chains_set_tempering(c, 0, NULL, 0))");
+    ARGCHK(cfg->deme >= 2 && cfg->deme <= ANNEAL_DMAX, "ppde_chains_set_annealing: deme must be in 2..1024");
+    ARGCHK(c->n % cfg->deme == 0, "ppde_chains_set_annealing: n_chains must be a multiple of deme (demes of consecutive chains)");
+    ARGCHK(c->cfg.chain_offset % (uint64_t)cfg->deme == 0, "ppde_chains_set_annealing: chain_offset must be a multiple of deme (a deme "
+                                                           "may not straddle two shards)");
+    ARGCHK(cfg->every >= 1, "ppde_chains_set_annealing: every must be >= 1");
+    ARGCHK(cfg->n_stages >= 1 && cfg->n_stages <= 4096, "ppde_chains_set_annealing: n_stages must be in 1..4096");
+    ARGCHK(cfg->beta, "ppde_chains_set_annealing: no schedule (beta is NULL)");
+    const int S = cfg->n_stages, cap = std::min(S, c->T / cfg->every);
+    ARGCHK(cap >= 1, "ppde_chains_set_annealing: no event would fit (events_cap = min(n_stages, max_steps / every) is 0)");
+    for (int s = 0; s <= S; ++s) {
+        const float b = cfg->beta[s];
+        if (!(b > 0.f) || !(b < INFINITY))
+            return fail(PPDE_ERR_INVALID, "ppde_chains_set_annealing: beta[" + std::to_string(s) + "] must be finite and positive");
+        if (s > 0 && b < cfg->beta[s - 1])
+            return fail(PPDE_ERR_INVALID, "ppde_chains_set_annealing: the schedule must not decrease (beta[" + std::to_string(s) +
+                                          "] < beta[" + std::to_string(s - 1) + "])");
+    }
+    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_annealing: n_streams > 1 is not supported (the selection "
+                                                            "couples the chains of a deme)");
+    HIPCHK(hipSetDevice(c->device));
+    // allocate everything first: a failure leaves the object as it was
+    const size_t n = c->n, demes = n / cfg->deme;
+    ppde_chains t;                                   // (a holder for free_annealing on the error path)
+    hipError_t e = dalloc(&t.an_sched_dev, (size_t)S + 1);
+    if (e == hipSuccess) e = hipMemcpy(t.an_sched_dev, cfg->beta, ((size_t)S + 1) * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dalloc(&t.an_beta, n);
+    if (e == hipSuccess) e = dalloc(&t.an_pre, (size_t)cap * n);
+    if (e == hipSuccess) e = dalloc(&t.an_parent, (size_t)cap * n);
+    if (e == hipSuccess) e = dalloc(&t.an_lmw, (size_t)cap * demes);
+    if (e == hipSuccess) e = dalloc(&t.an_ess, (size_t)cap * demes);
+    if (e != hipSuccess) {
+        free_annealing(&t);
+        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_annealing: device allocation: ") + hipGetErrorString(e));
+    }
+    free_annealing(c);
+    c->an_sched_dev = t.an_sched_dev; c->an_beta = t.an_beta; c->an_pre = t.an_pre; c->an_parent = t.an_parent;
+    c->an_lmw = t.an_lmw; c->an_ess = t.an_ess;
+    t.an_sched_dev = t.an_beta = t.an_pre = nullptr; t.an_parent = nullptr; t.an_lmw = t.an_ess = nullptr;
+    c->an_on = true; c->an_D = cfg->deme; c->an_every = cfg->every; c->an_S = S; c->an_cap = cap;
+    c->an_sched.assign(cfg->beta, cfg->beta + S + 1);
+    return PPDE_OK;
+}
+
+int ppde_chains_annealing_shape(ppde_chains* c, int32_t* deme, int32_t* events_cap, int32_t* events_done) {
+    ARGCHK(c, "null argument");
+    ARGCHK(c->an_on, "ppde_chains_annealing_shape: no annealing was set (ppde_chains_set_annealing)");
+    if (deme) *deme = c->an_D;
+    if (events_cap) *events_cap = c->an_cap;
+    if (events_done) *events_done = annealing_events_done(c);
+    return PPDE_OK;
+}
+
+int ppde_chains_annealing_read(ppde_chains* c, int first_event, int n_events, int32_t* parent, float* pre_energy, double* log_mean_w,
+                               double* ess, float* beta_now) {
+    ARGCHK(c && c->an_on, "ppde_chains_annealing_read: no annealing was set (ppde_chains_set_annealing)");
+    ARGCHK(c->initialised, "chains not initialised");
+    ARGCHK(first_event >= 0 && n_events >= 0 && first_event + n_events <= annealing_events_done(c),
+           "ppde_chains_annealing_read: events beyond those that have happened (ppde_chains_annealing_shape)");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    const size_t n = c->n, demes = n / c->an_D, f = (size_t)first_event, k = (size_t)n_events;
+    if (parent && k) HIPCHK(hipMemcpy(parent, c->an_parent + f * n, k * n * sizeof(int), hipMemcpyDeviceToHost));
+    if (pre_energy && k) HIPCHK(hipMemcpy(pre_energy, c->an_pre + f * n, k * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (log_mean_w && k) HIPCHK(hipMemcpy(log_mean_w, c->an_lmw + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
+    if (ess && k) HIPCHK(hipMemcpy(ess, c->an_ess + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
+    if (beta_now) HIPCHK(hipMemcpy(beta_now, c->an_beta, n * sizeof(float), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 
@@ -1858,6 +1987,10 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
     if (c->n_rungs > 0) {
         rc = init_tempering(c);
         if (rc) return rc;
+    }
+    if (c->an_on) {                                 // (a fresh start: every chain at beta[0])
+        const std::vector<float> hb((size_t)n, c->an_sched[0]);
+        HIPCHK(hipMemcpy(c->an_beta, hb.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     }
     if (c->rec_on) HIPCHK(hipMemset(c->rec_counts, 0, (size_t)g.L * PPDE_A * sizeof(unsigned long long)));   // (a fresh start counts from zero)
     if (c->pair_on) HIPCHK(hipMemset(c->pair_counts, 0, pair_tiles(c) * PAIR_TILE * sizeof(unsigned long long)));

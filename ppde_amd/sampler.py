@@ -37,6 +37,15 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         population (and every shard boundary) must be a multiple of the ladder; not with ppde_streams > 1.
                         Histories and best states stay on the untempered energy. After run(), `sampler.tempering` holds
                         betas, rung_history [T+1, n], swap_attempts and swap_accepts [n / R, R - 1].
+    ppde_anneal_betas   None (default), or a schedule of inverse temperatures beta[0] <= beta[1] <= ... <= beta[S]: population
+                        annealing of a reversible run (include/ppde_hip.h, ppde_chains_set_annealing). Consecutive chains form
+                        demes of ppde_deme (default 0: all chains of the run); every chain starts at beta[0], and behind every
+                        ppde_anneal_every-th iteration (default 1) each deme is resampled with weights exp(dbeta energy) and moves
+                        to the next beta. Needs ppde_reversible; not with ppde_betas, not with ppde_streams > 1; the population
+                        (and every shard boundary) must be a multiple of the deme. Histories and best states stay on the
+                        untempered energy. After run(), `sampler.annealing` holds betas, deme, every, parent [events, n] (GLOBAL
+                        chain index of the ancestor), pre_energy [events, n], log_mean_w and ess [events, n / deme], beta_now [n]
+                        and `summary` (ppde_amd/anneal.py: summarise).
     ppde_sample_every   0 (default): off. k > 0: the population after every k-th iteration (counted from ppde_sample_burn_in,
                         default 0) is recorded on the device (include/ppde_hip.h, ppde_chains_set_recorder): no host round trip,
                         nothing else of the run changes. With a ladder the recorder follows rung ppde_sample_rung (default 0, the
@@ -76,7 +85,7 @@ import time
 import numpy as np
 import torch
 
-from . import _hip, archive as chain_archive, library as design_library, stats as chain_stats
+from . import _hip, anneal as chain_anneal, archive as chain_archive, library as design_library, stats as chain_stats
 from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
@@ -186,6 +195,55 @@ def check_ladder(betas):
     return np.ascontiguousarray(b)
 
 
+def check_schedule(betas):
+    """An annealing schedule as fp32 [S + 1], or ValueError: 2..4097 finite, positive, non-decreasing inverse temperatures."""
+    b = np.asarray(betas, dtype=np.float32).reshape(-1)
+    if not 2 <= b.size <= 4097:
+        raise ValueError(f"ppde_anneal_betas: a schedule has 1 to 4096 stages (2 to 4097 betas), got {b.size} betas")
+    if not np.isfinite(b).all():
+        raise ValueError("ppde_anneal_betas: every beta must be finite")
+    if not (b > 0).all():
+        raise ValueError("ppde_anneal_betas: every beta must be positive")
+    if not (b[1:] >= b[:-1]).all():
+        raise ValueError("ppde_anneal_betas: the schedule must not decrease")
+    return np.ascontiguousarray(b)
+
+
+def check_annealing(betas, every, deme, reversible, ladder, n_streams):
+    """(schedule fp32 [S + 1] or None, every, deme) of the ppde_anneal_* arguments; ValueError for what the ABI would refuse and
+    can be seen without the population (deme 0 = all chains of the run, resolved there)."""
+    if betas is None or len(betas) == 0:
+        return None, int(every), int(deme)
+    sched = check_schedule(betas)
+    if not reversible:
+        raise ValueError("ppde_anneal_betas: annealing needs ppde_reversible (only there is the law at beta, exp(beta energy)/Z, defined)")
+    if ladder is not None:
+        raise ValueError("ppde_anneal_betas: a schedule and a ladder (ppde_betas) cannot be combined")
+    if int(every) < 1:
+        raise ValueError("ppde_anneal_every must be >= 1")
+    if int(deme) != 0 and not 2 <= int(deme) <= 1024:
+        raise ValueError("ppde_deme must be in 2..1024 (0: all chains of the run)")
+    if int(n_streams) > 1:
+        raise ValueError("ppde_anneal_betas: ppde_streams > 1 is not supported (the selection couples the chains of a deme)")
+    return sched, int(every), int(deme)
+
+
+def check_demes(n_global, deme, num_steps, every, n_stages, shard_starts=(0,)):
+    """The deme size of a run of n_global chains (deme 0: all of them), or ValueError: a size outside 2..1024, a population or a
+    shard boundary that cuts a deme, a run too short for one event."""
+    D = int(n_global) if int(deme) == 0 else int(deme)
+    if not 2 <= D <= 1024:
+        raise ValueError(f"ppde_deme: a deme has 2 to 1024 chains, got {D}" + (" (ppde_deme 0 = all chains of the run)" if int(deme) == 0 else ""))
+    if n_global % D:
+        raise ValueError(f"ppde_deme: the population of {n_global} chains is no multiple of the deme of {D}")
+    for r, start in enumerate(shard_starts):
+        if start % D:
+            raise ValueError(f"ppde_deme: the shard boundary at chain {start} (rank {r} of {len(shard_starts)}) cuts a deme of {D} chains")
+    if min(int(n_stages), int(num_steps) // int(every)) == 0:
+        raise ValueError(f"ppde_anneal_every: no event fits into {int(num_steps)} iterations (every {int(every)})")
+    return D
+
+
 class Chains:
     """Owner of a `ppde_chains` (include/ppde_hip.h)."""
 
@@ -253,6 +311,44 @@ class Chains:
         """uint8 [steps_done + 1, n]: the rung each chain held after every iteration (row 0: the start)."""
         out = np.empty((self.steps_done + 1, self.n), np.uint8)
         _hip.check(self.lib.ppde_chains_tempering_history(self.handle, _hip.ptr(out)))
+        return out
+
+    def set_annealing(self, betas, every=1, deme=None):
+        """Population annealing (include/ppde_hip.h, ppde_chains_set_annealing): a schedule betas[0] <= ... <= betas[S] over demes
+        of `deme` consecutive chains (None: all chains of the object), one stage behind every `every`-th iteration. None or an
+        empty schedule clears it. Needs reversible mode; only before init()."""
+        with torch.cuda.device(self.model.device):
+            if betas is None or len(betas) == 0:
+                _hip.check(self.lib.ppde_chains_set_annealing(self.handle, None))
+                self.anneal = None
+                return
+            sched = np.ascontiguousarray(np.asarray(betas, dtype=np.float32).reshape(-1))
+            D = self.n if deme is None else int(deme)
+            cfg = _hip.AnnealConfig(deme=D, every=int(every), n_stages=int(sched.size) - 1,
+                                    beta=sched.ctypes.data_as(C.POINTER(C.c_float)))
+            _hip.check(self.lib.ppde_chains_set_annealing(self.handle, C.byref(cfg)))
+        self.anneal = dict(betas=sched, every=int(every), deme=D)
+
+    def annealing_shape(self):
+        """(deme size, event capacity, events that have happened)."""
+        d, cap, done = C.c_int32(), C.c_int32(), C.c_int32()
+        _hip.check(self.lib.ppde_chains_annealing_shape(self.handle, C.byref(d), C.byref(cap), C.byref(done)))
+        return d.value, cap.value, done.value
+
+    def annealing_state(self, first=0, count=None):
+        """Events [first, first + count) (default: all so far): parent int32 [count, n] (local index of the ancestor), pre_energy
+        fp32 [count, n], log_mean_w / ess fp64 [count, n / D]; beta fp32 [n] each chain holds now; events = how many have happened."""
+        D, _, done = self.annealing_shape()
+        first = int(first)
+        count = done - first if count is None else int(count)
+        k = max(count, 0)
+        out = dict(parent=np.empty((k, self.n), np.int32), pre_energy=np.empty((k, self.n), np.float32),
+                   log_mean_w=np.empty((k, self.n // D), np.float64), ess=np.empty((k, self.n // D), np.float64),
+                   beta=np.empty(self.n, np.float32))
+        with torch.cuda.device(self.model.device):
+            _hip.check(self.lib.ppde_chains_annealing_read(self.handle, first, count, *[_hip.ptr(out[k_]) for k_ in (
+                "parent", "pre_energy", "log_mean_w", "ess", "beta")]))
+        out["events"] = done
         return out
 
     def set_recorder(self, every, burn_in=0, rung=None, keep_samples=True):
@@ -497,6 +593,10 @@ class PPDE_PAS(BaseSampler):
                 raise ValueError("ppde_swap_every must be >= 0")
             if int(self.n_streams) > 1:
                 raise ValueError("ppde_betas: ppde_streams > 1 is not supported (the swap couples the chains of an ensemble)")
+        self.anneal_betas, self.anneal_every, self.deme = check_annealing(
+            getattr(args, "ppde_anneal_betas", None), getattr(args, "ppde_anneal_every", 1) or 1, getattr(args, "ppde_deme", 0) or 0,
+            self.reversible, self.betas, self.n_streams)
+        self.annealing = None
         self.sample_every = int(getattr(args, "ppde_sample_every", 0) or 0)
         self.sample_burn_in = int(getattr(args, "ppde_sample_burn_in", 0) or 0)
         self.sample_rung = getattr(args, "ppde_sample_rung", None)
@@ -568,6 +668,10 @@ class PPDE_PAS(BaseSampler):
                 if shard_range(n_global, r, ws)[0] % R:
                     raise ValueError(f"ppde_betas: the shard boundary at chain {shard_range(n_global, r, ws)[0]} (rank {r} of {ws}) "
                                      f"cuts an ensemble of {R} chains")
+        D = 0
+        if self.anneal_betas is not None:               # (host only, before any device work)
+            D = check_demes(n_global, self.deme, num_steps, self.anneal_every, self.anneal_betas.size - 1,
+                            [shard_range(n_global, r, ws)[0] for r in range(ws)])
         comm = self.shard and collectives_active()        # (ws > 1, or the one-rank rehearsal of the RCCL path)
         lo, hi = shard_range(n_global, rank, ws)
         n = hi - lo
@@ -600,6 +704,8 @@ class PPDE_PAS(BaseSampler):
             chains.set_reversible(True)
         if R:
             chains.set_tempering(self.betas, self.swap_every)
+        if D:
+            chains.set_annealing(self.anneal_betas, self.anneal_every, D)
         if self.sample_every:
             chains.set_recorder(self.sample_every, self.sample_burn_in, self.sample_rung, not self.sample_counts_only)
         if pair_on:
@@ -616,6 +722,25 @@ class PPDE_PAS(BaseSampler):
         def gathered_ensembles(a):
             # (every shard boundary is a multiple of R, so the shards are equal and the n / R ensembles split the same way)
             return all_gather_rows(torch.as_tensor(a), n_global // R).numpy() if comm and R > 1 else np.asarray(a)
+
+        def gathered_demes(a):
+            # (every shard boundary is a multiple of D: the n / D demes split as the chains do)
+            return all_gather_rows(torch.as_tensor(a), n_global // D, dim=1).numpy() if comm else np.asarray(a)
+
+        an_logged = [0]
+
+        def anneal_log():
+            # one line when events happened since the last log: the latest stage, its beta, the smallest ESS and the slots replaced
+            _, _, ev = chains.annealing_shape()
+            if ev > an_logged[0]:
+                st = chains.annealing_state(an_logged[0], ev - an_logged[0])
+                ess = gathered_demes(st["ess"])
+                replaced = int(sum(int((row != np.arange(n)).sum()) for row in st["parent"]))
+                if comm:
+                    replaced = int(sum_over_ranks(torch.tensor([replaced], dtype=torch.int64))[0])
+                print(f'   # annealing: stage {ev} of {self.anneal_betas.size - 1}, beta = {float(self.anneal_betas[ev]):.6g}, '
+                      f'min ESS = {float(ess.min()):.2f} of {D}, slots replaced = {replaced}')
+                an_logged[0] = ev
 
         def stats_gathered(raw):
             # (per-chain arrays in global chain order, the others summed: every rank ends with the full result)
@@ -644,6 +769,8 @@ class PPDE_PAS(BaseSampler):
                 if R:
                     ts = chains.tempering_state()
                     print(f'   # swaps accepted = {int(gathered_ensembles(ts["swap_accepts"]).sum())} / {int(gathered_ensembles(ts["swap_attempts"]).sum())}')
+                if D:
+                    anneal_log()
                 if self.stats_spec is not None:
                     print(chain_stats.log_line(stats_gathered(chains.stats())))
                 print('', flush=True)
@@ -700,6 +827,16 @@ class PPDE_PAS(BaseSampler):
                 betas=self.betas.copy(),
                 rung_history=all_gather_rows(torch.from_numpy(rh), n_global, dim=1).numpy() if comm else rh,
                 swap_attempts=gathered_ensembles(ts["swap_attempts"]), swap_accepts=gathered_ensembles(ts["swap_accepts"]))
+        self.annealing = None
+        if D:
+            st = chains.annealing_state()
+            parent = all_gather_rows(torch.from_numpy(st["parent"].astype(np.int64) + lo), n_global, dim=1).numpy() if comm \
+                else st["parent"].astype(np.int64) + lo
+            an = dict(betas=self.anneal_betas.copy(), deme=D, every=self.anneal_every, parent=parent,
+                      pre_energy=all_gather_rows(torch.from_numpy(st["pre_energy"]), n_global, dim=1).numpy() if comm else st["pre_energy"],
+                      log_mean_w=gathered_demes(st["log_mean_w"]), ess=gathered_demes(st["ess"]), beta_now=gathered(st["beta"]))
+            an["summary"] = chain_anneal.summarise(an["parent"], an["log_mean_w"], an["ess"], an["betas"])
+            self.annealing = an
         self.samples = None
         if self.sample_every:
             rec = chains.recorded()

@@ -137,6 +137,10 @@ def main(args):
         if tempering is not None:
             for name in ("rung_history", "swap_attempts", "swap_accepts"):
                 np.save(results_path / f"{name}.npy", tempering[name])
+        annealing = getattr(sampler, "annealing", None)
+        if annealing is not None:
+            for name in ("parent", "pre_energy", "log_mean_w", "ess", "betas"):
+                np.save(results_path / f"anneal_{name}.npy", annealing[name])
         samples = getattr(sampler, "samples", None)
         if samples is not None:
             np.save(results_path / "site_counts.npy", samples["site_counts"])
@@ -242,6 +246,16 @@ def build_parser():
     pp.add_argument("--ppde_swap_every", type=int, default=1,
                     help="with --ppde_betas: neighbouring rungs of an ensemble propose to exchange their temperatures every this "
                          "many iterations (0: never)")
+    pp.add_argument("--ppde_anneal_betas", type=lambda t: [float(v) for v in t.split(",") if v.strip()], default=None,
+                    help="population annealing (needs --ppde_reversible; not with --ppde_betas): a non-decreasing schedule of "
+                         "inverse temperatures, e.g. '0.25,0.5,1'. Every chain starts at the first; at each stage every deme is "
+                         "resampled with weights exp(dbeta energy) and moves to the next. Writes anneal_parent.npy [events, n], "
+                         "anneal_pre_energy.npy [events, n], anneal_log_mean_w.npy and anneal_ess.npy [events, demes] and "
+                         "anneal_betas.npy; the periodic log gains a line when a stage was passed")
+    pp.add_argument("--ppde_anneal_every", type=int, default=1, help="with --ppde_anneal_betas: iterations per stage of the schedule")
+    pp.add_argument("--ppde_deme", type=int, default=0,
+                    help="with --ppde_anneal_betas: chains per deme, 2..1024 (0: all chains of the run); consecutive chains form a "
+                         "deme, --n_chains must be a multiple of it")
     pp.add_argument("--ppde_sample_every", type=int, default=0,
                     help="record the population on the device after every this many iterations (0: off): samples.npy, "
                          "sample_energy.npy, sample_fitness.npy, sample_chain.npy and site_counts.npy next to the other results. "
