@@ -46,18 +46,35 @@ static hipError_t dalloc(T** p, size_t count) {
     return hipMalloc((void**)p, count * sizeof(T));
 }
 
+// The one owner of a device allocation in this file: a mode's buffers as members of its struct (Tempering ... MoveStats below), a
+// call's temporaries as locals. Move-only; every way out of a scope (HIPCHK / ARGCHK included) releases what it holds, and
+// assigning over one releases what was there. Reads as the plain pointer wherever one is expected.
+template <typename T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { if (p) hipFree(p); p = o.p; o.p = nullptr; }
+        return *this;
+    }
+    ~DevBuf() { if (p) hipFree(p); }
+    hipError_t alloc(size_t count) {                 // (dalloc's rule: a count of 0 allocates one element)
+        if (p) hipFree(p);
+        return dalloc(&p, count);
+    }
+    hipError_t alloc_zero(size_t count) {
+        const hipError_t e = alloc(count);
+        return e != hipSuccess ? e : hipMemset(p, 0, std::max<size_t>(count, 1) * sizeof(T));
+    }
+    operator T*() const { return p; }
+};
+
 #include "tf_host.h"
 
-// Scope guards for the temporaries of the host layer: every early return (HIPCHK / ARGCHK) releases them.
-struct DevTmp {
-    void* p = nullptr;
-    DevTmp() = default;
-    DevTmp(const DevTmp&) = delete;
-    DevTmp& operator=(const DevTmp&) = delete;
-    ~DevTmp() { if (p) hipFree(p); }
-    template <typename T> hipError_t alloc(size_t count) { T* q = nullptr; hipError_t e = dalloc(&q, count); p = q; return e; }
-    template <typename T> T* as() const { return (T*)p; }
-};
+// Scope guard for the event pairs of the timing hooks: every early return (HIPCHK / ARGCHK) releases them.
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     ~EventPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
@@ -692,9 +709,9 @@ int ppde_model_set_transformer(ppde_model* m, int n_layers, int dim, int heads, 
     if (rc) { delete t; return rc; }
     // wild type's local score (nets.py:188) with the kernels that evaluate every other state
     TfWork wk;
-    DevTmp sc;
-    if ((rc = tf_alloc_work(t, &wk, 1)) == PPDE_OK && sc.alloc<float>(1) != hipSuccess) rc = fail(PPDE_ERR_HIP, "allocation failed");
-    if (rc == PPDE_OK) rc = tf_eval(t, &wk, m->d_wt, m->g.Ls, m->g.sh, 1, sc.as<float>(), nullptr, 0);
+    DevBuf<float> sc;
+    if ((rc = tf_alloc_work(t, &wk, 1)) == PPDE_OK && sc.alloc(1) != hipSuccess) rc = fail(PPDE_ERR_HIP, "allocation failed");
+    if (rc == PPDE_OK) rc = tf_eval(t, &wk, m->d_wt, m->g.Ls, m->g.sh, 1, sc.p, nullptr, 0);
     if (rc == PPDE_OK && hipMemcpy(&t->wt_score, sc.p, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PPDE_ERR_HIP, "copy failed");
     if (rc) { delete t; return rc; }
     m->tf = t;
@@ -709,33 +726,34 @@ int ppde_transformer_time_gemm(int device, int M, int N, int K, int reps, int ep
     // PPDE_TF_TIME_ROTATE=r (diagnostic): r sets of the [M][*] operands used in rotation, so that a launch finds its A rows and
     // second epilogue operand in HBM, as inside an evaluation, and not in the 256 MiB Infinity Cache the previous launch left them in
     static const int rot = []() { const char* e = getenv("PPDE_TF_TIME_ROTATE"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : v > 8 ? 8 : v; }();
-    DevTmp A[8], B, C[8], C2[8], bias;
+    DevBuf<half_t> A[8], B, C[8], C2[8];
+    DevBuf<float> bias;
     for (int r = 0; r < rot; ++r) {
-        HIPCHK(A[r].alloc<half_t>((size_t)M * K)); HIPCHK(C[r].alloc<half_t>((size_t)M * N)); HIPCHK(C2[r].alloc<half_t>((size_t)M * N));
+        HIPCHK(A[r].alloc((size_t)M * K)); HIPCHK(C[r].alloc((size_t)M * N)); HIPCHK(C2[r].alloc((size_t)M * N));
     }
-    HIPCHK(B.alloc<half_t>((size_t)N * K)); HIPCHK(bias.alloc<float>((size_t)N));
+    HIPCHK(B.alloc((size_t)N * K)); HIPCHK(bias.alloc((size_t)N));
     HIPCHK(hipMemset(bias.p, 0, (size_t)N * sizeof(float)));
     hipStream_t s;
     HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     struct SG { hipStream_t s; ~SG() { hipStreamDestroy(s); } } sg{s};
     for (int r = 0; r < rot; ++r) {
-        hipLaunchKernelGGL(tf_fill_random, dim3((unsigned)(((size_t)M * K + 255) / 256)), dim3(256), 0, s, A[r].as<half_t>(), (size_t)M * K, 1u + 16u * r);
+        hipLaunchKernelGGL(tf_fill_random, dim3((unsigned)(((size_t)M * K + 255) / 256)), dim3(256), 0, s, A[r].p, (size_t)M * K, 1u + 16u * r);
         HIPCHK(hipMemsetAsync(C2[r].p, 0, (size_t)M * N * sizeof(half_t), s));
     }
-    hipLaunchKernelGGL(tf_fill_random, dim3((unsigned)(((size_t)N * K + 255) / 256)), dim3(256), 0, s, B.as<half_t>(), (size_t)N * K, 2u);
+    hipLaunchKernelGGL(tf_fill_random, dim3((unsigned)(((size_t)N * K + 255) / 256)), dim3(256), 0, s, B.p, (size_t)N * K, 2u);
     HIPCHK(hipGetLastError());
     EventPair ev;
     HIPCHK(hipEventCreate(&ev.a)); HIPCHK(hipEventCreate(&ev.b));
     int rc = PPDE_OK;
     auto one = [&](int i) {
-        const half_t* a = A[i % rot].as<half_t>();
-        half_t *c = C[i % rot].as<half_t>(), *c2 = C2[i % rot].as<half_t>();
+        const half_t* a = A[i % rot].p;
+        half_t *c = C[i % rot].p, *c2 = C2[i % rot].p;
         switch (epilogue) {
-            case TF_EPI_PLAIN: return tf_gemm<TF_EPI_PLAIN>(s, a, B.as<half_t>(), c, M, N, K);
-            case TF_EPI_BIAS: return tf_gemm<TF_EPI_BIAS>(s, a, B.as<half_t>(), c, M, N, K, bias.as<float>());
-            case TF_EPI_BIAS_RESID: return tf_gemm<TF_EPI_BIAS_RESID>(s, a, B.as<half_t>(), c, M, N, K, bias.as<float>(), c2);
-            case TF_EPI_GELU_BWD: return tf_gemm<TF_EPI_GELU_BWD>(s, a, B.as<half_t>(), c, M, N, K, nullptr, c2);
-            default: return tf_gemm<TF_EPI_BIAS_GELU>(s, a, B.as<half_t>(), c, M, N, K, bias.as<float>(), nullptr, c2);
+            case TF_EPI_PLAIN: return tf_gemm<TF_EPI_PLAIN>(s, a, B.p, c, M, N, K);
+            case TF_EPI_BIAS: return tf_gemm<TF_EPI_BIAS>(s, a, B.p, c, M, N, K, bias.p);
+            case TF_EPI_BIAS_RESID: return tf_gemm<TF_EPI_BIAS_RESID>(s, a, B.p, c, M, N, K, bias.p, c2);
+            case TF_EPI_GELU_BWD: return tf_gemm<TF_EPI_GELU_BWD>(s, a, B.p, c, M, N, K, nullptr, c2);
+            default: return tf_gemm<TF_EPI_BIAS_GELU>(s, a, B.p, c, M, N, K, bias.p, nullptr, c2);
         }
     };
     for (int i = 0; i < 3 && rc == PPDE_OK; ++i) rc = one(i);
@@ -756,15 +774,15 @@ int ppde_transformer_time_gemm(int device, int M, int N, int K, int reps, int ep
 int ppde_transformer_time_fc1_in_situ(ppde_model* m, const uint8_t* idx_dev, int n, float* avg_us, int* launches) {
     ARGCHK(m && m->tf && idx_dev && n >= 1 && avg_us && launches, "bad argument");
     HIPCHK(hipSetDevice(m->device));
-    DevTmp e, fit, grad;
-    HIPCHK(e.alloc<float>((size_t)n)); HIPCHK(fit.alloc<float>((size_t)n)); HIPCHK(grad.alloc<float>((size_t)n * m->g.N));
+    DevBuf<float> e, fit, grad;
+    HIPCHK(e.alloc((size_t)n)); HIPCHK(fit.alloc((size_t)n)); HIPCHK(grad.alloc((size_t)n * m->g.N));
     struct Guard { TfEventList l; ~Guard() { g_tf_fc1_events = nullptr; for (hipEvent_t x : l.ev) if (x) hipEventDestroy(x); } } g;
     g.l.ev.assign((size_t)2 * m->tf->layers, nullptr);
     for (auto& x : g.l.ev) HIPCHK(hipEventCreate(&x));
-    int rc = ppde_energy_grad(m, idx_dev, n, 4, e.as<float>(), fit.as<float>(), grad.as<float>(), nullptr);   // warm (workspace, caches)
+    int rc = ppde_energy_grad(m, idx_dev, n, 4, e.p, fit.p, grad.p, nullptr);   // warm (workspace, caches)
     if (rc) return rc;
     g_tf_fc1_events = &g.l;
-    rc = ppde_energy_grad(m, idx_dev, n, 4, e.as<float>(), fit.as<float>(), grad.as<float>(), nullptr);
+    rc = ppde_energy_grad(m, idx_dev, n, 4, e.p, fit.p, grad.p, nullptr);
     g_tf_fc1_events = nullptr;
     if (rc) return rc;
     HIPCHK(hipDeviceSynchronize());
@@ -828,25 +846,25 @@ static int set_potts_body(ppde_model* m, const float* J, const float* h, int Lp,
     if (rc) return rc;
     const Geom& g = m->g;
     const size_t nJ = (size_t)Lp * Lp * 400;
-    DevTmp raw;
-    HIPCHK(raw.alloc<float>(nJ));
+    DevBuf<float> raw;
+    HIPCHK(raw.alloc(nJ));
     HIPCHK(hipMemcpy(raw.p, J, nJ * sizeof(float), hipMemcpyHostToDevice));
     const size_t nJt = (size_t)Lp * 5 * g.NC * 320;           // float4s
     HIPCHK(dalloc(&m->d_Jt, nJt));
     HIPCHK(dalloc(&m->d_h, (size_t)Lp * 20));
     HIPCHK(hipMemcpy(m->d_h, h, (size_t)Lp * 20 * sizeof(float), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(potts_prepare_kernel, dim3(1024), dim3(256), 0, 0, raw.as<float>(), (float*)m->d_Jt, Lp, g.NC);
+    hipLaunchKernelGGL(potts_prepare_kernel, dim3(1024), dim3(256), 0, 0, raw.p, (float*)m->d_Jt, Lp, g.NC);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     // wt_H = H(wild type) with the same kernel that evaluates every other state
-    DevTmp grad, ep, e;
-    HIPCHK(grad.alloc<float>((size_t)g.N));
-    HIPCHK(ep.alloc<float>((size_t)Lp));
-    HIPCHK(e.alloc<float>(1));
-    EvalTargets t{grad.as<float>(), ep.as<float>(), nullptr, nullptr, 0};
+    DevBuf<float> grad, ep, e;
+    HIPCHK(grad.alloc((size_t)g.N));
+    HIPCHK(ep.alloc((size_t)Lp));
+    HIPCHK(e.alloc(1));
+    EvalTargets t{grad.p, ep.p, nullptr, nullptr, 0};
     rc = launch_potts(m, States{m->d_wt, m->d_wtT, potts_t4_pad(1)}, 1, t, 0);
     if (rc) return rc;
-    hipLaunchKernelGGL(potts_energy_finalize_kernel, dim3(1), dim3(64), 0, 0, ep.as<float>(), Lp, 0.0f, e.as<float>(), 1);
+    hipLaunchKernelGGL(potts_energy_finalize_kernel, dim3(1), dim3(64), 0, 0, ep.p, Lp, 0.0f, e.p, 1);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(&m->wt_H, e.p, sizeof(float), hipMemcpyDeviceToHost));
     return PPDE_OK;
@@ -1157,6 +1175,84 @@ int ppde_energy_grad(ppde_model* m, const uint8_t* idx_dev, int n, int which, fl
 }  // extern "C"
 
 // --------------------------------------------------------------------------------------------
+// The optional modes of a chains object, one struct each: what the mode was set with, its device buffers and the sizes that follow
+// from them. A mode is on while it holds its buffers. ppde_chains_set_* builds a local one and moves it into the object once
+// everything is allocated (a failure on the way leaves the object as it was and the local's destructor releases what there is);
+// assigning {} clears it.
+
+// parallel tempering (ppde_chains_set_tempering)
+struct Tempering {
+    int n_rungs = 0, swap_every = 0;
+    std::vector<float> ladder;                   // beta[0] > beta[1] > ... > 0
+    DevBuf<float> beta;                          // [n]
+    DevBuf<int> rung, slot;                      // [n], [n/R][R]
+    DevBuf<long long> swap_attempts, swap_accepts;   // [n/R][R-1]
+    DevBuf<uint8_t> rung_hist;                   // [T+1][n]
+    bool on() const { return beta.p != nullptr; }
+};
+
+// population annealing (ppde_chains_set_annealing)
+struct Annealing {
+    int D = 0, every = 0, S = 0, cap = 0;        // deme size, iterations per stage, stages, events_cap
+    std::vector<float> sched;                    // beta[0] <= ... <= beta[S]
+    DevBuf<float> sched_dev, beta, pre;          // [S+1], [n], [events_cap][n]
+    DevBuf<int> parent;                          // [events_cap][n]
+    DevBuf<double> lmw, ess;                     // [events_cap][n/D]
+    bool on() const { return sched_dev.p != nullptr; }
+    int events_done(int steps_done) const { return std::min(cap, steps_done / every); }
+};
+
+// recorder (ppde_chains_set_recorder)
+struct Recorder {
+    ppde_record_config cfg{};
+    int rows_cap = 0, slots = 0;
+    DevBuf<uint8_t> idx;                         // [rows_cap][slots][Ls] (keep_samples)
+    DevBuf<float> e, f;                          // [rows_cap][slots]
+    DevBuf<int> chain;
+    DevBuf<unsigned long long> counts;           // [L][20]
+    bool on() const { return counts.p != nullptr; }
+    int rows_done(int steps_done) const { return steps_done > cfg.burn_in ? (steps_done - cfg.burn_in) / cfg.every : 0; }
+};
+
+// pair counts (ppde_chains_set_pair_counts)
+struct PairCounts {
+    std::vector<int32_t> sites;                  // [S] residues, strictly increasing
+    int nt = 0;                                  // tiles per side (pairs.h)
+    DevBuf<int> sites_dev;                       // [nt * PAIR_TS], padded with -1
+    DevBuf<unsigned long long> counts;           // [nt (nt + 1) / 2][PAIR_TILE]
+    bool on() const { return counts.p != nullptr; }
+    size_t tiles() const { return (size_t)nt * ((size_t)nt + 1) / 2; }
+};
+
+// archive (ppde_chains_set_archive)
+struct Archive {
+    int k = 0;
+    DevBuf<uint8_t> idx;                         // [n][K][Ls]
+    DevBuf<float> e, f;                          // [n][K]
+    DevBuf<int> step, count;                     // [n][K], [n]
+    DevBuf<unsigned int> hash;                   // [n][K] fingerprints (archive.h)
+    bool on() const { return idx.p != nullptr; }
+};
+
+// move statistics (ppde_chains_set_stats)
+struct MoveStats {
+    int n = 0, R = 1, M = 0, L = 0, per_site = 0;   // the shape at the set call: chains, R' = max(n_rungs, 1), path lengths, residues
+    DevBuf<long long> cnt;                       // six [n][R'], two [R'][M], then [R'][L] with per_site (counter)
+    DevBuf<uint8_t> prev;                        // [2][n][Ls] the state the last counted iteration left, read and written in turns (stats.h)
+    DevBuf<int> dist;                            // [n]     its mutation count
+    bool on() const { return cnt.p != nullptr; }
+    // the counters in one allocation: k = 0..5 iters, accepts, moved, jump_sum, dist_sum, wt_returns [n][R'];
+    // 6, 7 len_attempts, len_accepts [R'][M]; 8 site_changes [R'][L]
+    size_t cells(int k) const { return k < 6 ? (size_t)n * R : k < 8 ? (size_t)R * M : per_site ? (size_t)R * L : 0; }
+    size_t cells_before(int k) const {
+        size_t o = 0;
+        for (int j = 0; j < k; ++j) o += cells(j);
+        return o;
+    }
+    long long* counter(int k) const { return cnt + cells_before(k); }
+    size_t cells_total() const { return cells_before(9); }
+};
+
 struct ppde_chains {
     ppde_model* m = nullptr;
     int device = 0;                              // (kept here: destroy must not depend on the model still being alive)
@@ -1196,125 +1292,32 @@ struct ppde_chains {
     int n_captures = 0, n_captures_in_run = 0;   // graphs captured in all / inside ppde_chains_run (must stay 0)
     long long n_replayed_steps = 0, n_eager_steps = 0;
     std::vector<void*> allocs;
-    uint32_t* allowed = nullptr;                 // design library [L] (ppde_chains_set_library), owned here; NULL = none
+    DevBuf<uint32_t> allowed;                    // design library [L] (ppde_chains_set_library); NULL = none
     bool reversible = false;                     // ppde_chains_set_reversible: the accept phases run the *_rev kernels
-    // parallel tempering (ppde_chains_set_tempering): owned here, allocated there; n_rungs 0 = none
-    int n_rungs = 0, swap_every = 0;
-    std::vector<float> ladder;                   // beta[0] > beta[1] > ... > 0
-    float* beta = nullptr;                       // [n]
-    int *rung = nullptr, *slot = nullptr;        // [n], [n/R][R]
-    long long *swap_attempts = nullptr, *swap_accepts = nullptr;   // [n/R][R-1]
-    uint8_t* rung_hist = nullptr;                // [T+1][n]
-    // population annealing (ppde_chains_set_annealing): owned here, allocated there; an_on false = none
-    bool an_on = false;
-    int an_D = 0, an_every = 0, an_S = 0, an_cap = 0;   // deme size, iterations per stage, stages, events_cap
-    std::vector<float> an_sched;                 // beta[0] <= ... <= beta[S]
-    float *an_sched_dev = nullptr, *an_beta = nullptr, *an_pre = nullptr;   // [S+1], [n], [events_cap][n]
-    int* an_parent = nullptr;                    // [events_cap][n]
-    double *an_lmw = nullptr, *an_ess = nullptr; // [events_cap][n/D]
-    // recorder (ppde_chains_set_recorder): owned here, allocated there; rec_on false = none
-    bool rec_on = false;
-    ppde_record_config rcfg{};
-    int rec_rows_cap = 0, rec_slots = 0;
-    uint8_t* rec_idx = nullptr;                  // [rows_cap][slots][Ls] (keep_samples)
-    float *rec_e = nullptr, *rec_f = nullptr;    // [rows_cap][slots]
-    int* rec_chain = nullptr;
-    unsigned long long* rec_counts = nullptr;    // [L][20]
-    // pair counts (ppde_chains_set_pair_counts): owned here, allocated there; pair_on false = none
-    bool pair_on = false;
-    std::vector<int32_t> pair_sites;             // [S] residues, strictly increasing
-    int pair_nt = 0;                             // tiles per side (pairs.h)
-    int* pair_sites_dev = nullptr;               // [pair_nt * PAIR_TS], padded with -1
-    unsigned long long* pair_counts = nullptr;   // [pair_nt (pair_nt + 1) / 2][PAIR_TILE]
-    // archive (ppde_chains_set_archive): owned here, allocated there; arch_k 0 = none
-    int arch_k = 0;
-    uint8_t* arch_idx = nullptr;                 // [n][K][Ls]
-    float *arch_e = nullptr, *arch_f = nullptr;  // [n][K]
-    int *arch_step = nullptr, *arch_count = nullptr;   // [n][K], [n]
-    unsigned int* arch_hash = nullptr;           // [n][K] fingerprints (archive.h)
-    // move statistics (ppde_chains_set_stats): owned here, allocated there; stat_on false = none
-    bool stat_on = false;
-    int stat_per_site = 0, stat_R = 1;           // R' = max(n_rungs, 1) at the set call
-    long long* stat_cnt = nullptr;               // six [n][R'], two [R'][M], then [R'][L] with per_site (stat_counter)
-    uint8_t* stat_prev = nullptr;                // [2][n][Ls] the state the last counted iteration left, read and written in turns (stats.h)
-    int* stat_dist = nullptr;                    // [n]     its mutation count
+    Tempering temper;
+    Annealing anneal;
+    Recorder recorder;
+    PairCounts pairs;
+    Archive archive;
+    MoveStats stats;
+
+    ppde_chains() = default;
+    ppde_chains(const ppde_chains&) = delete;
+    ppde_chains& operator=(const ppde_chains&) = delete;
+    // everything the object owns; the members (the modes' buffers) go after the body, with this device current
+    ~ppde_chains() {
+        hipSetDevice(device);
+        for (auto& gs : graphs) {
+            if (gs.exec) hipGraphExecDestroy(gs.exec);
+            if (gs.graph) hipGraphDestroy(gs.graph);
+        }
+        for (void* p : allocs) hipFree(p);
+        delete tfw;
+        if (h_err) hipHostFree(h_err);
+        for (hipStream_t st : streams) if (st) hipStreamDestroy(st);
+        for (hipEvent_t ev : events) if (ev) hipEventDestroy(ev);
+    }
 };
-
-static void free_recorder(ppde_chains* c) {
-    if (c->rec_idx) hipFree(c->rec_idx);
-    if (c->rec_e) hipFree(c->rec_e);
-    if (c->rec_f) hipFree(c->rec_f);
-    if (c->rec_chain) hipFree(c->rec_chain);
-    if (c->rec_counts) hipFree(c->rec_counts);
-    c->rec_idx = nullptr; c->rec_e = c->rec_f = nullptr; c->rec_chain = nullptr; c->rec_counts = nullptr;
-    c->rec_on = false; c->rcfg = ppde_record_config{}; c->rec_rows_cap = 0; c->rec_slots = 0;
-}
-static void free_pairs(ppde_chains* c) {
-    if (c->pair_sites_dev) hipFree(c->pair_sites_dev);
-    if (c->pair_counts) hipFree(c->pair_counts);
-    c->pair_sites_dev = nullptr; c->pair_counts = nullptr;
-    c->pair_on = false; c->pair_sites.clear(); c->pair_nt = 0;
-}
-static void free_archive(ppde_chains* c) {
-    if (c->arch_idx) hipFree(c->arch_idx);
-    if (c->arch_e) hipFree(c->arch_e);
-    if (c->arch_f) hipFree(c->arch_f);
-    if (c->arch_step) hipFree(c->arch_step);
-    if (c->arch_count) hipFree(c->arch_count);
-    if (c->arch_hash) hipFree(c->arch_hash);
-    c->arch_idx = nullptr; c->arch_e = c->arch_f = nullptr; c->arch_step = c->arch_count = nullptr; c->arch_hash = nullptr;
-    c->arch_k = 0;
-}
-static void free_stats(ppde_chains* c) {
-    if (c->stat_cnt) hipFree(c->stat_cnt);
-    if (c->stat_prev) hipFree(c->stat_prev);
-    if (c->stat_dist) hipFree(c->stat_dist);
-    c->stat_cnt = nullptr; c->stat_prev = nullptr; c->stat_dist = nullptr;
-    c->stat_on = false; c->stat_per_site = 0; c->stat_R = 1;
-}
-// the statistics' counters in one allocation: k = 0..5 iters, accepts, moved, jump_sum, dist_sum, wt_returns [n][R'];
-// 6, 7 len_attempts, len_accepts [R'][M]; 8 site_changes [R'][L]
-static size_t stat_cells(const ppde_chains* c, int k) {
-    const size_t R = c->stat_R;
-    return k < 6 ? (size_t)c->n * R : k < 8 ? R * (size_t)c->mu_max : c->stat_per_site ? R * (size_t)c->m->g.L : 0;
-}
-static long long* stat_counter(const ppde_chains* c, int k) {
-    size_t o = 0;
-    for (int j = 0; j < k; ++j) o += stat_cells(c, j);
-    return c->stat_cnt + o;
-}
-static size_t stat_cells_total(const ppde_chains* c) {
-    size_t o = 0;
-    for (int j = 0; j < 9; ++j) o += stat_cells(c, j);
-    return o;
-}
-static size_t pair_tiles(const ppde_chains* c) { return (size_t)c->pair_nt * ((size_t)c->pair_nt + 1) / 2; }
-static int recorder_rows_done(const ppde_chains* c) {
-    return c->steps_done > c->rcfg.burn_in ? (c->steps_done - c->rcfg.burn_in) / c->rcfg.every : 0;
-}
-
-static void free_tempering(ppde_chains* c) {
-    if (c->beta) hipFree(c->beta);
-    if (c->rung) hipFree(c->rung);
-    if (c->slot) hipFree(c->slot);
-    if (c->swap_attempts) hipFree(c->swap_attempts);
-    if (c->swap_accepts) hipFree(c->swap_accepts);
-    if (c->rung_hist) hipFree(c->rung_hist);
-    c->beta = nullptr; c->rung = nullptr; c->slot = nullptr; c->swap_attempts = nullptr; c->swap_accepts = nullptr; c->rung_hist = nullptr;
-    c->n_rungs = 0; c->swap_every = 0; c->ladder.clear();
-}
-
-static void free_annealing(ppde_chains* c) {
-    if (c->an_sched_dev) hipFree(c->an_sched_dev);
-    if (c->an_beta) hipFree(c->an_beta);
-    if (c->an_pre) hipFree(c->an_pre);
-    if (c->an_parent) hipFree(c->an_parent);
-    if (c->an_lmw) hipFree(c->an_lmw);
-    if (c->an_ess) hipFree(c->an_ess);
-    c->an_sched_dev = c->an_beta = c->an_pre = nullptr; c->an_parent = nullptr; c->an_lmw = c->an_ess = nullptr;
-    c->an_on = false; c->an_D = c->an_every = c->an_S = c->an_cap = 0; c->an_sched.clear();
-}
-static int annealing_events_done(const ppde_chains* c) { return std::min(c->an_cap, c->steps_done / c->an_every); }
 
 static PasArgs chain_args(const ppde_chains* c) {
     const ppde_model* m = c->m;
@@ -1339,9 +1342,37 @@ static PasArgs chain_args(const ppde_chains* c) {
     a.err_flag = c->err_flag;
     a.dbg = c->dbg;
     a.allowed = c->allowed;
-    a.beta = c->an_on ? c->an_beta : c->beta; a.rung = c->rung; a.slot = c->slot; a.swap_attempts = c->swap_attempts; a.swap_accepts = c->swap_accepts;
-    a.rung_hist = c->rung_hist; a.n_rungs = c->n_rungs; a.swap_every = c->swap_every;
+    a.beta = c->anneal.on() ? c->anneal.beta.p : c->temper.beta.p; a.rung = c->temper.rung; a.slot = c->temper.slot; a.swap_attempts = c->temper.swap_attempts; a.swap_accepts = c->temper.swap_accepts;
+    a.rung_hist = c->temper.rung_hist; a.n_rungs = c->temper.n_rungs; a.swap_every = c->temper.swap_every;
     return a;
+}
+
+// the recorder's kernel for iteration it_base + it_local (record.h): every chain of the object; reads cur, the history rows, slot
+static int launch_record(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
+    const Geom& g = c->m->g;
+    const Recorder& rec = c->recorder;
+    RecArgs r{};
+    r.it_base = it_base; r.it_local = it_local;
+    r.n = c->n; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
+    r.burn_in = rec.cfg.burn_in; r.every = rec.cfg.every; r.rung = rec.cfg.rung; r.n_rungs = c->temper.n_rungs; r.slots = rec.slots;
+    r.cur = c->cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist; r.slot = c->temper.slot;
+    r.idx = rec.idx; r.energy = rec.e; r.fitness = rec.f; r.chain = rec.chain; r.counts = rec.counts;
+    hipLaunchKernelGGL(k_record, dim3(((g.Ls >> 2) + 3) / 4), dim3(REC_BLOCK), 0, s, r);
+    HIPCHK(hipGetLastError());
+    return PPDE_OK;
+}
+
+// the pair counts' kernel for the same iteration (pairs.h), on the recorder's schedule and slots; reads cur and slot only
+static int launch_pairs(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
+    const Geom& g = c->m->g;
+    const Recorder& rec = c->recorder;
+    PairArgs p{};
+    p.it_base = it_base; p.it_local = it_local; p.Ls = g.Ls; p.sh = g.sh;
+    p.burn_in = rec.cfg.burn_in; p.every = rec.cfg.every; p.rung = rec.cfg.rung; p.n_rungs = c->temper.n_rungs; p.slots = rec.slots;
+    p.nt = c->pairs.nt; p.cur = c->cur; p.slot = c->temper.slot; p.sites = c->pairs.sites_dev; p.counts = c->pairs.counts;
+    hipLaunchKernelGGL(k_record_pairs, dim3((unsigned)c->pairs.tiles()), dim3(PAIR_BLOCK), 0, s, p);
+    HIPCHK(hipGetLastError());
+    return PPDE_OK;
 }
 
 // the archive's kernel for the state after it_base + it_local + 1 completed iterations (archive.h): every chain of the object
@@ -1349,10 +1380,10 @@ static int launch_archive(ppde_chains* c, const int* it_base, int it_local, hipS
     const Geom& g = c->m->g;
     ArchArgs r{};
     r.it_base = it_base; r.it_local = it_local;
-    r.n = c->n; r.K = c->arch_k; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
+    r.n = c->n; r.K = c->archive.k; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
     r.rec = c->rec; r.rec_stride = c->rec_stride; r.cur = c->cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist;
-    r.idx = c->arch_idx; r.energy = c->arch_e; r.fitness = c->arch_f; r.step = c->arch_step; r.count = c->arch_count;
-    r.hash = c->arch_hash;
+    r.idx = c->archive.idx; r.energy = c->archive.e; r.fitness = c->archive.f; r.step = c->archive.step; r.count = c->archive.count;
+    r.hash = c->archive.hash;
     hipLaunchKernelGGL(k_archive, dim3((c->n + ARCH_BLOCK / 64 - 1) / (ARCH_BLOCK / 64)), dim3(ARCH_BLOCK), 0, s, r);
     HIPCHK(hipGetLastError());
     return PPDE_OK;
@@ -1364,16 +1395,17 @@ static int launch_stats(ppde_chains* c, const int* it_base, int it_local, const 
     const Geom& g = c->m->g;
     StatArgs r{};
     r.it_base = it_base; r.it_local = it_local;
-    r.n = c->n; r.R = c->stat_R; r.M = c->mu_max; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
+    r.n = c->n; r.R = c->stats.R; r.M = c->mu_max; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
     r.rng_mode = c->cfg.rng_mode; r.pas = c->cfg.pas_length; r.mu_cap = mu_cap > 0 ? mu_cap : c->mu_max;
     r.key = chain_args(c).key;
-    r.rec = c->rec; r.rec_stride = c->rec_stride; r.cur = c->cur; r.rung_hist = c->n_rungs > 0 ? c->rung_hist : nullptr; r.U_in = U;
-    r.prev = c->stat_prev; r.pdist = c->stat_dist;
-    r.iters = stat_counter(c, 0); r.accepts = stat_counter(c, 1); r.moved = stat_counter(c, 2); r.jump_sum = stat_counter(c, 3);
-    r.dist_sum = stat_counter(c, 4); r.wt_returns = stat_counter(c, 5);
-    r.len_attempts = stat_counter(c, 6); r.len_accepts = stat_counter(c, 7);
-    r.site_changes = c->stat_per_site ? stat_counter(c, 8) : nullptr;
-    r.site_blocks = c->stat_per_site ? ((g.Ls >> 2) + 3) / 4 : 0;
+    r.rec = c->rec; r.rec_stride = c->rec_stride; r.cur = c->cur; r.rung_hist = c->temper.on() ? c->temper.rung_hist.p : nullptr; r.U_in = U;
+    r.prev = c->stats.prev; r.pdist = c->stats.dist;
+    const MoveStats& st = c->stats;
+    r.iters = st.counter(0); r.accepts = st.counter(1); r.moved = st.counter(2); r.jump_sum = st.counter(3);
+    r.dist_sum = st.counter(4); r.wt_returns = st.counter(5);
+    r.len_attempts = st.counter(6); r.len_accepts = st.counter(7);
+    r.site_changes = st.per_site ? st.counter(8) : nullptr;
+    r.site_blocks = c->stats.per_site ? ((g.Ls >> 2) + 3) / 4 : 0;
     const size_t lds = std::max(2 * (size_t)r.M, (size_t)16) * r.R * sizeof(unsigned int);   // (at most 64 x 127 x 2 cells: 65 024 bytes)
     hipLaunchKernelGGL(k_stats, dim3(r.site_blocks + (c->n + STAT_NW - 1) / STAT_NW + 1), dim3(STAT_BLOCK), lds, s, r);
     HIPCHK(hipGetLastError());
@@ -1385,13 +1417,13 @@ static int launch_select(ppde_chains* c, const int* it_base, int it_local, hipSt
     const PasArgs p = chain_args(c);
     AnnealArgs r{};
     r.it_base = it_base; r.it_local = it_local;
-    r.n = c->n; r.D = c->an_D; r.every = c->an_every; r.S = c->an_S;
+    r.n = c->n; r.D = c->anneal.D; r.every = c->anneal.every; r.S = c->anneal.S;
     r.g = p.g; r.n_pad = c->n_pad; r.key = p.key;
     r.rec_stride = c->rec_stride; r.random_chain = c->cfg.random_chain; r.reuse = c->cfg.reuse_grad;
-    r.sched = c->an_sched_dev; r.beta = c->an_beta; r.rec = c->rec; r.cur = c->cur; r.curT = (uint8_t*)c->curT;
+    r.sched = c->anneal.sched_dev; r.beta = c->anneal.beta; r.rec = c->rec; r.cur = c->cur; r.curT = (uint8_t*)c->curT;
     r.grad_cur = c->grad_cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist; r.best_state = c->best_state; r.rtraj = c->rtraj;
-    r.parent = c->an_parent; r.pre_energy = c->an_pre; r.log_mean_w = c->an_lmw; r.ess = c->an_ess;
-    hipLaunchKernelGGL(k_select_plan, dim3(c->n / c->an_D), dim3(ANNEAL_BLOCK), 0, s, r);
+    r.parent = c->anneal.parent; r.pre_energy = c->anneal.pre; r.log_mean_w = c->anneal.lmw; r.ess = c->anneal.ess;
+    hipLaunchKernelGGL(k_select_plan, dim3(c->n / c->anneal.D), dim3(ANNEAL_BLOCK), 0, s, r);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_select_copy, dim3(c->n), dim3(ANNEAL_BLOCK), 0, s, r);
     HIPCHK(hipGetLastError());
@@ -1449,7 +1481,7 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
                         else hipLaunchKernelGGL(K, dim3(n_sub), dim3(PPDE_BLOCK), lds, s, a); } while (0)
     with_gpt([&](auto G) {
         constexpr int GP = decltype(G)::value;
-        if (c->n_rungs > 0 || c->an_on) {            // tempering, annealing (reversible mode): general instantiations, rows and ratio on beta[b] * E
+        if (c->temper.on() || c->anneal.on()) {          // tempering, annealing (reversible mode): general instantiations, rows and ratio on beta[b] * E
             if (which == KP_PROPOSE) {
                 if (a.rng_mode == 0) { if (lib) PPDE_CL((k_propose_temp<GP, true, true>)); else PPDE_CL((k_propose_temp<GP, true, false>)); }
                 else { if (lib) PPDE_CL((k_propose_temp<GP, false, true>)); else PPDE_CL((k_propose_temp<GP, false, false>)); }
@@ -1502,8 +1534,7 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
     PasArgs a = chain_args(c);
     a.b_off = b_off; a.it_base = it_base; a.U_in = U; a.q_in = q; a.u_in = u;
     if (mu_cap > 0) a.mu_cap = mu_cap;              // caller-supplied noise holds only max_u[i] sub-steps of variates
-    const bool temper = c->n_rungs > 0;
-    const bool fuse = c->cfg.reuse_grad && c->cfg.rng_mode == 1 && !temper && !c->an_on;
+    const bool fuse = c->cfg.reuse_grad && c->cfg.rng_mode == 1 && !c->temper.on() && !c->anneal.on();
     int rc;
     for (int i = 0; i < count; ++i) {
         a.it_local = first_local + i;
@@ -1520,41 +1551,17 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
         if (rc) return rc;
         rc = launch_chain_kernel(c, (fuse && i + 1 < count) ? KP_ACCEPT_PROPOSE : KP_ACCEPT, a, n_sub, s);
         if (rc) return rc;
-        if (temper) {                                // (one stream: every chain of the object)
+        // what follows runs on the object's one stream and covers every chain of it: the swap or the selection, then the observers,
+        // which see the population those left
+        if (c->temper.on()) {
             hipLaunchKernelGGL(k_swap, dim3((c->n + 255) / 256), dim3(256), 0, s, a);
             HIPCHK(hipGetLastError());
         }
-        if (c->an_on) {                              // (one stream: every chain of the object; the observers below see the selected population)
-            rc = launch_select(c, it_base, a.it_local, s);
-            if (rc) return rc;
-        }
-        if (c->rec_on) {                             // (one stream: every chain of the object; reads cur, the history rows, slot)
-            const Geom& g = m->g;
-            RecArgs r{};
-            r.it_base = it_base; r.it_local = a.it_local;
-            r.n = c->n; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
-            r.burn_in = c->rcfg.burn_in; r.every = c->rcfg.every; r.rung = c->rcfg.rung; r.n_rungs = c->n_rungs; r.slots = c->rec_slots;
-            r.cur = c->cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist; r.slot = c->slot;
-            r.idx = c->rec_idx; r.energy = c->rec_e; r.fitness = c->rec_f; r.chain = c->rec_chain; r.counts = c->rec_counts;
-            hipLaunchKernelGGL(k_record, dim3(((g.Ls >> 2) + 3) / 4), dim3(REC_BLOCK), 0, s, r);
-            HIPCHK(hipGetLastError());
-            if (c->pair_on) {                        // (the same schedule and slots; reads cur and slot only)
-                PairArgs p{};
-                p.it_base = it_base; p.it_local = a.it_local; p.Ls = g.Ls; p.sh = g.sh;
-                p.burn_in = r.burn_in; p.every = r.every; p.rung = r.rung; p.n_rungs = r.n_rungs; p.slots = r.slots;
-                p.nt = c->pair_nt; p.cur = c->cur; p.slot = c->slot; p.sites = c->pair_sites_dev; p.counts = c->pair_counts;
-                hipLaunchKernelGGL(k_record_pairs, dim3((unsigned)pair_tiles(c)), dim3(PAIR_BLOCK), 0, s, p);
-                HIPCHK(hipGetLastError());
-            }
-        }
-        if (c->arch_k) {                             // (one stream: every chain of the object; reads cur, the history rows, dist_cur)
-            rc = launch_archive(c, it_base, a.it_local, s);
-            if (rc) return rc;
-        }
-        if (c->stat_on) {                            // (one stream: every chain of the object; reads cur, the records, rung_hist)
-            rc = launch_stats(c, it_base, a.it_local, U, mu_cap, s);
-            if (rc) return rc;
-        }
+        if (c->anneal.on() && (rc = launch_select(c, it_base, a.it_local, s))) return rc;
+        if (c->recorder.on() && (rc = launch_record(c, it_base, a.it_local, s))) return rc;
+        if (c->pairs.on() && (rc = launch_pairs(c, it_base, a.it_local, s))) return rc;      // (set only next to a recorder)
+        if (c->archive.on() && (rc = launch_archive(c, it_base, a.it_local, s))) return rc;
+        if (c->stats.on() && (rc = launch_stats(c, it_base, a.it_local, U, mu_cap, s))) return rc;
     }
     return PPDE_OK;
 }
@@ -1696,11 +1703,6 @@ int ppde_chains_create(ppde_chains** out, ppde_model* m, const ppde_chain_config
         c->sub_n.push_back(base + (k < extra ? 1 : 0));
     }
     if (!ok) {
-        for (void* p : c->allocs) hipFree(p);
-        delete c->tfw;
-        if (c->h_err) hipHostFree(c->h_err);
-        for (hipStream_t st : c->streams) if (st) hipStreamDestroy(st);
-        for (hipEvent_t ev : c->events) if (ev) hipEventDestroy(ev);
         delete c;
         return fail(PPDE_ERR_HIP, "device allocation failed while creating chains");
     }
@@ -1713,22 +1715,6 @@ int ppde_chains_destroy(ppde_chains* c) {
     if (!c) return PPDE_OK;
     hipSetDevice(c->device);
     for (hipStream_t st : c->streams) if (st) hipStreamSynchronize(st);
-    for (auto& gs : c->graphs) {
-        if (gs.exec) hipGraphExecDestroy(gs.exec);
-        if (gs.graph) hipGraphDestroy(gs.graph);
-    }
-    for (void* p : c->allocs) hipFree(p);
-    if (c->allowed) hipFree(c->allowed);
-    free_tempering(c);
-    free_annealing(c);
-    free_recorder(c);
-    free_pairs(c);
-    free_archive(c);
-    free_stats(c);
-    delete c->tfw;
-    if (c->h_err) hipHostFree(c->h_err);
-    for (hipStream_t st : c->streams) if (st) hipStreamDestroy(st);
-    for (hipEvent_t ev : c->events) if (ev) hipEventDestroy(ev);
     delete c;
     return PPDE_OK;
 }
@@ -1739,7 +1725,7 @@ int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host) {
     const ppde_model* m = c->m;
     HIPCHK(hipSetDevice(c->device));
     if (!allowed_host) {                            // clear
-        if (c->allowed) { hipFree(c->allowed); c->allowed = nullptr; }
+        c->allowed = {};
         return PPDE_OK;
     }
     int open_in_range = 0;
@@ -1754,15 +1740,11 @@ int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host) {
     if (!open_in_range)
         return fail(PPDE_ERR_INVALID, "design library: no open residue in [min_pos, max_pos] = [" + std::to_string(c->cfg.min_pos) +
                                       ", " + std::to_string(c->cfg.max_pos) + "]");
-    uint32_t* d = nullptr;
-    HIPCHK(dalloc(&d, (size_t)m->L));
+    DevBuf<uint32_t> d;
+    HIPCHK(d.alloc((size_t)m->L));
     hipError_t e = hipMemcpy(d, allowed_host, (size_t)m->L * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(d);
-        return fail(PPDE_ERR_HIP, std::string("design library upload: ") + hipGetErrorString(e));
-    }
-    if (c->allowed) hipFree(c->allowed);
-    c->allowed = d;
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("design library upload: ") + hipGetErrorString(e));
+    c->allowed = std::move(d);
     return PPDE_OK;
 }
 
@@ -1771,10 +1753,10 @@ int ppde_chains_set_reversible(ppde_chains* c, int on) {
     ARGCHK(!c->initialised, "ppde_chains_set_reversible: the mode must be set before ppde_chains_init (its graphs hold the kernel choice)");
     ARGCHK(!(on && c->cfg.paper_results), "ppde_chains_set_reversible: paper_results restarts a rejected chain from its initial state, "
                                           "which is no Metropolis step; the two cannot be combined");
-    ARGCHK(on || c->n_rungs == 0, "ppde_chains_set_reversible: tempering is set and needs reversible mode (clear it with "
+    ARGCHK(on || !c->temper.on(), "ppde_chains_set_reversible: tempering is set and needs reversible mode (clear it with "
                                   "ppde_chains_set_tempering(c, 0, NULL, 0) first)");
-    ARGCHK(on || !c->an_on, "ppde_chains_set_reversible: annealing is set and needs reversible mode (clear it with "
-                            "ppde_chains_set_annealing(c, NULL) first)");
+    ARGCHK(on || !c->anneal.on(), "ppde_chains_set_reversible: annealing is set and needs reversible mode (clear it with "
+                                  "ppde_chains_set_annealing(c, NULL) first)");
     c->reversible = on != 0;
     return PPDE_OK;
 }
@@ -1782,15 +1764,15 @@ int ppde_chains_set_reversible(ppde_chains* c, int on) {
 int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_host, int swap_every) {
     ARGCHK(c, "null argument");
     ARGCHK(!c->initialised, "ppde_chains_set_tempering: the ladder must be set before ppde_chains_init (its graphs hold the kernel choice)");
-    ARGCHK(!(c->rec_on && c->rcfg.rung >= 0), "ppde_chains_set_tempering: a recorder that follows a rung is set; clear it first "
-                                              "(ppde_chains_set_recorder(c, NULL))");
-    ARGCHK(!c->stat_on, "ppde_chains_set_tempering: move statistics are set and were shaped by the ladder there was; clear them first "
-                        "(ppde_chains_set_stats(c, NULL))");
-    ARGCHK(!c->an_on, "ppde_chains_set_tempering: annealing is set (a schedule and a ladder cannot be combined); clear it first "
-                      "(ppde_chains_set_annealing(c, NULL))");
+    ARGCHK(!(c->recorder.on() && c->recorder.cfg.rung >= 0), "ppde_chains_set_tempering: a recorder that follows a rung is set; clear it first "
+                                                             "(ppde_chains_set_recorder(c, NULL))");
+    ARGCHK(!c->stats.on(), "ppde_chains_set_tempering: move statistics are set and were shaped by the ladder there was; clear them first "
+                           "(ppde_chains_set_stats(c, NULL))");
+    ARGCHK(!c->anneal.on(), "ppde_chains_set_tempering: annealing is set (a schedule and a ladder cannot be combined); clear it first "
+                            "(ppde_chains_set_annealing(c, NULL))");
     HIPCHK(hipSetDevice(c->device));
     if (n_rungs == 0 || !beta_host) {               // clear
-        free_tempering(c);
+        c->temper = {};
         return PPDE_OK;
     }
     const int R = n_rungs;
@@ -1813,23 +1795,17 @@ int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_hos
                                                             "the chains of an ensemble)");
     // allocate everything first: a failure leaves the object as it was
     const size_t n = c->n, pairs = (n / R) * (size_t)(R - 1);
-    ppde_chains t;                                   // (a holder for free_tempering on the error path)
-    hipError_t e = dalloc(&t.beta, n);
-    if (e == hipSuccess) e = dalloc(&t.rung, n);
-    if (e == hipSuccess) e = dalloc(&t.slot, n);
-    if (e == hipSuccess) e = dalloc(&t.swap_attempts, pairs);
-    if (e == hipSuccess) e = dalloc(&t.swap_accepts, pairs);
-    if (e == hipSuccess) e = dalloc(&t.rung_hist, ((size_t)c->T + 1) * n);
-    if (e != hipSuccess) {
-        free_tempering(&t);
-        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_tempering: device allocation: ") + hipGetErrorString(e));
-    }
-    free_tempering(c);
-    c->beta = t.beta; c->rung = t.rung; c->slot = t.slot; c->swap_attempts = t.swap_attempts; c->swap_accepts = t.swap_accepts;
-    c->rung_hist = t.rung_hist;
-    t.beta = nullptr; t.rung = nullptr; t.slot = nullptr; t.swap_attempts = nullptr; t.swap_accepts = nullptr; t.rung_hist = nullptr;
-    c->n_rungs = R; c->swap_every = swap_every;
-    c->ladder.assign(beta_host, beta_host + R);
+    Tempering t;
+    t.n_rungs = R; t.swap_every = swap_every;
+    t.ladder.assign(beta_host, beta_host + R);
+    hipError_t e = t.beta.alloc(n);
+    if (e == hipSuccess) e = t.rung.alloc(n);
+    if (e == hipSuccess) e = t.slot.alloc(n);
+    if (e == hipSuccess) e = t.swap_attempts.alloc(pairs);
+    if (e == hipSuccess) e = t.swap_accepts.alloc(pairs);
+    if (e == hipSuccess) e = t.rung_hist.alloc(((size_t)c->T + 1) * n);
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_tempering: device allocation: ") + hipGetErrorString(e));
+    c->temper = std::move(t);
     return PPDE_OK;
 }
 
@@ -1838,12 +1814,12 @@ int ppde_chains_set_annealing(ppde_chains* c, const ppde_anneal_config* cfg) {
     ARGCHK(!c->initialised, "ppde_chains_set_annealing: the schedule must be set before ppde_chains_init (its graphs hold the kernel choice)");
     if (!cfg) {                                     // clear
         HIPCHK(hipSetDevice(c->device));
-        free_annealing(c);
+        c->anneal = {};
         return PPDE_OK;
     }
     ARGCHK(c->reversible, "ppde_chains_set_annealing: annealing needs reversible mode (ppde_chains_set_reversible): only there is the "
                           "law at beta, exp(beta E)/Z, defined");
-    ARGCHK(c->n_rungs == 0, "ppde_chains_set_annealing: tempering is set (a schedule and a ladder cannot be combined); clear it first "
+    ARGCHK(!c->temper.on(), "ppde_chains_set_annealing: tempering is set (a schedule and a ladder cannot be combined); clear it first "
                             "(ppde_chains_set_tempering(c, 0, NULL, 0))");
     ARGCHK(cfg->deme >= 2 && cfg->deme <= ANNEAL_DMAX, "ppde_chains_set_annealing: deme must be in 2..1024");
     ARGCHK(c->n % cfg->deme == 0, "ppde_chains_set_annealing: n_chains must be a multiple of deme (demes of consecutive chains)");
@@ -1867,67 +1843,61 @@ int ppde_chains_set_annealing(ppde_chains* c, const ppde_anneal_config* cfg) {
     HIPCHK(hipSetDevice(c->device));
     // allocate everything first: a failure leaves the object as it was
     const size_t n = c->n, demes = n / cfg->deme;
-    ppde_chains t;                                   // (a holder for free_annealing on the error path)
-    hipError_t e = dalloc(&t.an_sched_dev, (size_t)S + 1);
-    if (e == hipSuccess) e = hipMemcpy(t.an_sched_dev, cfg->beta, ((size_t)S + 1) * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dalloc(&t.an_beta, n);
-    if (e == hipSuccess) e = dalloc(&t.an_pre, (size_t)cap * n);
-    if (e == hipSuccess) e = dalloc(&t.an_parent, (size_t)cap * n);
-    if (e == hipSuccess) e = dalloc(&t.an_lmw, (size_t)cap * demes);
-    if (e == hipSuccess) e = dalloc(&t.an_ess, (size_t)cap * demes);
-    if (e != hipSuccess) {
-        free_annealing(&t);
-        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_annealing: device allocation: ") + hipGetErrorString(e));
-    }
-    free_annealing(c);
-    c->an_sched_dev = t.an_sched_dev; c->an_beta = t.an_beta; c->an_pre = t.an_pre; c->an_parent = t.an_parent;
-    c->an_lmw = t.an_lmw; c->an_ess = t.an_ess;
-    t.an_sched_dev = t.an_beta = t.an_pre = nullptr; t.an_parent = nullptr; t.an_lmw = t.an_ess = nullptr;
-    c->an_on = true; c->an_D = cfg->deme; c->an_every = cfg->every; c->an_S = S; c->an_cap = cap;
-    c->an_sched.assign(cfg->beta, cfg->beta + S + 1);
+    Annealing t;
+    t.D = cfg->deme; t.every = cfg->every; t.S = S; t.cap = cap;
+    t.sched.assign(cfg->beta, cfg->beta + S + 1);
+    hipError_t e = t.sched_dev.alloc((size_t)S + 1);
+    if (e == hipSuccess) e = hipMemcpy(t.sched_dev, cfg->beta, ((size_t)S + 1) * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = t.beta.alloc(n);
+    if (e == hipSuccess) e = t.pre.alloc((size_t)cap * n);
+    if (e == hipSuccess) e = t.parent.alloc((size_t)cap * n);
+    if (e == hipSuccess) e = t.lmw.alloc((size_t)cap * demes);
+    if (e == hipSuccess) e = t.ess.alloc((size_t)cap * demes);
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_annealing: device allocation: ") + hipGetErrorString(e));
+    c->anneal = std::move(t);
     return PPDE_OK;
 }
 
 int ppde_chains_annealing_shape(ppde_chains* c, int32_t* deme, int32_t* events_cap, int32_t* events_done) {
     ARGCHK(c, "null argument");
-    ARGCHK(c->an_on, "ppde_chains_annealing_shape: no annealing was set (ppde_chains_set_annealing)");
-    if (deme) *deme = c->an_D;
-    if (events_cap) *events_cap = c->an_cap;
-    if (events_done) *events_done = annealing_events_done(c);
+    ARGCHK(c->anneal.on(), "ppde_chains_annealing_shape: no annealing was set (ppde_chains_set_annealing)");
+    if (deme) *deme = c->anneal.D;
+    if (events_cap) *events_cap = c->anneal.cap;
+    if (events_done) *events_done = c->anneal.events_done(c->steps_done);
     return PPDE_OK;
 }
 
 int ppde_chains_annealing_read(ppde_chains* c, int first_event, int n_events, int32_t* parent, float* pre_energy, double* log_mean_w,
                                double* ess, float* beta_now) {
-    ARGCHK(c && c->an_on, "ppde_chains_annealing_read: no annealing was set (ppde_chains_set_annealing)");
+    ARGCHK(c && c->anneal.on(), "ppde_chains_annealing_read: no annealing was set (ppde_chains_set_annealing)");
     ARGCHK(c->initialised, "chains not initialised");
-    ARGCHK(first_event >= 0 && n_events >= 0 && first_event + n_events <= annealing_events_done(c),
+    ARGCHK(first_event >= 0 && n_events >= 0 && first_event + n_events <= c->anneal.events_done(c->steps_done),
            "ppde_chains_annealing_read: events beyond those that have happened (ppde_chains_annealing_shape)");
     int rc = ppde_chains_sync(c);
     if (rc) return rc;
-    const size_t n = c->n, demes = n / c->an_D, f = (size_t)first_event, k = (size_t)n_events;
-    if (parent && k) HIPCHK(hipMemcpy(parent, c->an_parent + f * n, k * n * sizeof(int), hipMemcpyDeviceToHost));
-    if (pre_energy && k) HIPCHK(hipMemcpy(pre_energy, c->an_pre + f * n, k * n * sizeof(float), hipMemcpyDeviceToHost));
-    if (log_mean_w && k) HIPCHK(hipMemcpy(log_mean_w, c->an_lmw + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
-    if (ess && k) HIPCHK(hipMemcpy(ess, c->an_ess + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
-    if (beta_now) HIPCHK(hipMemcpy(beta_now, c->an_beta, n * sizeof(float), hipMemcpyDeviceToHost));
+    const size_t n = c->n, demes = n / c->anneal.D, f = (size_t)first_event, k = (size_t)n_events;
+    if (parent && k) HIPCHK(hipMemcpy(parent, c->anneal.parent + f * n, k * n * sizeof(int), hipMemcpyDeviceToHost));
+    if (pre_energy && k) HIPCHK(hipMemcpy(pre_energy, c->anneal.pre + f * n, k * n * sizeof(float), hipMemcpyDeviceToHost));
+    if (log_mean_w && k) HIPCHK(hipMemcpy(log_mean_w, c->anneal.lmw + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
+    if (ess && k) HIPCHK(hipMemcpy(ess, c->anneal.ess + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
+    if (beta_now) HIPCHK(hipMemcpy(beta_now, c->anneal.beta, n * sizeof(float), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 
 // rungs, temperatures, slots and counters of a fresh start: chain g = chain_offset + b starts on rung g % R (chain_offset % R == 0)
 static int init_tempering(ppde_chains* c) {
-    const int R = c->n_rungs;
+    const int R = c->temper.n_rungs;
     const size_t n = c->n, pairs = (n / R) * (size_t)(R - 1);
     std::vector<float> hb(n);
     std::vector<int> hr(n), hs(n);
     std::vector<uint8_t> h8(n);
-    for (size_t b = 0; b < n; ++b) { hr[b] = (int)(b % R); hb[b] = c->ladder[hr[b]]; hs[b] = (int)b; h8[b] = (uint8_t)hr[b]; }
-    HIPCHK(hipMemcpy(c->beta, hb.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->rung, hr.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->slot, hs.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->rung_hist, h8.data(), n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(c->swap_attempts, 0, std::max<size_t>(pairs, 1) * sizeof(long long)));
-    HIPCHK(hipMemset(c->swap_accepts, 0, std::max<size_t>(pairs, 1) * sizeof(long long)));
+    for (size_t b = 0; b < n; ++b) { hr[b] = (int)(b % R); hb[b] = c->temper.ladder[hr[b]]; hs[b] = (int)b; h8[b] = (uint8_t)hr[b]; }
+    HIPCHK(hipMemcpy(c->temper.beta, hb.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->temper.rung, hr.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->temper.slot, hs.data(), n * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(c->temper.rung_hist, h8.data(), n, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(c->temper.swap_attempts, 0, std::max<size_t>(pairs, 1) * sizeof(long long)));
+    HIPCHK(hipMemset(c->temper.swap_accepts, 0, std::max<size_t>(pairs, 1) * sizeof(long long)));
     return PPDE_OK;
 }
 
@@ -1984,26 +1954,26 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(s));
-    if (c->n_rungs > 0) {
+    if (c->temper.on()) {
         rc = init_tempering(c);
         if (rc) return rc;
     }
-    if (c->an_on) {                                 // (a fresh start: every chain at beta[0])
-        const std::vector<float> hb((size_t)n, c->an_sched[0]);
-        HIPCHK(hipMemcpy(c->an_beta, hb.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    if (c->anneal.on()) {                                 // (a fresh start: every chain at beta[0])
+        const std::vector<float> hb((size_t)n, c->anneal.sched[0]);
+        HIPCHK(hipMemcpy(c->anneal.beta, hb.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     }
-    if (c->rec_on) HIPCHK(hipMemset(c->rec_counts, 0, (size_t)g.L * PPDE_A * sizeof(unsigned long long)));   // (a fresh start counts from zero)
-    if (c->pair_on) HIPCHK(hipMemset(c->pair_counts, 0, pair_tiles(c) * PAIR_TILE * sizeof(unsigned long long)));
-    if (c->arch_k) {                                // (a fresh start: an empty archive, then the initial population as t = 0)
-        HIPCHK(hipMemsetAsync(c->arch_count, 0, (size_t)n * sizeof(int), s));
+    if (c->recorder.on()) HIPCHK(hipMemset(c->recorder.counts, 0, (size_t)g.L * PPDE_A * sizeof(unsigned long long)));   // (a fresh start counts from zero)
+    if (c->pairs.on()) HIPCHK(hipMemset(c->pairs.counts, 0, c->pairs.tiles() * PAIR_TILE * sizeof(unsigned long long)));
+    if (c->archive.on()) {                              // (a fresh start: an empty archive, then the initial population as t = 0)
+        HIPCHK(hipMemsetAsync(c->archive.count, 0, (size_t)n * sizeof(int), s));
         rc = launch_archive(c, nullptr, -1, s);
         if (rc) return rc;
         HIPCHK(hipStreamSynchronize(s));
     }
-    if (c->stat_on) {                               // (a fresh start: zero counters, the initial population as the state before iteration 0)
-        HIPCHK(hipMemsetAsync(c->stat_cnt, 0, stat_cells_total(c) * sizeof(long long), s));
-        HIPCHK(hipMemcpyAsync(c->stat_prev, c->cur, (size_t)n * g.Ls, hipMemcpyDeviceToDevice, s));   // (buffer 0: iteration 0 reads it)
-        hipLaunchKernelGGL(k_stats_init, dim3((n + 255) / 256), dim3(256), 0, s, c->rec, c->rec_stride, c->stat_dist, n);
+    if (c->stats.on()) {                               // (a fresh start: zero counters, the initial population as the state before iteration 0)
+        HIPCHK(hipMemsetAsync(c->stats.cnt, 0, c->stats.cells_total() * sizeof(long long), s));
+        HIPCHK(hipMemcpyAsync(c->stats.prev, c->cur, (size_t)n * g.Ls, hipMemcpyDeviceToDevice, s));   // (buffer 0: iteration 0 reads it)
+        hipLaunchKernelGGL(k_stats_init, dim3((n + 255) / 256), dim3(256), 0, s, c->rec, c->rec_stride, c->stats.dist, n);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(s));
     }
@@ -2087,6 +2057,25 @@ int ppde_chains_sync(ppde_chains* c) {
 
 int ppde_chains_steps_done(ppde_chains* c) { return c ? c->steps_done : PPDE_ERR_INVALID; }
 
+// `units` x `per_unit` state rows [Ls] at the device address `src` -> plain rows [L] at the host address `dst`, through a device
+// buffer, a block of whole units at a time (32-bit thread indices: at most 2^30 per launch)
+static int read_state_rows(ppde_chains* c, const uint8_t* src, size_t units, size_t per_unit, uint8_t* dst) {
+    const Geom& g = c->m->g;
+    const size_t L = g.L, per = per_unit * (size_t)std::max(g.L, g.Ls);
+    const size_t block = std::max<size_t>(1, std::min<size_t>(units, ((size_t)1 << 30) / per));
+    DevBuf<uint8_t> tmp;
+    HIPCHK(tmp.alloc(block * per_unit * L));
+    for (size_t u = 0; u < units; u += block) {
+        const int rows_n = (int)(std::min(block, units - u) * per_unit);
+        hipLaunchKernelGGL(k_unpack_state, dim3((rows_n * g.L + 255) / 256), dim3(256), 0, c->stream,
+                           src + u * per_unit * g.Ls, tmp.p, rows_n, g.L, g.Ls, g.sh);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy(dst + u * per_unit * L, tmp.p, (size_t)rows_n * L, hipMemcpyDeviceToHost));
+    }
+    return PPDE_OK;
+}
+
 int ppde_chains_peek(ppde_chains* c, uint8_t* idx, float* energy, float* fitness, uint8_t* accepted, int32_t* dist) {
     ARGCHK(c && c->initialised, "chains not initialised");
     int rc = ppde_chains_sync(c);
@@ -2142,42 +2131,42 @@ int ppde_chains_collect(ppde_chains* c, uint8_t* best_idx, float* best_energy, f
 
 int ppde_chains_tempering_state(ppde_chains* c, int32_t* rung, float* beta, int64_t* swap_attempts, int64_t* swap_accepts) {
     ARGCHK(c && c->initialised, "chains not initialised");
-    ARGCHK(c->n_rungs > 0, "ppde_chains_tempering_state: no tempering was set (ppde_chains_set_tempering)");
+    ARGCHK(c->temper.on(), "ppde_chains_tempering_state: no tempering was set (ppde_chains_set_tempering)");
     int rc = ppde_chains_sync(c);
     if (rc) return rc;
-    const size_t n = c->n, pairs = (n / c->n_rungs) * (size_t)(c->n_rungs - 1);
-    if (rung) HIPCHK(hipMemcpy(rung, c->rung, n * sizeof(int), hipMemcpyDeviceToHost));
-    if (beta) HIPCHK(hipMemcpy(beta, c->beta, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (swap_attempts && pairs) HIPCHK(hipMemcpy(swap_attempts, c->swap_attempts, pairs * sizeof(long long), hipMemcpyDeviceToHost));
-    if (swap_accepts && pairs) HIPCHK(hipMemcpy(swap_accepts, c->swap_accepts, pairs * sizeof(long long), hipMemcpyDeviceToHost));
+    const size_t n = c->n, pairs = (n / c->temper.n_rungs) * (size_t)(c->temper.n_rungs - 1);
+    if (rung) HIPCHK(hipMemcpy(rung, c->temper.rung, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (beta) HIPCHK(hipMemcpy(beta, c->temper.beta, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (swap_attempts && pairs) HIPCHK(hipMemcpy(swap_attempts, c->temper.swap_attempts, pairs * sizeof(long long), hipMemcpyDeviceToHost));
+    if (swap_accepts && pairs) HIPCHK(hipMemcpy(swap_accepts, c->temper.swap_accepts, pairs * sizeof(long long), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 
 int ppde_chains_tempering_history(ppde_chains* c, uint8_t* rung_history) {
     ARGCHK(c && c->initialised && rung_history, "chains not initialised, or null argument");
-    ARGCHK(c->n_rungs > 0, "ppde_chains_tempering_history: no tempering was set (ppde_chains_set_tempering)");
+    ARGCHK(c->temper.on(), "ppde_chains_tempering_history: no tempering was set (ppde_chains_set_tempering)");
     int rc = ppde_chains_sync(c);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(rung_history, c->rung_hist, ((size_t)c->steps_done + 1) * c->n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rung_history, c->temper.rung_hist, ((size_t)c->steps_done + 1) * c->n, hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 
 int ppde_chains_set_recorder(ppde_chains* c, const ppde_record_config* cfg) {
     ARGCHK(c, "null argument");
     ARGCHK(!c->initialised, "ppde_chains_set_recorder: the recorder must be set before ppde_chains_init (its graphs hold the pointers)");
-    ARGCHK(!c->pair_on, "ppde_chains_set_recorder: pair counts are set and follow this recorder's schedule; clear the pair counts first "
-                        "(ppde_chains_set_pair_counts(c, NULL))");
+    ARGCHK(!c->pairs.on(), "ppde_chains_set_recorder: pair counts are set and follow this recorder's schedule; clear the pair counts first "
+                           "(ppde_chains_set_pair_counts(c, NULL))");
     if (!cfg) {                                     // clear
         HIPCHK(hipSetDevice(c->device));
-        free_recorder(c);
+        c->recorder = {};
         return PPDE_OK;
     }
     ARGCHK(cfg->every >= 1, "ppde_chains_set_recorder: every must be >= 1");
     ARGCHK(cfg->burn_in >= 0, "ppde_chains_set_recorder: negative burn_in");
     ARGCHK(cfg->rung >= -1, "ppde_chains_set_recorder: rung must be -1 (every chain) or a rung of the ladder");
     ARGCHK(cfg->keep_samples == 0 || cfg->keep_samples == 1, "ppde_chains_set_recorder: keep_samples must be 0 or 1");
-    ARGCHK(cfg->rung < 0 || c->n_rungs > 0, "ppde_chains_set_recorder: following a rung needs tempering (ppde_chains_set_tempering first)");
-    ARGCHK(cfg->rung < c->n_rungs || cfg->rung < 0, "ppde_chains_set_recorder: rung beyond the ladder");
+    ARGCHK(cfg->rung < 0 || c->temper.on(), "ppde_chains_set_recorder: following a rung needs tempering (ppde_chains_set_tempering first)");
+    ARGCHK(cfg->rung < c->temper.n_rungs || cfg->rung < 0, "ppde_chains_set_recorder: rung beyond the ladder");
     ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_recorder: n_streams > 1 is not supported (the counters have one "
                                                             "owner per launch)");
     const int rows_cap = c->T > cfg->burn_in ? (c->T - cfg->burn_in) / cfg->every : 0;
@@ -2185,69 +2174,48 @@ int ppde_chains_set_recorder(ppde_chains* c, const ppde_record_config* cfg) {
     HIPCHK(hipSetDevice(c->device));
     // allocate everything first: a failure leaves the object as it was
     const Geom& g = c->m->g;
-    const size_t slots = cfg->rung >= 0 ? (size_t)c->n / c->n_rungs : (size_t)c->n, cells = (size_t)rows_cap * slots;
+    const size_t slots = cfg->rung >= 0 ? (size_t)c->n / c->temper.n_rungs : (size_t)c->n, cells = (size_t)rows_cap * slots;
     const size_t n_counts = (size_t)g.L * PPDE_A;
-    ppde_chains t;                                   // (a holder for free_recorder on the error path)
-    hipError_t e = dalloc(&t.rec_counts, n_counts);
-    if (e == hipSuccess) e = hipMemset(t.rec_counts, 0, n_counts * sizeof(unsigned long long));
+    Recorder t;
+    t.cfg = *cfg; t.rows_cap = rows_cap; t.slots = (int)slots;
+    hipError_t e = t.counts.alloc_zero(n_counts);
     if (cfg->keep_samples) {
-        if (e == hipSuccess) e = dalloc(&t.rec_idx, cells * (size_t)g.Ls);
-        if (e == hipSuccess) e = hipMemset(t.rec_idx, 0, cells * (size_t)g.Ls);
-        if (e == hipSuccess) e = dalloc(&t.rec_e, cells);
-        if (e == hipSuccess) e = dalloc(&t.rec_f, cells);
-        if (e == hipSuccess) e = dalloc(&t.rec_chain, cells);
+        if (e == hipSuccess) e = t.idx.alloc_zero(cells * (size_t)g.Ls);
+        if (e == hipSuccess) e = t.e.alloc(cells);
+        if (e == hipSuccess) e = t.f.alloc(cells);
+        if (e == hipSuccess) e = t.chain.alloc(cells);
     }
-    if (e != hipSuccess) {
-        free_recorder(&t);
-        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_recorder: device allocation: ") + hipGetErrorString(e));
-    }
-    free_recorder(c);
-    c->rec_counts = t.rec_counts; c->rec_idx = t.rec_idx; c->rec_e = t.rec_e; c->rec_f = t.rec_f; c->rec_chain = t.rec_chain;
-    t.rec_counts = nullptr; t.rec_idx = nullptr; t.rec_e = t.rec_f = nullptr; t.rec_chain = nullptr;
-    c->rec_on = true; c->rcfg = *cfg; c->rec_rows_cap = rows_cap; c->rec_slots = (int)slots;
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_recorder: device allocation: ") + hipGetErrorString(e));
+    c->recorder = std::move(t);
     return PPDE_OK;
 }
 
 int ppde_chains_recorder_shape(ppde_chains* c, int32_t* rows_done, int32_t* rows_cap, int32_t* slots) {
     ARGCHK(c, "null argument");
-    ARGCHK(c->rec_on, "ppde_chains_recorder_shape: no recorder was set (ppde_chains_set_recorder)");
-    if (rows_done) *rows_done = c->initialised ? recorder_rows_done(c) : 0;
-    if (rows_cap) *rows_cap = c->rec_rows_cap;
-    if (slots) *slots = c->rec_slots;
+    ARGCHK(c->recorder.on(), "ppde_chains_recorder_shape: no recorder was set (ppde_chains_set_recorder)");
+    if (rows_done) *rows_done = c->initialised ? c->recorder.rows_done(c->steps_done) : 0;
+    if (rows_cap) *rows_cap = c->recorder.rows_cap;
+    if (slots) *slots = c->recorder.slots;
     return PPDE_OK;
 }
 
 int ppde_chains_recorder_read(ppde_chains* c, int first_row, int n_rows, uint8_t* idx, float* energy, float* fitness,
                               int32_t* chain, uint64_t* site_counts) {
     ARGCHK(c && c->initialised, "chains not initialised");
-    ARGCHK(c->rec_on, "ppde_chains_recorder_read: no recorder was set (ppde_chains_set_recorder)");
-    ARGCHK(first_row >= 0 && n_rows >= 0 && (long long)first_row + n_rows <= recorder_rows_done(c),
+    ARGCHK(c->recorder.on(), "ppde_chains_recorder_read: no recorder was set (ppde_chains_set_recorder)");
+    ARGCHK(first_row >= 0 && n_rows >= 0 && (long long)first_row + n_rows <= c->recorder.rows_done(c->steps_done),
            "ppde_chains_recorder_read: rows beyond those recorded so far (ppde_chains_recorder_shape: rows_done)");
-    ARGCHK(c->rcfg.keep_samples || !(idx || energy || fitness || chain),
+    ARGCHK(c->recorder.cfg.keep_samples || !(idx || energy || fitness || chain),
            "ppde_chains_recorder_read: the recorder keeps site counts only (keep_samples = 0): pass NULL for the samples");
     int rc = ppde_chains_sync(c);
     if (rc) return rc;
     const Geom& g = c->m->g;
-    const size_t slots = c->rec_slots, cells = (size_t)n_rows * slots, o = (size_t)first_row * slots;
-    if (idx && cells) {
-        // unpack [rows][slots][Ls] -> [rows][slots][L] through a device buffer, a block of rows at a time (32-bit thread indices)
-        const size_t per_row = slots * (size_t)std::max(g.L, g.Ls);
-        const int block = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_rows, ((size_t)1 << 30) / per_row));
-        DevTmp tmp;
-        HIPCHK(tmp.alloc<uint8_t>((size_t)block * slots * g.L));
-        for (int r = 0; r < n_rows; r += block) {
-            const int nr = std::min(block, n_rows - r), rows_n = (int)((size_t)nr * slots);
-            hipLaunchKernelGGL(k_unpack_state, dim3((rows_n * g.L + 255) / 256), dim3(256), 0, c->stream,
-                               c->rec_idx + (o + (size_t)r * slots) * g.Ls, tmp.as<uint8_t>(), rows_n, g.L, g.Ls, g.sh);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipMemcpy(idx + (size_t)r * slots * g.L, tmp.p, (size_t)rows_n * g.L, hipMemcpyDeviceToHost));
-        }
-    }
-    if (energy && cells) HIPCHK(hipMemcpy(energy, c->rec_e + o, cells * sizeof(float), hipMemcpyDeviceToHost));
-    if (fitness && cells) HIPCHK(hipMemcpy(fitness, c->rec_f + o, cells * sizeof(float), hipMemcpyDeviceToHost));
-    if (chain && cells) HIPCHK(hipMemcpy(chain, c->rec_chain + o, cells * sizeof(int), hipMemcpyDeviceToHost));
-    if (site_counts) HIPCHK(hipMemcpy(site_counts, c->rec_counts, (size_t)g.L * PPDE_A * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const size_t slots = c->recorder.slots, cells = (size_t)n_rows * slots, o = (size_t)first_row * slots;
+    if (idx && cells && (rc = read_state_rows(c, c->recorder.idx + o * g.Ls, (size_t)n_rows, slots, idx))) return rc;   // [rows][slots][Ls] -> [L]
+    if (energy && cells) HIPCHK(hipMemcpy(energy, c->recorder.e + o, cells * sizeof(float), hipMemcpyDeviceToHost));
+    if (fitness && cells) HIPCHK(hipMemcpy(fitness, c->recorder.f + o, cells * sizeof(float), hipMemcpyDeviceToHost));
+    if (chain && cells) HIPCHK(hipMemcpy(chain, c->recorder.chain + o, cells * sizeof(int), hipMemcpyDeviceToHost));
+    if (site_counts) HIPCHK(hipMemcpy(site_counts, c->recorder.counts, (size_t)g.L * PPDE_A * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 
@@ -2256,7 +2224,7 @@ int ppde_chains_set_archive(ppde_chains* c, const ppde_archive_config* cfg) {
     ARGCHK(!c->initialised, "ppde_chains_set_archive: the archive must be set before ppde_chains_init (its graphs hold the pointers)");
     if (!cfg) {                                     // clear
         HIPCHK(hipSetDevice(c->device));
-        free_archive(c);
+        c->archive = {};
         return PPDE_OK;
     }
     ARGCHK(cfg->k >= 1 && cfg->k <= ARCH_KMAX, "ppde_chains_set_archive: k must be in 1..32");
@@ -2268,63 +2236,43 @@ int ppde_chains_set_archive(ppde_chains* c, const ppde_archive_config* cfg) {
     // allocate everything first: a failure leaves the object as it was
     const Geom& g = c->m->g;
     const size_t n = c->n, cells = n * (size_t)cfg->k;
-    ppde_chains t;                                   // (a holder for free_archive on the error path)
-    hipError_t e = dalloc(&t.arch_idx, cells * (size_t)g.Ls);
-    if (e == hipSuccess) e = hipMemset(t.arch_idx, 0, cells * (size_t)g.Ls);
-    if (e == hipSuccess) e = dalloc(&t.arch_e, cells);
-    if (e == hipSuccess) e = dalloc(&t.arch_f, cells);
-    if (e == hipSuccess) e = dalloc(&t.arch_step, cells);
-    if (e == hipSuccess) e = dalloc(&t.arch_hash, cells);
-    if (e == hipSuccess) e = dalloc(&t.arch_count, n);
-    if (e == hipSuccess) e = hipMemset(t.arch_count, 0, n * sizeof(int));
-    if (e != hipSuccess) {
-        free_archive(&t);
-        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_archive: device allocation: ") + hipGetErrorString(e));
-    }
-    free_archive(c);
-    c->arch_idx = t.arch_idx; c->arch_e = t.arch_e; c->arch_f = t.arch_f; c->arch_step = t.arch_step; c->arch_count = t.arch_count;
-    c->arch_hash = t.arch_hash;
-    t.arch_idx = nullptr; t.arch_e = t.arch_f = nullptr; t.arch_step = t.arch_count = nullptr; t.arch_hash = nullptr;
-    c->arch_k = cfg->k;
+    Archive t;
+    t.k = cfg->k;
+    hipError_t e = t.idx.alloc_zero(cells * (size_t)g.Ls);
+    if (e == hipSuccess) e = t.e.alloc(cells);
+    if (e == hipSuccess) e = t.f.alloc(cells);
+    if (e == hipSuccess) e = t.step.alloc(cells);
+    if (e == hipSuccess) e = t.hash.alloc(cells);
+    if (e == hipSuccess) e = t.count.alloc_zero(n);
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_archive: device allocation: ") + hipGetErrorString(e));
+    c->archive = std::move(t);
     return PPDE_OK;
 }
 
 int ppde_chains_archive_shape(ppde_chains* c, int32_t* k) {
     ARGCHK(c, "null argument");
-    ARGCHK(c->arch_k, "ppde_chains_archive_shape: no archive was set (ppde_chains_set_archive)");
-    if (k) *k = c->arch_k;
+    ARGCHK(c->archive.on(), "ppde_chains_archive_shape: no archive was set (ppde_chains_set_archive)");
+    if (k) *k = c->archive.k;
     return PPDE_OK;
 }
 
 int ppde_chains_archive_read(ppde_chains* c, uint8_t* idx, float* energy, float* fitness, int32_t* step, int32_t* count) {
-    ARGCHK(c && c->arch_k, "ppde_chains_archive_read: no archive was set (ppde_chains_set_archive)");
+    ARGCHK(c && c->archive.on(), "ppde_chains_archive_read: no archive was set (ppde_chains_set_archive)");
     ARGCHK(c->initialised, "chains not initialised");
     int rc = ppde_chains_sync(c);
     if (rc) return rc;
     const Geom& g = c->m->g;
-    const size_t n = c->n, K = c->arch_k, cells = n * K, L = g.L;
+    const size_t n = c->n, K = c->archive.k, cells = n * K, L = g.L;
     std::vector<float> he(cells), hf(cells);
     std::vector<int> hs(cells), hc(n);
-    HIPCHK(hipMemcpy(he.data(), c->arch_e, cells * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hf.data(), c->arch_f, cells * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hs.data(), c->arch_step, cells * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hc.data(), c->arch_count, n * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(he.data(), c->archive.e, cells * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hf.data(), c->archive.f, cells * sizeof(float), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hs.data(), c->archive.step, cells * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hc.data(), c->archive.count, n * sizeof(int), hipMemcpyDeviceToHost));
     std::vector<uint8_t> hi;
     if (idx) {
-        // unpack [n][K][Ls] -> [n][K][L] through a device buffer, a block of chains at a time (32-bit thread indices)
         hi.resize(cells * L);
-        const size_t per_chain = K * (size_t)std::max(g.L, g.Ls);
-        const size_t block = std::max<size_t>(1, std::min<size_t>(n, ((size_t)1 << 30) / per_chain));
-        DevTmp tmp;
-        HIPCHK(tmp.alloc<uint8_t>(block * K * L));
-        for (size_t b = 0; b < n; b += block) {
-            const int rows_n = (int)(std::min(block, n - b) * K);
-            hipLaunchKernelGGL(k_unpack_state, dim3((rows_n * g.L + 255) / 256), dim3(256), 0, c->stream,
-                               c->arch_idx + b * K * g.Ls, tmp.as<uint8_t>(), rows_n, g.L, g.Ls, g.sh);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipMemcpy(hi.data() + b * K * L, tmp.p, (size_t)rows_n * L, hipMemcpyDeviceToHost));
-        }
+        if ((rc = read_state_rows(c, c->archive.idx, n, K, hi.data()))) return rc;   // [n][K][Ls] -> [n][K][L]
     }
     // each chain's entries by (energy descending, step ascending); the slots beyond count filled
     std::vector<int> order(K);
@@ -2356,7 +2304,7 @@ int ppde_chains_set_stats(ppde_chains* c, const ppde_stats_config* cfg) {
     ARGCHK(!c->initialised, "ppde_chains_set_stats: the statistics must be set before ppde_chains_init (its graphs hold the pointers)");
     if (!cfg) {                                     // clear
         HIPCHK(hipSetDevice(c->device));
-        free_stats(c);
+        c->stats = {};
         return PPDE_OK;
     }
     ARGCHK(cfg->per_site == 0 || cfg->per_site == 1, "ppde_chains_set_stats: per_site must be 0 or 1");
@@ -2365,49 +2313,37 @@ int ppde_chains_set_stats(ppde_chains* c, const ppde_stats_config* cfg) {
     HIPCHK(hipSetDevice(c->device));
     // allocate everything first: a failure leaves the object as it was
     const Geom& g = c->m->g;
-    const size_t n = c->n;
-    ppde_chains t;                                   // (a holder for free_stats on the error path)
-    t.m = c->m; t.n = c->n; t.mu_max = c->mu_max;
-    t.stat_R = std::max(c->n_rungs, 1); t.stat_per_site = cfg->per_site;
-    const size_t cells = stat_cells_total(&t);
-    hipError_t e = dalloc(&t.stat_cnt, cells);
-    if (e == hipSuccess) e = hipMemset(t.stat_cnt, 0, cells * sizeof(long long));
-    if (e == hipSuccess) e = dalloc(&t.stat_prev, 2 * n * (size_t)g.Ls);
-    if (e == hipSuccess) e = hipMemset(t.stat_prev, 0, 2 * n * (size_t)g.Ls);
-    if (e == hipSuccess) e = dalloc(&t.stat_dist, n);
-    if (e == hipSuccess) e = hipMemset(t.stat_dist, 0, n * sizeof(int));
-    if (e != hipSuccess) {
-        free_stats(&t);
-        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_stats: device allocation: ") + hipGetErrorString(e));
-    }
-    free_stats(c);
-    c->stat_cnt = t.stat_cnt; c->stat_prev = t.stat_prev; c->stat_dist = t.stat_dist;
-    t.stat_cnt = nullptr; t.stat_prev = nullptr; t.stat_dist = nullptr;
-    c->stat_on = true; c->stat_per_site = cfg->per_site; c->stat_R = t.stat_R;
+    MoveStats t;
+    t.n = c->n; t.R = std::max(c->temper.n_rungs, 1); t.M = c->mu_max; t.L = g.L; t.per_site = cfg->per_site;
+    hipError_t e = t.cnt.alloc_zero(t.cells_total());
+    if (e == hipSuccess) e = t.prev.alloc_zero(2 * (size_t)t.n * g.Ls);
+    if (e == hipSuccess) e = t.dist.alloc_zero((size_t)t.n);
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_stats: device allocation: ") + hipGetErrorString(e));
+    c->stats = std::move(t);
     return PPDE_OK;
 }
 
 int ppde_chains_stats_shape(ppde_chains* c, int32_t* n_rungs, int32_t* n_lengths, int32_t* per_site) {
     ARGCHK(c, "null argument");
-    ARGCHK(c->stat_on, "ppde_chains_stats_shape: no statistics were set (ppde_chains_set_stats)");
-    if (n_rungs) *n_rungs = c->stat_R;
+    ARGCHK(c->stats.on(), "ppde_chains_stats_shape: no statistics were set (ppde_chains_set_stats)");
+    if (n_rungs) *n_rungs = c->stats.R;
     if (n_lengths) *n_lengths = c->mu_max;
-    if (per_site) *per_site = c->stat_per_site;
+    if (per_site) *per_site = c->stats.per_site;
     return PPDE_OK;
 }
 
 int ppde_chains_stats_read(ppde_chains* c, int64_t* iters, int64_t* accepts, int64_t* moved, int64_t* jump_sum, int64_t* dist_sum,
                            int64_t* wt_returns, int64_t* len_attempts, int64_t* len_accepts, int64_t* site_changes) {
-    ARGCHK(c && c->stat_on, "ppde_chains_stats_read: no statistics were set (ppde_chains_set_stats)");
+    ARGCHK(c && c->stats.on(), "ppde_chains_stats_read: no statistics were set (ppde_chains_set_stats)");
     ARGCHK(c->initialised, "chains not initialised");
-    ARGCHK(c->stat_per_site || !site_changes, "ppde_chains_stats_read: the statistics keep no per-site counts (per_site = 0): pass NULL "
-                                              "for site_changes");
+    ARGCHK(c->stats.per_site || !site_changes, "ppde_chains_stats_read: the statistics keep no per-site counts (per_site = 0): pass NULL "
+                                               "for site_changes");
     int rc = ppde_chains_sync(c);
     if (rc) return rc;
     int64_t* out[9] = {iters, accepts, moved, jump_sum, dist_sum, wt_returns, len_attempts, len_accepts, site_changes};
     for (int k = 0; k < 9; ++k)
-        if (out[k] && stat_cells(c, k))
-            HIPCHK(hipMemcpy(out[k], stat_counter(c, k), stat_cells(c, k) * sizeof(long long), hipMemcpyDeviceToHost));
+        if (out[k] && c->stats.cells(k))
+            HIPCHK(hipMemcpy(out[k], c->stats.counter(k), c->stats.cells(k) * sizeof(long long), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 
@@ -2416,11 +2352,11 @@ int ppde_chains_set_pair_counts(ppde_chains* c, const ppde_pair_config* cfg) {
     ARGCHK(!c->initialised, "ppde_chains_set_pair_counts: pair counts must be set before ppde_chains_init (its graphs hold the pointers)");
     if (!cfg) {                                     // clear
         HIPCHK(hipSetDevice(c->device));
-        free_pairs(c);
+        c->pairs = {};
         return PPDE_OK;
     }
-    ARGCHK(c->rec_on, "ppde_chains_set_pair_counts: no recorder was set (pair counts follow its schedule and slots: "
-                      "ppde_chains_set_recorder first)");
+    ARGCHK(c->recorder.on(), "ppde_chains_set_pair_counts: no recorder was set (pair counts follow its schedule and slots: "
+                             "ppde_chains_set_recorder first)");
     const int L = c->m->g.L;
     ARGCHK(cfg->n_sites >= 0 && cfg->n_sites <= L, "ppde_chains_set_pair_counts: n_sites must be in 0..L (0: every residue)");
     ARGCHK(cfg->n_sites == 0 || cfg->sites, "ppde_chains_set_pair_counts: n_sites > 0 needs a site list");
@@ -2436,49 +2372,41 @@ int ppde_chains_set_pair_counts(ppde_chains* c, const ppde_pair_config* cfg) {
     }
     HIPCHK(hipSetDevice(c->device));
     // allocate everything first: a failure leaves the object as it was
-    ppde_chains t;                                   // (a holder for free_pairs on the error path)
-    t.pair_nt = (S + PAIR_TS - 1) / PAIR_TS;
-    std::vector<int32_t> padded((size_t)t.pair_nt * PAIR_TS, -1);
+    PairCounts t;
+    t.nt = (S + PAIR_TS - 1) / PAIR_TS;
+    std::vector<int32_t> padded((size_t)t.nt * PAIR_TS, -1);
     for (int i = 0; i < S; ++i) padded[i] = cfg->n_sites ? cfg->sites[i] : i;
-    const size_t n_counts = pair_tiles(&t) * PAIR_TILE;
-    hipError_t e = dalloc(&t.pair_sites_dev, padded.size());
-    if (e == hipSuccess) e = hipMemcpy(t.pair_sites_dev, padded.data(), padded.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dalloc(&t.pair_counts, n_counts);
-    if (e == hipSuccess) e = hipMemset(t.pair_counts, 0, n_counts * sizeof(unsigned long long));
-    if (e != hipSuccess) {
-        free_pairs(&t);
-        return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_pair_counts: device allocation: ") + hipGetErrorString(e));
-    }
-    free_pairs(c);
-    c->pair_sites_dev = t.pair_sites_dev; c->pair_counts = t.pair_counts; c->pair_nt = t.pair_nt;
-    t.pair_sites_dev = nullptr; t.pair_counts = nullptr;
-    c->pair_sites.assign(padded.begin(), padded.begin() + S);
-    c->pair_on = true;
+    t.sites.assign(padded.begin(), padded.begin() + S);
+    hipError_t e = t.sites_dev.alloc(padded.size());
+    if (e == hipSuccess) e = hipMemcpy(t.sites_dev, padded.data(), padded.size() * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = t.counts.alloc_zero(t.tiles() * PAIR_TILE);
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_pair_counts: device allocation: ") + hipGetErrorString(e));
+    c->pairs = std::move(t);
     return PPDE_OK;
 }
 
 int ppde_chains_pair_counts_shape(ppde_chains* c, int32_t* n_sites, int32_t* sites) {
     ARGCHK(c, "null argument");
-    ARGCHK(c->pair_on, "ppde_chains_pair_counts_shape: no pair counts were set (ppde_chains_set_pair_counts)");
-    if (n_sites) *n_sites = (int32_t)c->pair_sites.size();
-    if (sites) std::copy(c->pair_sites.begin(), c->pair_sites.end(), sites);
+    ARGCHK(c->pairs.on(), "ppde_chains_pair_counts_shape: no pair counts were set (ppde_chains_set_pair_counts)");
+    if (n_sites) *n_sites = (int32_t)c->pairs.sites.size();
+    if (sites) std::copy(c->pairs.sites.begin(), c->pairs.sites.end(), sites);
     return PPDE_OK;
 }
 
 int ppde_chains_pair_counts_read(ppde_chains* c, uint64_t* pair_counts) {
     ARGCHK(c && c->initialised, "chains not initialised");
-    ARGCHK(c->pair_on, "ppde_chains_pair_counts_read: no pair counts were set (ppde_chains_set_pair_counts)");
+    ARGCHK(c->pairs.on(), "ppde_chains_pair_counts_read: no pair counts were set (ppde_chains_set_pair_counts)");
     int rc = ppde_chains_sync(c);
     if (rc) return rc;
     if (!pair_counts) return PPDE_OK;
     // the device keeps the upper block triangle, tile by tile (pairs.h): one row of tiles at a time to the host, mirrored here
-    const size_t S = c->pair_sites.size(), W = S * PPDE_A;
-    const int nt = c->pair_nt;
+    const size_t S = c->pairs.sites.size(), W = S * PPDE_A;
+    const int nt = c->pairs.nt;
     std::vector<unsigned long long> rowbuf((size_t)nt * PAIR_TILE);
     size_t first = 0;
     for (int ti = 0; ti < nt; ++ti) {
         const size_t tiles = (size_t)(nt - ti);
-        HIPCHK(hipMemcpy(rowbuf.data(), c->pair_counts + first * PAIR_TILE, tiles * PAIR_TILE * sizeof(unsigned long long),
+        HIPCHK(hipMemcpy(rowbuf.data(), c->pairs.counts + first * PAIR_TILE, tiles * PAIR_TILE * sizeof(unsigned long long),
                          hipMemcpyDeviceToHost));
         first += tiles;
         for (int tj = ti; tj < nt; ++tj)

@@ -3,31 +3,9 @@
 // RNG modes (eager, graph replay, several streams), peek / collect / trace, argument errors, and — with
 // `driver sweep` — the same sequence once per fallible runtime call with that call failing, so every clean-up path
 // of the host layer runs. Numbers are meaningless here (kernels do not run); memory errors and leaks are the point.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <random>
-#include <vector>
-#include "../../include/ppde_hip.h"
-
-extern "C" long hipmock_calls();
-extern "C" void hipmock_rearm(long fail_at);
-extern "C" long hipmock_launches();
-extern "C" long hipmock_allocs();
-extern "C" long hipmock_writes();
+#include "walk.h"
 
 namespace {
-std::mt19937 rng(7);
-std::vector<float> rnd(size_t n, float s = 0.1f) {
-    std::normal_distribution<float> d(0.f, s);
-    std::vector<float> v(n);
-    for (auto& x : v) x = d(rng);
-    return v;
-}
-struct Ptrs { std::vector<std::vector<float>> store; std::vector<const float*> p; };
-Ptrs many(int count, size_t n) { Ptrs r; for (int i = 0; i < count; ++i) r.store.push_back(rnd(n)); for (auto& v : r.store) r.p.push_back(v.data()); return r; }
-
-#define TRY(x) do { int rc_ = (x); if (rc_ != PPDE_OK) { if (verbose) fprintf(stderr, "  %s -> %d (%s)\n", #x, rc_, ppde_last_error()); status = rc_; goto done; } } while (0)
 #define EXPECT_FAIL(x) do { if ((x) == PPDE_OK) { fprintf(stderr, "expected an error from %s\n", #x); return 99; } } while (0)
 
 // the full sequence; returns the first non-OK status (after releasing everything it created)
@@ -190,12 +168,9 @@ int argument_errors() {
 // The shape limits of include/ppde_hip.h that need no kernel result: each refusal is PPDE_ERR_INVALID with a message, happens before
 // the object is touched -- across the refused call the runtime sees no kernel launch, no allocation and no copy or fill -- and leaves
 // it usable (the mock runs no kernel, so "usable" = the next valid call succeeds and nothing leaks).
-#define EXPECT_INVALID(x) do { const long l_ = hipmock_launches(), a_ = hipmock_allocs(), w_ = hipmock_writes(); int rc_ = (x); \
-    if (rc_ != PPDE_ERR_INVALID || !ppde_last_error()[0]) { \
-        fprintf(stderr, "expected PPDE_ERR_INVALID with a message from %s, got %d (%s)\n", #x, rc_, ppde_last_error()); return 99; } \
-    if (hipmock_launches() != l_ || hipmock_allocs() != a_ || hipmock_writes() != w_) { \
-        fprintf(stderr, "%s was refused after %ld launches, %ld allocations, %ld copies / fills\n", #x, hipmock_launches() - l_, \
-                hipmock_allocs() - a_, hipmock_writes() - w_); return 98; } } while (0)
+// (no clean-up label here: a failed expectation returns its code)
+#undef WALK_FAIL
+#define WALK_FAIL(code) return (code)
 int set_cnn_of(ppde_model* m, int n_nets, int C, int K, int F) {
     const int k = n_nets > 0 ? n_nets : 1, c = C > 0 ? C : 1, kk = K > 0 ? K : 1, f = F > 0 ? F : 1;
     auto cw = many(k, (size_t)c * 20 * kk), cb = many(k, c), lw = many(k, (size_t)f * c), lb = many(k, f), dw = many(k, f), db = many(k, 1);
@@ -274,33 +249,21 @@ int shape_limits() {
     ppde_model_destroy(m);
     return 0;
 }
+
+// the shape of a walk for run_walks: this driver keeps its refusals in argument_errors and shape_limits, so both 48-residue walks are
+// the plain sequence; the long one (chunked CNN path, ring Potts kernel) runs without the transformer expert
+int walk(int L, int Lp, int win, bool verbose, bool) { return sequence(L, Lp, win, L < 100, verbose); }
+int more(bool verbose) {
+    int rc = sequence(40, 40, 0, true, verbose, 96, 4);                              // head width 24: rows padded 96 -> 128
+    if (rc != PPDE_OK) { fprintf(stderr, "head-width-24 run failed\n"); return rc; }
+    rc = sequence(40, 40, 0, true, verbose, 256, 4);                                 // head width 64
+    if (rc != PPDE_OK) { fprintf(stderr, "head-width-64 run failed\n"); return rc; }
+    if ((rc = argument_errors())) { fprintf(stderr, "argument_errors: %d\n", rc); return rc; }
+    if ((rc = shape_limits())) fprintf(stderr, "shape_limits: %d\n", rc);
+    return rc;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
-    const bool sweep = argc > 1 && !strcmp(argv[1], "sweep");
-    hipmock_rearm(-1);
-    int rc = sequence(48, 40, 4, true, true);
-    if (rc != PPDE_OK) { fprintf(stderr, "clean sequence failed: %d (%s)\n", rc, ppde_last_error()); return 1; }
-    const long fallible = hipmock_calls();
-    rc = sequence(110, 100, 2, false, true);                                         // chunked CNN path (L >= 100), ring Potts kernel
-    if (rc != PPDE_OK) { fprintf(stderr, "long-sequence run failed: %d (%s)\n", rc, ppde_last_error()); return 1; }
-    rc = sequence(40, 40, 0, true, true, 96, 4);                                      // head width 24: rows padded 96 -> 128
-    if (rc != PPDE_OK) { fprintf(stderr, "head-width-24 run failed: %d (%s)\n", rc, ppde_last_error()); return 1; }
-    rc = sequence(40, 40, 0, true, true, 256, 4);                                     // head width 64
-    if (rc != PPDE_OK) { fprintf(stderr, "head-width-64 run failed: %d (%s)\n", rc, ppde_last_error()); return 1; }
-    rc = argument_errors();
-    if (rc) { fprintf(stderr, "argument_errors: %d\n", rc); return 1; }
-    rc = shape_limits();
-    if (rc) { fprintf(stderr, "shape_limits: %d\n", rc); return 1; }
-    long failures = 0;
-    if (sweep) {
-        for (long k = 1; k <= fallible; ++k) {
-            rng.seed(7);
-            hipmock_rearm(k);
-            if (sequence(48, 40, 4, true, false) != PPDE_OK) ++failures;              // must fail cleanly: the sanitizer reports anything left behind
-        }
-        hipmock_rearm(-1);
-    }
-    printf("hostcheck ok: %ld fallible runtime calls per sequence, %ld injected failures handled\n", fallible, failures);
-    return 0;
+    return run_walks(argc, argv, "hostcheck ok: %ld fallible runtime calls per sequence, %ld injected failures handled\n", walk, more);
 }

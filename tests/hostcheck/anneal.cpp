@@ -4,39 +4,10 @@
 // destroy on both RNG modes and both gradient policies (eager and from captured graphs), and -- with `driver sweep` -- the same walk
 // once per fallible runtime call with that call failing, so every clean-up path runs. Kernels do not run here: numbers mean
 // nothing, memory errors and leaks are the point.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <cmath>
-#include <random>
-#include <vector>
-#include "ppde_hip.h"
-
-extern "C" long hipmock_calls();
-extern "C" void hipmock_rearm(long fail_at);
-extern "C" long hipmock_launches();
-extern "C" long hipmock_allocs();
-extern "C" long hipmock_writes();
+#include "walk.h"
 
 namespace {
-std::mt19937 rng(7);
-std::vector<float> rnd(size_t n, float s = 0.1f) {
-    std::normal_distribution<float> d(0.f, s);
-    std::vector<float> v(n);
-    for (auto& x : v) x = d(rng);
-    return v;
-}
-struct Ptrs { std::vector<std::vector<float>> store; std::vector<const float*> p; };
-Ptrs many(int count, size_t n) { Ptrs r; for (int i = 0; i < count; ++i) r.store.push_back(rnd(n)); for (auto& v : r.store) r.p.push_back(v.data()); return r; }
 ppde_anneal_config acfg(int deme, int every, int stages, const float* beta) { ppde_anneal_config a{}; a.deme = deme; a.every = every; a.n_stages = stages; a.beta = beta; return a; }
-
-#define TRY(x) do { int rc_ = (x); if (rc_ != PPDE_OK) { if (verbose) fprintf(stderr, "  %s -> %d (%s)\n", #x, rc_, ppde_last_error()); status = rc_; goto done; } } while (0)
-// a refusal: PPDE_ERR_INVALID with a message, and the runtime sees no launch, allocation, copy or fill across the call
-#define EXPECT_INVALID(x) do { const long l_ = hipmock_launches(), a_ = hipmock_allocs(), w_ = hipmock_writes(); int rc_ = (x); \
-    if (rc_ != PPDE_ERR_INVALID || !ppde_last_error()[0]) { \
-        fprintf(stderr, "expected PPDE_ERR_INVALID with a message from %s, got %d (%s)\n", #x, rc_, ppde_last_error()); status = 99; goto done; } \
-    if (hipmock_launches() != l_ || hipmock_allocs() != a_ || hipmock_writes() != w_) { \
-        fprintf(stderr, "%s was refused after touching the runtime\n", #x); status = 98; goto done; } } while (0)
 
 // the walk; returns the first non-OK status after releasing everything it created. `refusals`: also the calls that must be refused
 // (left out of the failure sweep, where an injected failure in front of them would change what they answer)
@@ -213,25 +184,5 @@ done:
 }  // namespace
 
 int main(int argc, char** argv) {
-    const bool sweep = argc > 1 && !strcmp(argv[1], "sweep");
-    hipmock_rearm(-1);
-    int rc = walk(48, 40, 4, true, false);
-    if (rc != PPDE_OK) { fprintf(stderr, "clean walk failed: %d (%s)\n", rc, ppde_last_error()); return 1; }
-    const long fallible = hipmock_calls();
-    rng.seed(7);
-    rc = walk(48, 40, 4, true, true);                                                // the same with the refusals in it
-    if (rc != PPDE_OK) { fprintf(stderr, "walk with refusals failed: %d (%s)\n", rc, ppde_last_error()); return 1; }
-    rc = walk(110, 100, 2, true, true);                                              // two logit groups per thread, chunked CNN
-    if (rc != PPDE_OK) { fprintf(stderr, "long-sequence walk failed: %d (%s)\n", rc, ppde_last_error()); return 1; }
-    long failures = 0;
-    if (sweep) {
-        for (long k = 1; k <= fallible; ++k) {
-            rng.seed(7);
-            hipmock_rearm(k);
-            if (walk(48, 40, 4, false, false) != PPDE_OK) ++failures;                // must fail cleanly: the sanitizer reports anything left behind
-        }
-        hipmock_rearm(-1);
-    }
-    printf("hostcheck anneal ok: %ld fallible runtime calls per walk, %ld injected failures handled\n", fallible, failures);
-    return 0;
+    return run_walks(argc, argv, "hostcheck anneal ok: %ld fallible runtime calls per walk, %ld injected failures handled\n", walk);
 }

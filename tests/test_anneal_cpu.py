@@ -343,15 +343,15 @@ def test_summarise_reads_a_hand_made_genealogy():
 
 # ------------------------------------------------------------------------------------------------ the host layer
 def test_host_layer_of_annealing_under_address_sanitizer():
-    """tests/hostcheck_anneal/: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
+    """tests/hostcheck/anneal.cpp: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
     tests/hostcheck/, compiled with AddressSanitizer + LeakSanitizer: every refusal, then create -> set_reversible -> set_annealing
     -> init -> run -> annealing_shape / read -> destroy on both RNG modes and both gradient policies, then the walk once per
     fallible runtime call with that call failing. Any leak or out-of-bounds access fails the run."""
     import os
     import re
     import subprocess
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck_anneal", "build_and_run.sh")
-    r = subprocess.run(["bash", script, "sweep"], capture_output=True, text=True, timeout=600)
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck", "build_and_run.sh")
+    r = subprocess.run(["bash", script, "anneal", "sweep"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"hostcheck anneal ok: (\d+) fallible runtime calls per walk, (\d+) injected failures handled", r.stdout)
     assert m and int(m.group(1)) > 100 and m.group(1) == m.group(2), r.stdout

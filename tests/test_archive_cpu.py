@@ -1,6 +1,6 @@
 """The archive without a GPU: the online rule on hand-made histories, its agreement with the offline "K best distinct states" when
 energy is a function of the state, ppde_amd.archive.merge, what PPDE_PAS refuses before any device work, the driver's flag, the
-host side of the C ABI as a stand-alone program under AddressSanitizer (tests/hostcheck_archive/), and the conditions the GPU
+host side of the C ABI as a stand-alone program under AddressSanitizer (tests/hostcheck/archive.cpp), and the conditions the GPU
 tests of tests/test_archive_gpu.py stand on, asserted on CPU reference runs of the same configurations.
 
 Measured on those references (16 chains, T = 130, pas_length 2, Philox seed 202, helpers_archive.events):
@@ -184,12 +184,12 @@ def test_cli_flag_parses_into_the_sampler_argument():
 
 # ------------------------------------------------------------------------------------------------ the host layer
 def test_host_layer_of_the_archive_under_address_sanitizer():
-    """tests/hostcheck_archive/: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
+    """tests/hostcheck/archive.cpp: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
     tests/hostcheck/, compiled with AddressSanitizer + LeakSanitizer: every refusal, then set, shape, init, run, read, a second
     init, clear and destroy, then the walk once per fallible runtime call with that call failing. Any leak or out-of-bounds access
     fails the run."""
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck_archive", "build_and_run.sh")
-    r = subprocess.run(["bash", script, "sweep"], capture_output=True, text=True, timeout=600)
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck", "build_and_run.sh")
+    r = subprocess.run(["bash", script, "archive", "sweep"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"hostcheck archive ok: (\d+) fallible runtime calls per walk, (\d+) injected failures handled", r.stdout)
     assert m and int(m.group(1)) > 100 and m.group(1) == m.group(2), r.stdout

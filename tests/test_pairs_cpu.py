@@ -1,6 +1,6 @@
 """The pair counts without a GPU: the reference helper on hand-made populations, what PPDE_PAS refuses and how it reads
 ppde_sample_pairs before any device work, the driver's flag, the host side of the C ABI as a stand-alone program under
-AddressSanitizer (tests/hostcheck_pairs/), and the power condition of tests/test_pairs_gpu.py: on its seeded start populations the
+AddressSanitizer (tests/hostcheck/pairs.cpp), and the power condition of tests/test_pairs_gpu.py: on its seeded start populations the
 reference differs from itself with the letters of an off-diagonal block exchanged, and from itself with the two sites exchanged
 without their letters, so a kernel (or an unpacking) that transposes either would be seen."""
 import argparse
@@ -157,12 +157,12 @@ def test_cli_flag_parses_into_the_sampler_argument():
 
 # ------------------------------------------------------------------------------------------------ the host layer
 def test_host_layer_of_the_pair_counts_under_address_sanitizer():
-    """tests/hostcheck_pairs/: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
+    """tests/hostcheck/pairs.cpp: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
     tests/hostcheck/, compiled with AddressSanitizer + LeakSanitizer: every refusal, then a valid set, shape, init, run, read,
     clear and destroy, then the walk once per fallible runtime call with that call failing. Any leak or out-of-bounds access fails
     the run."""
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck_pairs", "build_and_run.sh")
-    r = subprocess.run(["bash", script, "sweep"], capture_output=True, text=True, timeout=600)
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck", "build_and_run.sh")
+    r = subprocess.run(["bash", script, "pairs", "sweep"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"hostcheck pairs ok: (\d+) fallible runtime calls per walk, (\d+) injected failures handled", r.stdout)
     assert m and int(m.group(1)) > 100 and m.group(1) == m.group(2), r.stdout

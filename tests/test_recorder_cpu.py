@@ -1,5 +1,5 @@
 """The recorder without a GPU: the row schedule at its edges, what PPDE_PAS refuses before any device work, the host side of the
-C ABI as a stand-alone program under AddressSanitizer (tests/hostcheck_recorder/), and the conditions the GPU law tests of
+C ABI as a stand-alone program under AddressSanitizer (tests/hostcheck/recorder.cpp), and the conditions the GPU law tests of
 tests/test_recorder_gpu.py stand on.
 
 Enumerated here (CPU, fp64 over the reference's fp32 tables), case A (helpers_library.law_case, 35 states), beta = (1, 1/2), a swap
@@ -117,12 +117,12 @@ def test_cli_flags_parse_into_the_sampler_arguments():
 
 # ------------------------------------------------------------------------------------------------ the host layer
 def test_host_layer_of_the_recorder_under_address_sanitizer():
-    """tests/hostcheck_recorder/: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
+    """tests/hostcheck/recorder.cpp: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
     tests/hostcheck/, compiled with AddressSanitizer + LeakSanitizer: every refusal, then a valid recorder, init, run, shape, read
     and destroy, then the walk once per fallible runtime call with that call failing. Any leak or out-of-bounds access fails the
     run."""
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck_recorder", "build_and_run.sh")
-    r = subprocess.run(["bash", script, "sweep"], capture_output=True, text=True, timeout=600)
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck", "build_and_run.sh")
+    r = subprocess.run(["bash", script, "recorder", "sweep"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"hostcheck recorder ok: (\d+) fallible runtime calls per walk, (\d+) injected failures handled", r.stdout)
     assert m and int(m.group(1)) > 100 and m.group(1) == m.group(2), r.stdout

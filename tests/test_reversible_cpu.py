@@ -136,15 +136,15 @@ def test_ppde_pas_refuses_a_start_state_outside_the_library():
 
 
 def test_host_layer_of_reversible_mode_under_address_sanitizer():
-    """tests/hostcheck_reversible/: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime
+    """tests/hostcheck/reversible.cpp: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime
     of tests/hostcheck/, compiled with AddressSanitizer + LeakSanitizer: create -> set_library -> set_reversible -> init -> run
     -> collect -> destroy on both RNG modes and gradient policies, the refusals, then the walk once per fallible runtime call
     with that call failing. Any leak or out-of-bounds access fails the run."""
     import os
     import re
     import subprocess
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck_reversible", "build_and_run.sh")
-    r = subprocess.run(["bash", script, "sweep"], capture_output=True, text=True, timeout=600)
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck", "build_and_run.sh")
+    r = subprocess.run(["bash", script, "reversible", "sweep"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"hostcheck reversible ok: (\d+) fallible runtime calls per walk, (\d+) injected failures handled", r.stdout)
     assert m and int(m.group(1)) > 100 and m.group(1) == m.group(2), r.stdout

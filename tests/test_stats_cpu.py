@@ -1,6 +1,6 @@
 """The move statistics without a GPU: the rule (helpers_stats.stats_of) on hand-made peeks, its identities on random inputs,
 ppde_amd.stats.summarise, what PPDE_PAS refuses before any device work, the driver's flags, the host side of the C ABI as a
-stand-alone program under AddressSanitizer (tests/hostcheck_stats/), and the conditions the GPU tests of tests/test_stats_gpu.py
+stand-alone program under AddressSanitizer (tests/hostcheck/stats.cpp), and the conditions the GPU tests of tests/test_stats_gpu.py
 stand on, asserted on CPU reference runs of the same configurations (TOY24, 16 chains, T = 130, pas_length 2, nmut_threshold 3,
 Philox seed 202). The tests assert ">= 1" of each kind of event, not the counts they print."""
 import argparse
@@ -154,12 +154,12 @@ def test_cli_flags_parse_into_the_sampler_argument():
 
 # ------------------------------------------------------------------------------------------------ the host layer
 def test_host_layer_of_the_statistics_under_address_sanitizer():
-    """tests/hostcheck_stats/: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
+    """tests/hostcheck/stats.cpp: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime of
     tests/hostcheck/, compiled with AddressSanitizer + LeakSanitizer: set, replace and clear, every refusal, reads before and after
     runs, a second init and destroy, then the walk once per fallible runtime call with that call failing. Any leak or out-of-bounds
     access fails the run."""
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck_stats", "build_and_run.sh")
-    r = subprocess.run(["bash", script, "sweep"], capture_output=True, text=True, timeout=600)
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck", "build_and_run.sh")
+    r = subprocess.run(["bash", script, "stats", "sweep"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"hostcheck stats ok: (\d+) fallible runtime calls per walk, (\d+) injected failures handled", r.stdout)
     assert m and int(m.group(1)) > 100 and m.group(1) == m.group(2), r.stdout

@@ -227,15 +227,15 @@ def test_cli_flags_parse_into_the_sampler_arguments():
 
 
 def test_host_layer_of_tempering_under_address_sanitizer():
-    """tests/hostcheck_tempering/: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime
+    """tests/hostcheck/tempering.cpp: a stand-alone C++ driver (its own main) over the host side of the C ABI and the mock runtime
     of tests/hostcheck/, compiled with AddressSanitizer + LeakSanitizer: create -> set_library -> set_reversible ->
     set_tempering (every refusal, then a valid ladder) -> init -> run -> tempering_state / history -> destroy, then the walk once
     per fallible runtime call with that call failing. Any leak or out-of-bounds access fails the run."""
     import os
     import re
     import subprocess
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck_tempering", "build_and_run.sh")
-    r = subprocess.run(["bash", script, "sweep"], capture_output=True, text=True, timeout=600)
+    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck", "build_and_run.sh")
+    r = subprocess.run(["bash", script, "tempering", "sweep"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     m = re.search(r"hostcheck tempering ok: (\d+) fallible runtime calls per walk, (\d+) injected failures handled", r.stdout)
     assert m and int(m.group(1)) > 100 and m.group(1) == m.group(2), r.stdout
