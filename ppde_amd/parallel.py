@@ -4,9 +4,14 @@ Chains are independent Markov chains, so the population splits into contiguous b
 per-step communication: the device RNG is keyed by the GLOBAL chain index, so a chain's trajectory does not
 depend on how many ranks there are. The only collective is the final population collect (all_gather over
 RCCL/xGMI on GPUs; gloo in the CPU tests).
+
+`Shard` is one rank's view of such a split and the owner of what a sharded run gathers at its end: per chain, per group of
+consecutive chains (tempering ensembles, annealing demes, recorder slots), summed over the ranks, or broadcast from the rank
+that owns a chain. Without communication every one of its operations hands its array back.
 """
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -85,3 +90,55 @@ def agree_from_rank0(values):
         return [int(v) for v in values]
     t = torch.tensor([int(v) for v in values], dtype=torch.int64)
     return [int(v) for v in broadcast_from(t, 0).tolist()]
+
+
+def boundary_cut(starts, size):
+    """(rank, start) of the first shard start that is no multiple of `size` -- a group of `size` consecutive chains would lie on
+    two ranks --, or None when the groups split as the chains do."""
+    for r, start in enumerate(starts):
+        if start % size:
+            return r, start
+    return None
+
+
+class Shard:
+    """Rank `rank` of `ws` in a population of n_global chains: its block [lo, hi) of n chains, and the collect of a sharded run.
+    comm False (one rank, or a run that does not shard inside an initialised process group): nothing below communicates and
+    every array comes back as it went in."""
+
+    def __init__(self, n_global, rank=0, ws=1, comm=False):
+        self.n_global, self.rank, self.ws, self.comm = int(n_global), int(rank), int(ws), bool(comm)
+        self.lo, self.hi = shard_range(self.n_global, self.rank, self.ws)
+        self.n = self.hi - self.lo
+
+    @property
+    def starts(self):
+        """First chain of every rank's block."""
+        return [shard_range(self.n_global, r, self.ws)[0] for r in range(self.ws)]
+
+    def owner(self, chain):
+        """The rank whose block holds global chain `chain`."""
+        return next(r for r in range(self.ws) if chain < shard_range(self.n_global, r, self.ws)[1])
+
+    def to_global(self, local):
+        """Local chain indices as int64 global ones."""
+        return local.astype(np.int64) + self.lo
+
+    def gather(self, a, dim=0, size=1):
+        """Every rank's block of `a` along its chain axis `dim`, in global order. size > 1: the axis holds one entry per group
+        of `size` consecutive chains (no shard start may cut a group: boundary_cut)."""
+        a = np.asarray(a)
+        return all_gather_rows(torch.from_numpy(a), self.n_global // size, dim=dim).numpy() if self.comm else a
+
+    def sum(self, a):
+        """Element-wise sum of `a` over the ranks (None stays None). uint64 counts travel as int64: the collectives have no
+        unsigned 64-bit sum."""
+        if a is None or not self.comm:
+            return a
+        if a.dtype == np.uint64:
+            return sum_over_ranks(torch.from_numpy(a.astype(np.int64))).numpy().astype(np.uint64)
+        return sum_over_ranks(torch.from_numpy(a)).numpy()
+
+    def broadcast(self, a, src):
+        """Rank src's `a` on every rank."""
+        return broadcast_from(torch.from_numpy(a), src).numpy() if self.comm else a

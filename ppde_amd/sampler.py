@@ -81,6 +81,7 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
 import ctypes as C
 import sys
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -89,7 +90,7 @@ from . import _hip, anneal as chain_anneal, archive as chain_archive, library as
 from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
-from .parallel import active as collectives_active, agree_from_rank0, all_gather_rows, broadcast_from, shard_range, sum_over_ranks, world
+from .parallel import Shard, active as collectives_active, agree_from_rank0, boundary_cut, world
 
 
 def recorder_rows(max_steps, burn_in, every):
@@ -195,6 +196,21 @@ def check_ladder(betas):
     return np.ascontiguousarray(b)
 
 
+def check_tempering(betas, swap_every, reversible, n_streams):
+    """(ladder fp32 [R] or None, swap_every) of the ppde_betas / ppde_swap_every arguments; ValueError for what the ABI would refuse
+    and can be seen without the population."""
+    ladder = None if betas is None or len(betas) == 0 else check_ladder(betas)
+    swap_every = int(swap_every)
+    if ladder is not None:
+        if not reversible:
+            raise ValueError("ppde_betas: tempering needs ppde_reversible (only there is the law at beta, exp(beta energy)/Z, defined)")
+        if swap_every < 0:
+            raise ValueError("ppde_swap_every must be >= 0")
+        if int(n_streams) > 1:
+            raise ValueError("ppde_betas: ppde_streams > 1 is not supported (the swap couples the chains of an ensemble)")
+    return ladder, swap_every
+
+
 def check_schedule(betas):
     """An annealing schedule as fp32 [S + 1], or ValueError: 2..4097 finite, positive, non-decreasing inverse temperatures."""
     b = np.asarray(betas, dtype=np.float32).reshape(-1)
@@ -236,12 +252,38 @@ def check_demes(n_global, deme, num_steps, every, n_stages, shard_starts=(0,)):
         raise ValueError(f"ppde_deme: a deme has 2 to 1024 chains, got {D}" + (" (ppde_deme 0 = all chains of the run)" if int(deme) == 0 else ""))
     if n_global % D:
         raise ValueError(f"ppde_deme: the population of {n_global} chains is no multiple of the deme of {D}")
-    for r, start in enumerate(shard_starts):
-        if start % D:
-            raise ValueError(f"ppde_deme: the shard boundary at chain {start} (rank {r} of {len(shard_starts)}) cuts a deme of {D} chains")
+    cut = boundary_cut(shard_starts, D)
+    if cut:
+        raise ValueError(f"ppde_deme: the shard boundary at chain {cut[1]} (rank {cut[0]} of {len(shard_starts)}) cuts a deme of {D} chains")
     if min(int(n_stages), int(num_steps) // int(every)) == 0:
         raise ValueError(f"ppde_anneal_every: no event fits into {int(num_steps)} iterations (every {int(every)})")
     return D
+
+
+def check_recorder(every, burn_in, rung, counts_only, pairs, ladder, n_streams):
+    """(every, burn_in, rung, counts_only, pairs) of the ppde_sample_* arguments (every 0: no recorder; rung None without a ladder,
+    default 0 with one; pairs as check_pair_spec); ValueError for what the ABI would refuse and can be seen without the run length."""
+    every, burn_in, counts_only = int(every or 0), int(burn_in or 0), bool(counts_only)
+    pairs = check_pair_spec(pairs)
+    if pairs is not None and every <= 0:
+        raise ValueError("ppde_sample_pairs needs ppde_sample_every > 0 (pair counts follow the recorder's schedule)")
+    if every < 0:
+        raise ValueError("ppde_sample_every must be >= 0 (0: no recorder)")
+    if every == 0 and (burn_in or rung is not None or counts_only):
+        raise ValueError("ppde_sample_burn_in / ppde_sample_rung / ppde_sample_counts_only need ppde_sample_every > 0")
+    if every:
+        if burn_in < 0:
+            raise ValueError("ppde_sample_burn_in must be >= 0")
+        if int(n_streams) > 1:
+            raise ValueError("ppde_sample_every: ppde_streams > 1 is not supported (the recorder's counters have one owner per launch)")
+        if ladder is None:
+            if rung is not None:
+                raise ValueError("ppde_sample_rung: following a rung needs a ladder (ppde_betas)")
+        else:
+            rung = 0 if rung is None else int(rung)
+            if not 0 <= rung < ladder.size:
+                raise ValueError(f"ppde_sample_rung must be a rung of the ladder, 0..{ladder.size - 1}")
+    return every, burn_in, rung, counts_only, pairs
 
 
 class Chains:
@@ -262,6 +304,11 @@ class Chains:
         with torch.cuda.device(model.device):
             _hip.check(self.lib.ppde_chains_create(C.byref(self.handle), model.handle, C.byref(self.cfg)))
 
+    def _call(self, name, *args):
+        """ppde_chains_<name>(handle, *args) on the model's device; a non-zero status raises (_hip.check)."""
+        with torch.cuda.device(self.model.device):
+            _hip.check(getattr(self.lib, "ppde_chains_" + name)(self.handle, *args))
+
     def close(self):
         if getattr(self, "handle", None) is not None and self.handle.value:
             self.lib.ppde_chains_destroy(self.handle)
@@ -277,14 +324,13 @@ class Chains:
         """Design library for the forward proposals: uint32 [L] (bit k = letter k allowed, 0 = frozen) or bool [L, 20]; None
         clears it. Only before init() (the graphs captured there hold the device copy's address)."""
         words = None if mask is None else design_library.as_words(mask, self.model.L)
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_set_library(self.handle, _hip.ptr(words)))
+        self._call("set_library", _hip.ptr(words))
         self.library = words
 
     def set_reversible(self, on=True):
         """Reversible mode (include/ppde_hip.h, ppde_chains_set_reversible): the accept phase scores the moves that undo the
         path under the forward row function, so the chains sample exp(energy)/Z over the library. Only before init()."""
-        _hip.check(self.lib.ppde_chains_set_reversible(self.handle, int(bool(on))))
+        self._call("set_reversible", int(bool(on)))
         self.reversible = bool(on)
 
     def set_tempering(self, betas, swap_every=1):
@@ -292,9 +338,7 @@ class Chains:
         ensembles of len(betas) consecutive chains, replica exchange every `swap_every` iterations (0: never). None or an
         empty ladder clears it. Needs reversible mode; only before init()."""
         ladder = None if betas is None or len(betas) == 0 else np.ascontiguousarray(np.asarray(betas, dtype=np.float32).reshape(-1))
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_set_tempering(self.handle, 0 if ladder is None else int(ladder.size), _hip.ptr(ladder),
-                                                          int(swap_every)))
+        self._call("set_tempering", 0 if ladder is None else int(ladder.size), _hip.ptr(ladder), int(swap_every))
         self.betas, self.swap_every = ladder, int(swap_every)
 
     def tempering_state(self):
@@ -303,36 +347,34 @@ class Chains:
         pairs = (self.n // R, R - 1) if R else (0, 0)
         out = dict(rung=np.empty(self.n, np.int32), beta=np.empty(self.n, np.float32),
                    swap_attempts=np.zeros(pairs, np.int64), swap_accepts=np.zeros(pairs, np.int64))
-        _hip.check(self.lib.ppde_chains_tempering_state(self.handle, *[_hip.ptr(out[k]) for k in (
-            "rung", "beta", "swap_attempts", "swap_accepts")]))
+        self._call("tempering_state", *[_hip.ptr(out[k]) for k in ("rung", "beta", "swap_attempts", "swap_accepts")])
         return out
 
     def tempering_history(self):
         """uint8 [steps_done + 1, n]: the rung each chain held after every iteration (row 0: the start)."""
         out = np.empty((self.steps_done + 1, self.n), np.uint8)
-        _hip.check(self.lib.ppde_chains_tempering_history(self.handle, _hip.ptr(out)))
+        self._call("tempering_history", _hip.ptr(out))
         return out
 
     def set_annealing(self, betas, every=1, deme=None):
         """Population annealing (include/ppde_hip.h, ppde_chains_set_annealing): a schedule betas[0] <= ... <= betas[S] over demes
         of `deme` consecutive chains (None: all chains of the object), one stage behind every `every`-th iteration. None or an
         empty schedule clears it. Needs reversible mode; only before init()."""
-        with torch.cuda.device(self.model.device):
-            if betas is None or len(betas) == 0:
-                _hip.check(self.lib.ppde_chains_set_annealing(self.handle, None))
-                self.anneal = None
-                return
-            sched = np.ascontiguousarray(np.asarray(betas, dtype=np.float32).reshape(-1))
-            D = self.n if deme is None else int(deme)
-            cfg = _hip.AnnealConfig(deme=D, every=int(every), n_stages=int(sched.size) - 1,
-                                    beta=sched.ctypes.data_as(C.POINTER(C.c_float)))
-            _hip.check(self.lib.ppde_chains_set_annealing(self.handle, C.byref(cfg)))
+        if betas is None or len(betas) == 0:
+            self._call("set_annealing", None)
+            self.anneal = None
+            return
+        sched = np.ascontiguousarray(np.asarray(betas, dtype=np.float32).reshape(-1))
+        D = self.n if deme is None else int(deme)
+        cfg = _hip.AnnealConfig(deme=D, every=int(every), n_stages=int(sched.size) - 1,
+                                beta=sched.ctypes.data_as(C.POINTER(C.c_float)))
+        self._call("set_annealing", C.byref(cfg))
         self.anneal = dict(betas=sched, every=int(every), deme=D)
 
     def annealing_shape(self):
         """(deme size, event capacity, events that have happened)."""
         d, cap, done = C.c_int32(), C.c_int32(), C.c_int32()
-        _hip.check(self.lib.ppde_chains_annealing_shape(self.handle, C.byref(d), C.byref(cap), C.byref(done)))
+        self._call("annealing_shape", C.byref(d), C.byref(cap), C.byref(done))
         return d.value, cap.value, done.value
 
     def annealing_state(self, first=0, count=None):
@@ -345,9 +387,7 @@ class Chains:
         out = dict(parent=np.empty((k, self.n), np.int32), pre_energy=np.empty((k, self.n), np.float32),
                    log_mean_w=np.empty((k, self.n // D), np.float64), ess=np.empty((k, self.n // D), np.float64),
                    beta=np.empty(self.n, np.float32))
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_annealing_read(self.handle, first, count, *[_hip.ptr(out[k_]) for k_ in (
-                "parent", "pre_energy", "log_mean_w", "ess", "beta")]))
+        self._call("annealing_read", first, count, *[_hip.ptr(out[k_]) for k_ in ("parent", "pre_energy", "log_mean_w", "ess", "beta")])
         out["events"] = done
         return out
 
@@ -356,21 +396,20 @@ class Chains:
         device when t > burn_in and (t - burn_in) % every == 0. rung None: every chain is a slot; rung r (tempering, set before):
         one slot per ensemble, the chain that holds rung r after that iteration's swap. keep_samples False: site counts only.
         every None clears it. Only before init()."""
-        with torch.cuda.device(self.model.device):
-            if every is None:
-                _hip.check(self.lib.ppde_chains_set_recorder(self.handle, None))
-                self.recorder = None
-                return
-            cfg = _hip.RecordConfig(burn_in=int(burn_in), every=int(every), rung=-1 if rung is None else int(rung),
-                                    keep_samples=int(bool(keep_samples)))
-            _hip.check(self.lib.ppde_chains_set_recorder(self.handle, C.byref(cfg)))
+        if every is None:
+            self._call("set_recorder", None)
+            self.recorder = None
+            return
+        cfg = _hip.RecordConfig(burn_in=int(burn_in), every=int(every), rung=-1 if rung is None else int(rung),
+                                keep_samples=int(bool(keep_samples)))
+        self._call("set_recorder", C.byref(cfg))
         self.recorder = dict(every=int(every), burn_in=int(burn_in), rung=None if rung is None else int(rung),
                              keep_samples=bool(keep_samples))
 
     def recorder_shape(self):
         """(rows recorded so far, row capacity, slots per row)."""
         d, cap, sl = C.c_int32(), C.c_int32(), C.c_int32()
-        _hip.check(self.lib.ppde_chains_recorder_shape(self.handle, C.byref(d), C.byref(cap), C.byref(sl)))
+        self._call("recorder_shape", C.byref(d), C.byref(cap), C.byref(sl))
         return d.value, cap.value, sl.value
 
     def recorded(self, first=0, count=None):
@@ -387,9 +426,7 @@ class Chains:
                    fitness=np.empty((max(count, 0), slots), np.float32) if keep else None,
                    chain=np.empty((max(count, 0), slots), np.int32) if keep else None,
                    site_counts=np.zeros((L, 20), np.uint64))
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_recorder_read(self.handle, first, count, *[_hip.ptr(out[k]) for k in (
-                "idx", "energy", "fitness", "chain", "site_counts")]))
+        self._call("recorder_read", first, count, *[_hip.ptr(out[k]) for k in ("idx", "energy", "fitness", "chain", "site_counts")])
         out["rows"] = done
         return out
 
@@ -400,69 +437,53 @@ class Chains:
         arr = None if sites is None else np.ascontiguousarray(np.asarray(sites, dtype=np.int32).reshape(-1))
         cfg = _hip.PairConfig(n_sites=0 if arr is None else int(arr.size),
                               sites=None if arr is None else arr.ctypes.data_as(C.POINTER(C.c_int32)))
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_set_pair_counts(self.handle, C.byref(cfg)))
+        self._call("set_pair_counts", C.byref(cfg))
 
     def clear_pair_counts(self):
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_set_pair_counts(self.handle, None))
+        self._call("set_pair_counts", None)
 
     def pair_counts(self):
         """(counts uint64 [S, 20, S, 20] over ALL rows recorded so far, sites int32 [S]): counts[i, a, j, b] = recorded (row, slot)
         pairs with letter a at residue sites[i] and letter b at residue sites[j]."""
         S = C.c_int32()
-        _hip.check(self.lib.ppde_chains_pair_counts_shape(self.handle, C.byref(S), None))
+        self._call("pair_counts_shape", C.byref(S), None)
         sites = np.empty(S.value, np.int32)
-        _hip.check(self.lib.ppde_chains_pair_counts_shape(self.handle, None, _hip.ptr(sites)))
+        self._call("pair_counts_shape", None, _hip.ptr(sites))
         counts = np.zeros((S.value, 20, S.value, 20), np.uint64)
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_pair_counts_read(self.handle, _hip.ptr(counts)))
+        self._call("pair_counts_read", _hip.ptr(counts))
         return counts, sites
 
     def set_archive(self, k):
         """Archive (include/ppde_hip.h, ppde_chains_set_archive): every chain keeps the k best distinct non-wild-type states it
         visited, 1 <= k <= 32. None clears it. Only before init()."""
-        with torch.cuda.device(self.model.device):
-            if k is None:
-                _hip.check(self.lib.ppde_chains_set_archive(self.handle, None))
-                return
-            cfg = _hip.ArchiveConfig(k=int(k))
-            _hip.check(self.lib.ppde_chains_set_archive(self.handle, C.byref(cfg)))
+        self._call("set_archive", None if k is None else C.byref(_hip.ArchiveConfig(k=int(k))))
 
     def archive(self):
         """What the archive holds: idx uint8 [n, K, L], energy / fitness fp32 [n, K], step int32 [n, K], count int32 [n]; every
         chain's entries by (energy descending, step ascending), the slots beyond count filled with 255, -inf, 0, -1."""
         K = C.c_int32()
-        _hip.check(self.lib.ppde_chains_archive_shape(self.handle, C.byref(K)))
+        self._call("archive_shape", C.byref(K))
         n, k, L = self.n, K.value, self.model.L
         out = dict(idx=np.empty((n, k, L), np.uint8), energy=np.empty((n, k), np.float32), fitness=np.empty((n, k), np.float32),
                    step=np.empty((n, k), np.int32), count=np.empty(n, np.int32))
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_archive_read(self.handle, *[_hip.ptr(out[k_]) for k_ in (
-                "idx", "energy", "fitness", "step", "count")]))
+        self._call("archive_read", *[_hip.ptr(out[k_]) for k_ in ("idx", "energy", "fitness", "step", "count")])
         return out
 
     def set_stats(self, per_site=True):
         """Move statistics (include/ppde_hip.h, ppde_chains_set_stats): acceptances, jump distances, mutation counts and wild-type
         returns per (chain, rung), attempts and acceptances per (rung, path length) and, with per_site, changes per (rung,
         residue), counted on the device. None clears them. Only before init(), and after set_tempering() when there is a ladder."""
-        with torch.cuda.device(self.model.device):
-            if per_site is None:
-                _hip.check(self.lib.ppde_chains_set_stats(self.handle, None))
-                return
-            cfg = _hip.StatsConfig(per_site=int(bool(per_site)))
-            _hip.check(self.lib.ppde_chains_set_stats(self.handle, C.byref(cfg)))
+        self._call("set_stats", None if per_site is None else C.byref(_hip.StatsConfig(per_site=int(bool(per_site)))))
 
     def stats(self):
         """The counters so far, int64: iters, accepts, moved, jump_sum, dist_sum, wt_returns [n, R'], len_attempts, len_accepts
         [R', M], site_changes [R', L] (None when per_site is off); R' = max(rungs, 1), M = 2 pas_length - 1."""
         R, M, ps = C.c_int32(), C.c_int32(), C.c_int32()
-        _hip.check(self.lib.ppde_chains_stats_shape(self.handle, C.byref(R), C.byref(M), C.byref(ps)))
+        self._call("stats_shape", C.byref(R), C.byref(M), C.byref(ps))
         out = {k: np.zeros((self.n, R.value), np.int64) for k in chain_stats.PER_CHAIN}
         out.update({k: np.zeros((R.value, M.value), np.int64) for k in chain_stats.PER_LENGTH})
         out["site_changes"] = np.zeros((R.value, self.model.L), np.int64) if ps.value else None
-        with torch.cuda.device(self.model.device):
-            _hip.check(self.lib.ppde_chains_stats_read(self.handle, *[_hip.ptr(out[k]) for k in chain_stats.KEYS]))
+        self._call("stats_read", *[_hip.ptr(out[k]) for k in chain_stats.KEYS])
         return out
 
     def init(self, idx0):
@@ -472,23 +493,23 @@ class Chains:
         if int(idx0.max()) >= 20:
             raise ValueError("residue indices must be in 0..19")
         torch.cuda.current_stream(self.model.device).synchronize()
-        _hip.check(self.lib.ppde_chains_init(self.handle, _hip.ptr(idx0)))
+        self._call("init", _hip.ptr(idx0))
 
     def run(self, steps, noise=None):
         """noise = (U int32 [steps,n], q fp32 [sum max_u, n, N], u fp32 [steps,n], max_u list) for rng_mode 0."""
         if noise is None:
-            _hip.check(self.lib.ppde_chains_run(self.handle, int(steps), None, None, None, None))
+            self._call("run", int(steps), None, None, None, None)
             return
         U, q, u, mus = noise
         dev = self.model.device
         U, q, u = (t.to(dev, non_blocking=False).contiguous() for t in (U, q, u))
         mu = np.ascontiguousarray(np.asarray(mus, dtype=np.int32))
         torch.cuda.current_stream(dev).synchronize()
-        _hip.check(self.lib.ppde_chains_run(self.handle, int(steps), _hip.ptr(U), _hip.ptr(q), _hip.ptr(u), _hip.ptr(mu)))
-        _hip.check(self.lib.ppde_chains_sync(self.handle))   # the noise tensors must outlive the kernels
+        self._call("run", int(steps), _hip.ptr(U), _hip.ptr(q), _hip.ptr(u), _hip.ptr(mu))
+        self._call("sync")   # the noise tensors must outlive the kernels
 
     def sync(self):
-        _hip.check(self.lib.ppde_chains_sync(self.handle))
+        self._call("sync")
 
     @property
     def steps_done(self):
@@ -499,7 +520,7 @@ class Chains:
         idx = np.empty((n, L), np.uint8)
         e, f = np.empty(n, np.float32), np.empty(n, np.float32)
         acc, dist = np.empty(n, np.uint8), np.empty(n, np.int32)
-        _hip.check(self.lib.ppde_chains_peek(self.handle, _hip.ptr(idx), _hip.ptr(e), _hip.ptr(f), _hip.ptr(acc), _hip.ptr(dist)))
+        self._call("peek", _hip.ptr(idx), _hip.ptr(e), _hip.ptr(f), _hip.ptr(acc), _hip.ptr(dist))
         return dict(idx=idx, energy=e, fitness=f, accepted=acc, dist=dist)
 
     def collect(self):
@@ -508,22 +529,22 @@ class Chains:
                    best_fitness=np.empty(n, np.float32), best_step=np.empty(n, np.int32),
                    energy_history=np.empty((rows, n), np.float32), fitness_history=np.empty((rows, n), np.float32),
                    random_traj=np.empty((rows, L), np.uint8) if self.cfg.random_chain >= 0 else None)
-        _hip.check(self.lib.ppde_chains_collect(self.handle, *[_hip.ptr(out[k]) for k in (
-            "best_idx", "best_energy", "best_fitness", "best_step", "energy_history", "fitness_history", "random_traj")]))
+        self._call("collect", *[_hip.ptr(out[k]) for k in (
+            "best_idx", "best_energy", "best_fitness", "best_step", "energy_history", "fitness_history", "random_traj")])
         return out
 
     def trace(self):
         t, n = self.steps_done, self.n
         out = dict(flat=np.empty((t, self.mu_max, n), np.int32), accepted=np.empty((t, n), np.uint8),
                    log_acc=np.empty((t, n), np.float32), U=np.empty((t, n), np.int32))
-        _hip.check(self.lib.ppde_chains_trace(self.handle, *[_hip.ptr(out[k]) for k in ("flat", "accepted", "log_acc", "U")]))
+        self._call("trace", *[_hip.ptr(out[k]) for k in ("flat", "accepted", "log_acc", "U")])
         return out
 
     def graph_stats(self):
         """How the iterations so far were issued: graphs captured (all by init), captured inside a run (0), steps
         replayed from graphs / launched eagerly."""
         a, b, r, e = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
-        _hip.check(self.lib.ppde_chains_graph_stats(self.handle, C.byref(a), C.byref(b), C.byref(r), C.byref(e)))
+        self._call("graph_stats", C.byref(a), C.byref(b), C.byref(r), C.byref(e))
         return dict(captures=a.value, captures_in_run=b.value, replayed_steps=r.value, eager_steps=e.value)
 
     def philox_dump(self, it, s):
@@ -534,26 +555,34 @@ class Chains:
         u = torch.empty(n, device=dev)
         U = torch.empty(n, dtype=torch.int32, device=dev)
         torch.cuda.current_stream(dev).synchronize()
-        _hip.check(self.lib.ppde_chains_philox_dump(self.handle, int(it), int(s), _hip.ptr(q), _hip.ptr(u), _hip.ptr(U)))
+        self._call("philox_dump", int(it), int(s), _hip.ptr(q), _hip.ptr(u), _hip.ptr(U))
         return q[:, :L + 20].contiguous(), u, U
 
     def time_potts_in_situ(self, iters=200):
         """Potts kernel launches inside `iters` real iterations (Potts-only energy): (mean us from the predecessor kernel's end
         to the launch's end, launches timed, mean us of the dispatches' own start -> end stamps or None)."""
         v, k, d = C.c_float(), C.c_int(), C.c_float()
-        _hip.check(self.lib.ppde_chains_time_potts_in_situ(self.handle, int(iters), C.byref(v), C.byref(k), C.byref(d)))
+        self._call("time_potts_in_situ", int(iters), C.byref(v), C.byref(k), C.byref(d))
         return v.value, k.value, (d.value if d.value > 0 else None)
 
     def time_experts(self, reps=100):
         """Mean duration (us) of one evaluation of all experts of the energy (current states -> proposal slot)."""
         v = C.c_float()
-        _hip.check(self.lib.ppde_chains_time_experts(self.handle, int(reps), C.byref(v)))
+        self._call("time_experts", int(reps), C.byref(v))
         return v.value
 
     def time_potts_kernel(self, reps=200):
         v = C.c_float()
-        _hip.check(self.lib.ppde_chains_time_potts_kernel(self.handle, int(reps), C.byref(v)))
+        self._call("time_potts_kernel", int(reps), C.byref(v))
         return v.value
+
+
+def gather_stats(shard, raw):
+    """Chains.stats() of a sharded run: the per-chain arrays in global chain order, the others summed, so every rank ends with the
+    full result."""
+    out = {k: shard.gather(raw[k]) for k in chain_stats.PER_CHAIN}
+    out.update({k: shard.sum(raw[k]) for k in chain_stats.PER_LENGTH + ("site_changes",)})
+    return out
 
 
 class PPDE_PAS(BaseSampler):
@@ -582,64 +611,29 @@ class PPDE_PAS(BaseSampler):
         if self.reversible and self.paper_results:
             raise ValueError("ppde_reversible: paper_results restarts a rejected chain from its initial state, which is no "
                              "Metropolis step; the two cannot be combined")
-        betas = getattr(args, "ppde_betas", None)
-        self.betas = None if betas is None or len(betas) == 0 else check_ladder(betas)
-        self.swap_every = int(getattr(args, "ppde_swap_every", 1))
-        self.tempering = None
-        if self.betas is not None:
-            if not self.reversible:
-                raise ValueError("ppde_betas: tempering needs ppde_reversible (only there is the law at beta, exp(beta energy)/Z, defined)")
-            if self.swap_every < 0:
-                raise ValueError("ppde_swap_every must be >= 0")
-            if int(self.n_streams) > 1:
-                raise ValueError("ppde_betas: ppde_streams > 1 is not supported (the swap couples the chains of an ensemble)")
+        self.betas, self.swap_every = check_tempering(
+            getattr(args, "ppde_betas", None), getattr(args, "ppde_swap_every", 1), self.reversible, self.n_streams)
         self.anneal_betas, self.anneal_every, self.deme = check_annealing(
             getattr(args, "ppde_anneal_betas", None), getattr(args, "ppde_anneal_every", 1) or 1, getattr(args, "ppde_deme", 0) or 0,
             self.reversible, self.betas, self.n_streams)
-        self.annealing = None
-        self.sample_every = int(getattr(args, "ppde_sample_every", 0) or 0)
-        self.sample_burn_in = int(getattr(args, "ppde_sample_burn_in", 0) or 0)
-        self.sample_rung = getattr(args, "ppde_sample_rung", None)
-        self.sample_counts_only = bool(getattr(args, "ppde_sample_counts_only", False))
-        self.samples = None
-        self.sample_pairs = check_pair_spec(getattr(args, "ppde_sample_pairs", None))
-        if self.sample_pairs is not None and self.sample_every <= 0:
-            raise ValueError("ppde_sample_pairs needs ppde_sample_every > 0 (pair counts follow the recorder's schedule)")
-        if self.sample_every < 0:
-            raise ValueError("ppde_sample_every must be >= 0 (0: no recorder)")
-        if self.sample_every == 0 and (self.sample_burn_in or self.sample_rung is not None or self.sample_counts_only):
-            raise ValueError("ppde_sample_burn_in / ppde_sample_rung / ppde_sample_counts_only need ppde_sample_every > 0")
-        if self.sample_every:
-            if self.sample_burn_in < 0:
-                raise ValueError("ppde_sample_burn_in must be >= 0")
-            if int(self.n_streams) > 1:
-                raise ValueError("ppde_sample_every: ppde_streams > 1 is not supported (the recorder's counters have one owner per launch)")
-            if self.betas is None:
-                if self.sample_rung is not None:
-                    raise ValueError("ppde_sample_rung: following a rung needs a ladder (ppde_betas)")
-            else:
-                self.sample_rung = 0 if self.sample_rung is None else int(self.sample_rung)
-                if not 0 <= self.sample_rung < self.betas.size:
-                    raise ValueError(f"ppde_sample_rung must be a rung of the ladder, 0..{self.betas.size - 1}")
+        self.sample_every, self.sample_burn_in, self.sample_rung, self.sample_counts_only, self.sample_pairs = check_recorder(
+            getattr(args, "ppde_sample_every", 0), getattr(args, "ppde_sample_burn_in", 0), getattr(args, "ppde_sample_rung", None),
+            getattr(args, "ppde_sample_counts_only", False), getattr(args, "ppde_sample_pairs", None), self.betas, self.n_streams)
         self.archive_k = check_archive(getattr(args, "ppde_archive", None), self.paper_results, self.n_streams)
-        self.archive = None
         self.stats_spec = check_stats(getattr(args, "ppde_stats", None), self.n_streams)
-        self.stats = None
+        self.tempering = self.annealing = self.samples = self.archive = self.stats = None     # what the last run() collected
         self.noise_bytes = getattr(args, "ppde_noise_bytes", 96 << 20)   # host->device noise is uploaded in chunks of about this size
         self.last_chains = None
+        self._anneal_logged = 0     # annealing events the periodic log of the running run() has reported
         self.timings = {}       # seconds of the last run(): setup (chains + hipGraph capture), iterations, log path, collect
 
     def approximate_energy_change(self, score_change):
         return score_change / self.ppde_temp
 
-    def run(self, initial_population, num_steps, energy_function, min_pos, max_pos, oracle, log_every=50):
-        print(min_pos, max_pos)
-        model = getattr(energy_function, "model", None)
-        if model is None or not hasattr(energy_function, "which"):
-            raise TypeError("PPDE_PAS.run needs a ppde_amd energy function (ProteinProductOfExperts / ProteinSupervised); "
-                            "there is no generic torch fallback")
+    def _plan(self, initial_population, num_steps, min_pos, max_pos):
+        """Everything of a run that is decided on the host, and every refusal that needs no device: the library's words of a
+        reversible run (None otherwise), rungs R and deme D (0: off), the pair sites, the recorded chain and this rank's Shard."""
         n_global, L = int(initial_population.size(0)), int(initial_population.size(1))
-        min_pos, max_pos = int(min_pos), int(max_pos)
         lib_words = None
         if self.reversible:
             # a reversible run always has a library, the range folded in: the restriction is hard and the law exact. The
@@ -653,8 +647,8 @@ class PPDE_PAS(BaseSampler):
         if self.sample_every and recorder_rows(int(num_steps), self.sample_burn_in, self.sample_every) == 0:
             raise ValueError(f"ppde_sample_every: no iteration of {int(num_steps)} would be recorded (burn-in {self.sample_burn_in}, "
                              f"every {self.sample_every})")
-        pair_on, pair_sites = self.sample_pairs is not None, None
-        if pair_on:                                     # (host only: the library's words as the chains will get them)
+        pair_sites = None
+        if self.sample_pairs is not None:               # (host only: the library's words as the chains will get them)
             words = lib_words
             if words is None and self.library is not None:
                 words = design_library.fold_range(design_library.as_words(self.library, L), min_pos, max_pos)
@@ -663,217 +657,223 @@ class PPDE_PAS(BaseSampler):
                 raise ValueError("ppde_sample_pairs: the selection holds no residue")
         random_idx = np.random.randint(0, n_global)                       # ppde.py:37 (same numpy RNG consumption)
         rank, ws = world() if self.shard else (0, 1)
-        if R:
-            for r in range(ws):
-                if shard_range(n_global, r, ws)[0] % R:
-                    raise ValueError(f"ppde_betas: the shard boundary at chain {shard_range(n_global, r, ws)[0]} (rank {r} of {ws}) "
-                                     f"cuts an ensemble of {R} chains")
+        # (comm: ws > 1, or the one-rank rehearsal of the RCCL path; never in a run that does not shard)
+        shard = Shard(n_global, rank, ws, comm=self.shard and collectives_active())
+        cut = boundary_cut(shard.starts, R) if R else None
+        if cut:
+            raise ValueError(f"ppde_betas: the shard boundary at chain {cut[1]} (rank {cut[0]} of {ws}) cuts an ensemble of {R} chains")
         D = 0
-        if self.anneal_betas is not None:               # (host only, before any device work)
-            D = check_demes(n_global, self.deme, num_steps, self.anneal_every, self.anneal_betas.size - 1,
-                            [shard_range(n_global, r, ws)[0] for r in range(ws)])
-        comm = self.shard and collectives_active()        # (ws > 1, or the one-rank rehearsal of the RCCL path)
-        lo, hi = shard_range(n_global, rank, ws)
-        n = hi - lo
-        idx0 = model.onehot_to_idx(initial_population)
-        # (63 bits whatever the rank count: the key travels through an int64 tensor when ranks agree on it, and a run's
-        # Philox streams must not depend on how many ranks there are)
-        seed = (self.seed if self.seed is not None else torch.initial_seed()) & (2 ** 63 - 1)
-        if comm:        # one recorded chain and one Philox key for the whole job, whatever each rank's host RNG state is
-            random_idx, seed = agree_from_rank0([random_idx, seed])
-        if self.rng == "torch" and not PPDE_PAS._hinted:
-            PPDE_PAS._hinted = True
-            print("[ppde_amd] ppde_rng='torch' replays the reference's random stream: every iteration waits for torch's CPU exponential_ "
-                  "(~100 iterations/s at 128 chains). --ppde_rng philox draws on the device: hundreds of times faster, same law, "
-                  "another trajectory.", file=sys.stderr, flush=True)
-        t_begin = time.perf_counter()
-        t_log = 0.0
+        if self.anneal_betas is not None:
+            D = check_demes(n_global, self.deme, num_steps, self.anneal_every, self.anneal_betas.size - 1, shard.starts)
+        return SimpleNamespace(L=L, lib_words=lib_words, R=R, D=D, pair_sites=pair_sites, random_idx=random_idx, shard=shard)
+
+    def _configured_chains(self, model, which, plan, num_steps, min_pos, max_pos, random_idx, seed):
+        """This rank's Chains with every mode of the run set, before init()."""
+        shard, lib_words = plan.shard, plan.lib_words
         if self.library is not None and not self.reversible:
             # the range goes INTO the library (exact) and the chains run over the full range: no entry of a library run is
             # masked by the leaky range mask. The same words on every rank.
-            lib_words = design_library.fold_range(design_library.as_words(self.library, L), min_pos, max_pos)
-        chains = Chains(model, n, num_steps, self.ppde_pas_length, self.nmut_threshold, self.paper_results,
-                        0 if lib_words is not None else min_pos,
-                        L - 1 if lib_words is not None else max_pos, energy_function.which, 0 if self.rng == "torch" else 1, self.reuse_grad, self.cpu_alias,
-                        self.trace, random_idx - lo if lo <= random_idx < hi else -1, self.use_graph, seed, lo,
+            lib_words = design_library.fold_range(design_library.as_words(self.library, plan.L), min_pos, max_pos)
+        chains = Chains(model, shard.n, num_steps, self.ppde_pas_length, self.nmut_threshold, self.paper_results,
+                        0 if lib_words is not None else min_pos, plan.L - 1 if lib_words is not None else max_pos, which,
+                        0 if self.rng == "torch" else 1, self.reuse_grad, self.cpu_alias, self.trace,
+                        random_idx - shard.lo if shard.lo <= random_idx < shard.hi else -1, self.use_graph, seed, shard.lo,
                         self.n_streams)
         self.last_chains = chains
         if lib_words is not None:
             chains.set_library(lib_words)
         if self.reversible:
             chains.set_reversible(True)
-        if R:
+        if plan.R:
             chains.set_tempering(self.betas, self.swap_every)
-        if D:
-            chains.set_annealing(self.anneal_betas, self.anneal_every, D)
+        if plan.D:
+            chains.set_annealing(self.anneal_betas, self.anneal_every, plan.D)
         if self.sample_every:
             chains.set_recorder(self.sample_every, self.sample_burn_in, self.sample_rung, not self.sample_counts_only)
-        if pair_on:
-            chains.set_pair_counts(pair_sites)
+        if self.sample_pairs is not None:
+            chains.set_pair_counts(plan.pair_sites)
         if self.archive_k:
             chains.set_archive(self.archive_k)
         if self.stats_spec is not None:
             chains.set_stats(self.stats_spec is True)
-        chains.init(idx0[lo:hi])
+        return chains
 
-        def gathered(a):
-            return all_gather_rows(torch.as_tensor(a), n_global).numpy() if comm else np.asarray(a)
+    def _advance(self, chains, shard, steps, N):
+        """`steps` iterations; in replay mode the host's noise goes up in chunks of about noise_bytes."""
+        if self.rng != "torch":
+            chains.run(steps)
+            return
+        kmax = max(1, int(self.noise_bytes // (self.ppde_pas_length * 2 * shard.n * N * 4 + 1)))
+        while steps > 0:
+            k = min(kmax, steps)
+            chains.run(k, draw_chunk(k, shard.n_global, N, self.ppde_pas_length, rows=(shard.lo, shard.hi)))
+            steps -= k
 
-        def gathered_ensembles(a):
-            # (every shard boundary is a multiple of R, so the shards are equal and the n / R ensembles split the same way)
-            return all_gather_rows(torch.as_tensor(a), n_global // R).numpy() if comm and R > 1 else np.asarray(a)
+    def _log(self, i, chains, plan, model, oracle, first=False):
+        shard = plan.shard
+        pk = chains.peek()
+        # (the one-hot form the oracle takes is expanded on the device: n x L bytes cross PCIe instead of n x L x 20 floats)
+        x_now = model.idx_to_onehot(torch.from_numpy(np.ascontiguousarray(shard.gather(pk["idx"]))))
+        gt = oracle(x_now).detach().cpu().numpy()
+        # (one call for the three rows: np.quantile's fixed cost is ~60 us, a seventh of a log line)
+        fq, gq, eq = np.quantile(np.stack([shard.gather(pk["fitness"]), gt, shard.gather(pk["energy"])]), [0.5, 0.9], axis=1).T
+        print(f'[Iteration {i}] energy: 50% {eq[0]:.3f}, 90% {eq[1]:.3f}', flush=not first)
+        if first:
+            print(f'[Iteration {i}] pred fit 50% {fq[0]:.3f}, 90% {fq[1]:.3f}')
+            print(f'[Iteration {i}] oracle fit 50% {gq[0]:.3f}, 90% {gq[1]:.3f}')
+            print('')
+        else:
+            print(f'[Iteration {i}] pred 50% {fq[0]:.3f}, 90% {fq[1]:.3f}', flush=True)
+            print(f'[Iteration {i}] oracle 50% {gq[0]:.3f}, 90% {gq[1]:.3f}', flush=True)
+            print(f'   # accepted = {float(shard.gather(pk["accepted"]).sum())}')
+            print(f'   # dist = {float(shard.gather(pk["dist"]).astype(np.float32).mean())}')
+            self._log_modes(chains, plan)
+            print('', flush=True)
 
-        def gathered_demes(a):
-            # (every shard boundary is a multiple of D: the n / D demes split as the chains do)
-            return all_gather_rows(torch.as_tensor(a), n_global // D, dim=1).numpy() if comm else np.asarray(a)
+    def _log_modes(self, chains, plan):
+        """The lines the optional modes add to a periodic log: swaps, the annealing stage, the move statistics."""
+        shard, R, D = plan.shard, plan.R, plan.D
+        if R:
+            ts = self._swap_counts(chains, shard, R)
+            print(f'   # swaps accepted = {int(ts["swap_accepts"].sum())} / {int(ts["swap_attempts"].sum())}')
+        if D:
+            self._log_annealing(chains, shard, D)
+        if self.stats_spec is not None:
+            print(chain_stats.log_line(gather_stats(shard, chains.stats())))
 
-        an_logged = [0]
+    def _log_annealing(self, chains, shard, D):
+        """One line when events happened since the last log: the latest stage, its beta, the smallest ESS and the slots replaced."""
+        _, _, ev = chains.annealing_shape()
+        if ev > self._anneal_logged:
+            st = chains.annealing_state(self._anneal_logged, ev - self._anneal_logged)
+            ess = shard.gather(st["ess"], dim=1, size=D)
+            replaced = sum(int((row != np.arange(shard.n)).sum()) for row in st["parent"])
+            replaced = int(shard.sum(np.array([replaced], np.int64))[0])
+            print(f'   # annealing: stage {ev} of {self.anneal_betas.size - 1}, beta = {float(self.anneal_betas[ev]):.6g}, '
+                  f'min ESS = {float(ess.min()):.2f} of {D}, slots replaced = {replaced}')
+            self._anneal_logged = ev
 
-        def anneal_log():
-            # one line when events happened since the last log: the latest stage, its beta, the smallest ESS and the slots replaced
-            _, _, ev = chains.annealing_shape()
-            if ev > an_logged[0]:
-                st = chains.annealing_state(an_logged[0], ev - an_logged[0])
-                ess = gathered_demes(st["ess"])
-                replaced = int(sum(int((row != np.arange(n)).sum()) for row in st["parent"]))
-                if comm:
-                    replaced = int(sum_over_ranks(torch.tensor([replaced], dtype=torch.int64))[0])
-                print(f'   # annealing: stage {ev} of {self.anneal_betas.size - 1}, beta = {float(self.anneal_betas[ev]):.6g}, '
-                      f'min ESS = {float(ess.min()):.2f} of {D}, slots replaced = {replaced}')
-                an_logged[0] = ev
+    @staticmethod
+    def _swap_counts(chains, shard, R):
+        """swap_accepts / swap_attempts [n_global / R, R - 1] (a ladder of one rung has no pairs: nothing to gather)."""
+        ts = chains.tempering_state()
+        return {k: shard.gather(ts[k], size=R) if R > 1 else ts[k] for k in ("swap_accepts", "swap_attempts")}
 
-        def stats_gathered(raw):
-            # (per-chain arrays in global chain order, the others summed: every rank ends with the full result)
-            out = {k: gathered(raw[k]) for k in chain_stats.PER_CHAIN}
-            for k in chain_stats.PER_LENGTH + ("site_changes",):
-                out[k] = raw[k] if raw[k] is None or not comm else sum_over_ranks(torch.from_numpy(raw[k])).numpy()
-            return out
+    def _collect_tempering(self, chains, shard, R):
+        if not R:
+            return None
+        ts = self._swap_counts(chains, shard, R)
+        return dict(betas=self.betas.copy(), rung_history=shard.gather(chains.tempering_history(), dim=1),
+                    swap_attempts=ts["swap_attempts"], swap_accepts=ts["swap_accepts"])
 
-        def log(i, first=False):
-            pk = chains.peek()
-            # (the one-hot form the oracle takes is expanded on the device: n x L bytes cross PCIe instead of n x L x 20 floats)
-            x_now = model.idx_to_onehot(torch.from_numpy(np.ascontiguousarray(gathered(pk["idx"]))))
-            gt = oracle(x_now).detach().cpu().numpy()
-            # (one call for the three rows: np.quantile's fixed cost is ~60 us, a seventh of a log line)
-            fq, gq, eq = np.quantile(np.stack([gathered(pk["fitness"]), gt, gathered(pk["energy"])]), [0.5, 0.9], axis=1).T
-            print(f'[Iteration {i}] energy: 50% {eq[0]:.3f}, 90% {eq[1]:.3f}', flush=not first)
-            if first:
-                print(f'[Iteration {i}] pred fit 50% {fq[0]:.3f}, 90% {fq[1]:.3f}')
-                print(f'[Iteration {i}] oracle fit 50% {gq[0]:.3f}, 90% {gq[1]:.3f}')
-                print('')
-            else:
-                print(f'[Iteration {i}] pred 50% {fq[0]:.3f}, 90% {fq[1]:.3f}', flush=True)
-                print(f'[Iteration {i}] oracle 50% {gq[0]:.3f}, 90% {gq[1]:.3f}', flush=True)
-                print(f'   # accepted = {float(gathered(pk["accepted"]).sum())}')
-                print(f'   # dist = {float(gathered(pk["dist"]).astype(np.float32).mean())}')
-                if R:
-                    ts = chains.tempering_state()
-                    print(f'   # swaps accepted = {int(gathered_ensembles(ts["swap_accepts"]).sum())} / {int(gathered_ensembles(ts["swap_attempts"]).sum())}')
-                if D:
-                    anneal_log()
-                if self.stats_spec is not None:
-                    print(chain_stats.log_line(stats_gathered(chains.stats())))
-                print('', flush=True)
+    def _collect_annealing(self, chains, shard, D):
+        if not D:
+            return None
+        st = chains.annealing_state()
+        an = dict(betas=self.anneal_betas.copy(), deme=D, every=self.anneal_every,
+                  parent=shard.gather(shard.to_global(st["parent"]), dim=1), pre_energy=shard.gather(st["pre_energy"], dim=1),
+                  log_mean_w=shard.gather(st["log_mean_w"], dim=1, size=D), ess=shard.gather(st["ess"], dim=1, size=D),
+                  beta_now=shard.gather(st["beta"]))
+        an["summary"] = chain_anneal.summarise(an["parent"], an["log_mean_w"], an["ess"], an["betas"])
+        return an
 
+    def _collect_samples(self, chains, shard, R):
+        if not self.sample_every:
+            return None
+        rec = chains.recorded()
+        out = dict(rows=rec["rows"], site_counts=shard.sum(rec["site_counts"]), idx=None, energy=None, fitness=None, chain=None,
+                   pair_counts=None, pair_sites=None)
+        if self.sample_pairs is not None:
+            pc, ps = chains.pair_counts()
+            out.update(pair_counts=shard.sum(pc), pair_sites=ps)
+        if not self.sample_counts_only:
+            rec["chain"] = shard.to_global(rec["chain"])
+            # (one slot per ensemble with a ladder, per chain without: shard boundaries are multiples of R, equal slot blocks)
+            out.update({k: shard.gather(rec[k], dim=1, size=R or 1) for k in ("idx", "energy", "fitness", "chain")})
+        return out
+
+    def _collect_archive(self, chains, shard):
+        if not self.archive_k:
+            return None
+        arc = {k: shard.gather(v) for k, v in chains.archive().items()}      # (global chain order)
+        arc["chain"] = np.arange(shard.n_global, dtype=np.int64)
+        arc["candidates"] = chain_archive.merge(arc["idx"], arc["energy"], arc["fitness"], arc["step"], arc["count"])
+        return arc
+
+    def _collect_stats(self, chains, shard):
+        if self.stats_spec is None:
+            return None
+        st = gather_stats(shard, chains.stats())
+        st["chain"] = np.arange(shard.n_global, dtype=np.int64)
+        st["betas"] = None if self.betas is None else self.betas.copy()
+        st["summary"] = chain_stats.summarise(st, st["betas"])
+        return st
+
+    def run(self, initial_population, num_steps, energy_function, min_pos, max_pos, oracle, log_every=50):
+        print(min_pos, max_pos)
+        model = getattr(energy_function, "model", None)
+        if model is None or not hasattr(energy_function, "which"):
+            raise TypeError("PPDE_PAS.run needs a ppde_amd energy function (ProteinProductOfExperts / ProteinSupervised); "
+                            "there is no generic torch fallback")
+        min_pos, max_pos = int(min_pos), int(max_pos)
+        # ---- host-only plan: every refusal that needs no device comes from here
+        plan = self._plan(initial_population, num_steps, min_pos, max_pos)
+        shard, R, D, L, random_idx = plan.shard, plan.R, plan.D, plan.L, plan.random_idx
+        idx0 = model.onehot_to_idx(initial_population)
+        # ---- RNG agreement
+        # (63 bits whatever the rank count: the key travels through an int64 tensor when ranks agree on it, and a run's
+        # Philox streams must not depend on how many ranks there are)
+        seed = (self.seed if self.seed is not None else torch.initial_seed()) & (2 ** 63 - 1)
+        if shard.comm:  # one recorded chain and one Philox key for the whole job, whatever each rank's host RNG state is
+            random_idx, seed = agree_from_rank0([random_idx, seed])
+        if self.rng == "torch" and not PPDE_PAS._hinted:
+            PPDE_PAS._hinted = True
+            print("[ppde_amd] ppde_rng='torch' replays the reference's random stream: every iteration waits for torch's CPU exponential_ "
+                  "(~100 iterations/s at 128 chains). --ppde_rng philox draws on the device: hundreds of times faster, same law, "
+                  "another trajectory.", file=sys.stderr, flush=True)
+        # ---- chains
+        t_begin = time.perf_counter()
+        t_log = 0.0
+        chains = self._configured_chains(model, energy_function.which, plan, num_steps, min_pos, max_pos, random_idx, seed)
+        chains.init(idx0[shard.lo:shard.hi])
+        self._anneal_logged = 0
         chains.sync()
         t_setup = time.perf_counter() - t_begin
+        # ---- iterations, with the log
         t0 = time.perf_counter()
-        log(0, first=True)
+        self._log(0, chains, plan, model, oracle, first=True)
         t_run0 = time.perf_counter()
         t_log0 = t_run0 - t0
-        N = L * 20
         done = 0
         while done < num_steps:
             # next iteration index i with i > 0 and (i+1) % log_every == 0  ->  stop after i+1 steps
             stop = min(num_steps, ((done // log_every) + 1) * log_every) if log_every > 0 else num_steps
-            if stop - done > 0:
-                if self.rng == "torch":
-                    per_it = self.ppde_pas_length * 2 * n * N * 4 + 1
-                    kmax = max(1, int(self.noise_bytes // per_it))
-                    while done < stop:
-                        k = min(kmax, stop - done)
-                        chains.run(k, draw_chunk(k, n_global, N, self.ppde_pas_length, rows=(lo, hi)))
-                        done += k
-                else:
-                    chains.run(stop - done)
-                    done = stop
+            self._advance(chains, shard, stop - done, L * 20)
+            done = stop
             i = done - 1
             if log_every > 0 and i > 0 and (i + 1) % log_every == 0:
                 chains.sync()
                 t0 = time.perf_counter()
-                log(i)
+                self._log(i, chains, plan, model, oracle)
                 t_log += time.perf_counter() - t0
         chains.sync()
         t_run = time.perf_counter() - t_run0 - t_log
+        # ---- collect
         t0 = time.perf_counter()
         res = chains.collect()
-        dev = initial_population.device
-        best_idx = gathered(res["best_idx"])
-        best_x = torch.from_numpy(idx_to_onehot(best_idx)).float().to(dev)
-        e_hist = all_gather_rows(torch.from_numpy(res["energy_history"]), n_global, dim=1).numpy() if comm else res["energy_history"]
-        f_hist = all_gather_rows(torch.from_numpy(res["fitness_history"]), n_global, dim=1).numpy() if comm else res["fitness_history"]
-        if comm:
-            owner = [r for r in range(ws) if shard_range(n_global, r, ws)[0] <= random_idx < shard_range(n_global, r, ws)[1]][0]
-            rt = torch.from_numpy(res["random_traj"]) if res["random_traj"] is not None else torch.zeros(num_steps + 1, L, dtype=torch.uint8)
-            rtraj = broadcast_from(rt, owner).numpy()
-        else:
-            rtraj = res["random_traj"]
+        best_x = torch.from_numpy(idx_to_onehot(shard.gather(res["best_idx"]))).float().to(initial_population.device)
+        e_hist, f_hist = shard.gather(res["energy_history"], dim=1), shard.gather(res["fitness_history"], dim=1)
+        # (only its owner recorded the random chain; the other ranks of a sharded run hand in a blank)
+        rtraj = res["random_traj"] if res["random_traj"] is not None else np.zeros((num_steps + 1, L), np.uint8)
+        rtraj = shard.broadcast(rtraj, shard.owner(random_idx))
         random_traj = list(idx_to_onehot(rtraj, dtype=np.float32))     # T + 1 arrays [L, 20] (views of one expansion)
-        best_e, best_f = gathered(res["best_energy"]), gathered(res["best_fitness"])
-        if R:
-            ts = chains.tempering_state()
-            rh = chains.tempering_history()
-            self.tempering = dict(
-                betas=self.betas.copy(),
-                rung_history=all_gather_rows(torch.from_numpy(rh), n_global, dim=1).numpy() if comm else rh,
-                swap_attempts=gathered_ensembles(ts["swap_attempts"]), swap_accepts=gathered_ensembles(ts["swap_accepts"]))
-        self.annealing = None
-        if D:
-            st = chains.annealing_state()
-            parent = all_gather_rows(torch.from_numpy(st["parent"].astype(np.int64) + lo), n_global, dim=1).numpy() if comm \
-                else st["parent"].astype(np.int64) + lo
-            an = dict(betas=self.anneal_betas.copy(), deme=D, every=self.anneal_every, parent=parent,
-                      pre_energy=all_gather_rows(torch.from_numpy(st["pre_energy"]), n_global, dim=1).numpy() if comm else st["pre_energy"],
-                      log_mean_w=gathered_demes(st["log_mean_w"]), ess=gathered_demes(st["ess"]), beta_now=gathered(st["beta"]))
-            an["summary"] = chain_anneal.summarise(an["parent"], an["log_mean_w"], an["ess"], an["betas"])
-            self.annealing = an
-        self.samples = None
-        if self.sample_every:
-            rec = chains.recorded()
-            n_slots = n_global // R if R else n_global                 # (shard boundaries are multiples of R: equal slot blocks)
-
-            def slots_gathered(a):
-                return all_gather_rows(torch.from_numpy(a), n_slots, dim=1).numpy() if comm else a
-
-            counts = rec["site_counts"]
-            if comm:
-                total = torch.from_numpy(counts.astype(np.int64))
-                counts = sum_over_ranks(total).numpy().astype(np.uint64)
-            self.samples = dict(rows=rec["rows"], site_counts=counts, idx=None, energy=None, fitness=None, chain=None,
-                                pair_counts=None, pair_sites=None)
-            if pair_on:
-                pc, ps = chains.pair_counts()
-                if comm:
-                    pc = sum_over_ranks(torch.from_numpy(pc.astype(np.int64))).numpy().astype(np.uint64)
-                self.samples.update(pair_counts=pc, pair_sites=ps)
-            if not self.sample_counts_only:
-                self.samples.update(idx=slots_gathered(rec["idx"]), energy=slots_gathered(rec["energy"]),
-                                    fitness=slots_gathered(rec["fitness"]),
-                                    chain=slots_gathered(rec["chain"].astype(np.int64) + lo))
-        self.archive = None
-        if self.archive_k:
-            arc = {k: gathered(v) for k, v in chains.archive().items()}      # (global chain order)
-            arc["chain"] = np.arange(n_global, dtype=np.int64)
-            arc["candidates"] = chain_archive.merge(arc["idx"], arc["energy"], arc["fitness"], arc["step"], arc["count"])
-            self.archive = arc
-        self.stats = None
-        if self.stats_spec is not None:
-            st = stats_gathered(chains.stats())
-            st["chain"] = np.arange(n_global, dtype=np.int64)
-            st["betas"] = None if self.betas is None else self.betas.copy()
-            st["summary"] = chain_stats.summarise(st, st["betas"])
-            self.stats = st
-        if n_global == 1:
+        best_e, best_f = shard.gather(res["best_energy"]), shard.gather(res["best_fitness"])
+        self.tempering = self._collect_tempering(chains, shard, R)
+        self.annealing = self._collect_annealing(chains, shard, D)
+        self.samples = self._collect_samples(chains, shard, R)
+        self.archive = self._collect_archive(chains, shard)
+        self.stats = self._collect_stats(chains, shard)
+        if shard.n_global == 1:
             # the reference's single-chain shapes (ppde.py:178-183; the ensemble's `.squeeze()`, nets.py:442, makes one chain's
             # fitness a scalar): fitness_history (T+1,) next to energy_history (T+1, 1); with ProteinSupervised the energy IS
             # that scalar, so energy_history is (T+1,) too and best_energy / best_fitness are 0-dim

@@ -119,6 +119,64 @@ def test_sharded_driver_two_ranks_equals_single_process():
             assert np.array_equal(np.load(os.path.join(d1, f)), np.load(os.path.join(d2, f))), f
 
 
+_HISTORIES = ["population", "energy_history", "fitness_history"]
+_SAMPLES = ["samples", "sample_energy", "sample_fitness", "sample_chain", "site_counts"]
+_ARCHIVE = ["archive"] + [f"archive_{k}" for k in ("energy", "fitness", "step", "count")] + \
+           ["candidates"] + [f"candidates_{k}" for k in ("energy", "fitness", "chain", "step", "nchains")]
+_STATS = [f"stats_{k}" for k in ("iters", "accepts", "moved", "jump_sum", "dist_sum", "wt_returns", "len_attempts", "len_accepts",
+                                 "site_changes")]
+_SHARDED_MODES = {
+    # 12 chains = 6 + 6, both multiples of the three rungs: two ensembles and two recorder slots per rank
+    "ladder": dict(port="29571", first_shard=6,
+                   flags=["--n_chains", "12", "--ppde_betas", "1,0.5,0.25", "--ppde_sample_every", "5", "--ppde_sample_burn_in", "5",
+                          "--ppde_sample_rung", "1", "--ppde_sample_pairs", "open", "--ppde_archive", "4", "--ppde_stats"],
+                   files=_HISTORIES + ["rung_history", "swap_attempts", "swap_accepts"] + _SAMPLES + ["pair_counts", "pair_sites"]
+                   + _ARCHIVE + _STATS),
+    # 16 chains = 8 + 8, both multiples of the deme of four: two demes per rank
+    "schedule": dict(port="29572", first_shard=8,
+                     flags=["--n_chains", "16", "--ppde_anneal_betas", "0.25,0.5,1", "--ppde_anneal_every", "10", "--ppde_deme", "4",
+                            "--ppde_sample_every", "10", "--ppde_archive", "2"],
+                     files=_HISTORIES + [f"anneal_{k}" for k in ("parent", "pre_energy", "log_mean_w", "ess", "betas")] + _SAMPLES
+                     + _ARCHIVE),
+}
+
+
+@pytest.mark.parametrize("mode", sorted(_SHARDED_MODES))
+def test_sharded_collect_of_every_mode_equals_single_process(mode):
+    """`--ppde_shard` over two gloo ranks on one card with every optional mode on (a ladder and a schedule exclude each other, so
+    two configurations): per-chain, per-ensemble, per-deme and per-slot gathers, summed counts, local -> global chain indices and
+    the merged archive -- every file the driver writes for these modes is identical to the single-process run's."""
+    import subprocess
+    import sys
+    cfg = _SHARDED_MODES[mode]
+    with tempfile.TemporaryDirectory() as root, tempfile.TemporaryDirectory() as res1, tempfile.TemporaryDirectory() as res2:
+        synthetic.write_weights_dir(root, "TOY24", potts_seed=7)
+        common = ["--protein_weights", root, "--protein", "TOY24", "--device", "cuda:0", "--disable_MSA_transformer_scoring",
+                  "--n_iters", "40", "--seed", "5", "--log_every", "20", "--nmut_threshold", "3", "--ppde_rng", "philox",
+                  "--ppde_reversible", "--run_signature", mode, *cfg["flags"]]
+        script = os.path.join(REPO, "scripts", "directed_evolution.py")
+        r = subprocess.run([sys.executable, script, *common, "--results_path", res1], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        env = dict(os.environ, PPDE_ONE_GPU="1", PPDE_DIST_BACKEND="gloo", OMP_NUM_THREADS="2")
+        r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
+                            "127.0.0.1", "--master-port", cfg["port"], script, *common, "--results_path", res2, "--ppde_shard"],
+                           capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout + r.stderr
+        d1 = glob.glob(os.path.join(res1, "TOY24", "*"))[0]
+        d2 = glob.glob(os.path.join(res2, "TOY24", "*"))[0]
+        one = {f: np.load(os.path.join(d1, f + ".npy")) for f in cfg["files"]}
+        for f, a in one.items():
+            b = np.load(os.path.join(d2, f + ".npy"))
+            assert a.dtype == b.dtype and np.array_equal(a, b), f
+    # the modes were at work, and on both shards: an all-equal result does not come from idle ones
+    assert (one["sample_chain"] >= cfg["first_shard"]).any()
+    if mode == "ladder":
+        assert one["swap_accepts"].sum() > 0
+    else:
+        assert (one["anneal_parent"] >= cfg["first_shard"]).any()
+        assert (one["anneal_parent"] != np.arange(16)).any()
+
+
 def test_single_chain_contract_of_the_reference():
     """One chain: the reference special-cases n_chains == 1 (ppde.py:178-183) and its ensemble squeezes a single prediction to
     a scalar (nets.py:442), so `run` returns fitness_history (T+1,) next to energy_history (T+1, 1), best_x [1, L, 20],
