@@ -55,6 +55,28 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 __device__ __forceinline__ void use_here(float& v) { asm volatile("" : "+v"(v)); }
 __device__ __forceinline__ void use_here(int& v) { asm volatile("" : "+v"(v)); }
 
+// Write-through stores (sc1) for what a launch writes last and the NEXT launch reads: a plain store leaves its line dirty in the
+// XCD's L2, and the write-back of such lines stands between the launch's last instruction and the start of its successor; a
+// write-through store's bytes leave for memory when it issues. They pay only where EVERY store of the launch's tail is one: the
+// chain kernels' (0.45 us per step); converting a part of them, or the Potts kernel's stores, measured slower than plain stores
+// (profiles/r07_experiments.md). Vector stores from inline asm (hipcc's nontemporal store emits `nt`, another policy), so hipcc
+// does not count them: use only where the launch does not read the bytes back (the end of the program drains them). The 16-byte
+// form ends in s_nop 1: the store reads its data registers after it has issued.
+typedef float ppde_v4f __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void store_wt16(float4* p, const float4 v) {
+    const ppde_v4f d = {v.x, v.y, v.z, v.w};
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(d) : "memory");
+}
+__device__ __forceinline__ void store_wt4(float* p, const float v) {
+    asm volatile("global_store_dword %0, %1, off sc1" :: "v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void store_wt4(int* p, const int v) {
+    asm volatile("global_store_dword %0, %1, off sc1" :: "v"(p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void store_wt1(uint8_t* p, const uint8_t v) {
+    asm volatile("global_store_byte %0, %1, off sc1" :: "v"(p), "v"((uint32_t)v) : "memory");
+}
+
 // Touch every 64-byte line of the kernel-argument segment at kernel entry. hipcc loads a by-value argument struct
 // lazily, field group by field group, each behind its own s_waitcnt: with a 350-byte struct that is five or six
 // SERIAL scalar-cache misses before the first vector load is issued (0.6-0.9 us per launch). One dword per line,

@@ -154,10 +154,11 @@ __host__ __device__ inline size_t pas_lds_bytes(const Geom& g) {
 __host__ __device__ inline size_t pas_lib_lds_bytes(const Geom& g) { return (size_t)((g.L + 3) & ~3) * 4; }
 
 // a state byte in both forms: the row (CNN, chain kernels) and, for residues of the padded Potts window, its T4 slot
+// (write-through, like every store of the chain kernels' tails: common.h store_wt*)
 __device__ __forceinline__ void store_letter(uint8_t* rows, uint8_t* T, const Geom& g, int n_pad, int b, int l, uint8_t v) {
-    rows[(size_t)b * g.Ls + g.sh + l] = v;
+    store_wt1(rows + (size_t)b * g.Ls + g.sh + l, v);
     const int wl = l - g.i0;
-    if (g.Lp > 0 && wl >= 0 && wl < 16 * g.NC) T[state_t4_offset_dev(g.NC, n_pad, b, wl)] = v;
+    if (g.Lp > 0 && wl >= 0 && wl < 16 * g.NC) store_wt1(T + state_t4_offset_dev(g.NC, n_pad, b, wl), v);
 }
 
 // the error word lives in host memory mapped into the device (ppde_api.hip): system scope, error paths only
@@ -1032,11 +1033,11 @@ __device__ __forceinline__ void propose_body(const PasArgs& a, const RowLds& lds
     PPDE_STAMP(a.dbg, 18, stamp);
     if (tid == 0) {
         ChainRec* rc = rec_of(a, b);
-        rc->Ucur = Ub;
-        rc->dist_prop = dist;
+        store_wt4(&rc->Ucur, Ub);
+        store_wt4(&rc->dist_prop, dist);
         if (a.tr_U) a.tr_U[(size_t)it * a.n + b] = Ub;
         for (int s = Ub; s < a.mu_max; ++s) {
-            rec_flat(rc)[s] = -1;
+            store_wt4(rec_flat(rc) + s, -1);
             if (a.tr_flat) a.tr_flat[((size_t)it * a.mu_max + s) * a.n + b] = -1;
         }
     }
@@ -1233,14 +1234,14 @@ __device__ __forceinline__ void propose_body_dev(const PasArgs& a, const RowLds&
     PPDE_STAMP(a.dbg, 18, stamp);
     // forward log-probabilities of the path: a masked entry keeps 2^-23 after the clamp (ppde/utils.py:106-111), so it CAN win
     // a race; its log-probability is log(2^-23 / S3) like any other entry's
-    if (tid < Ub) rec_logp(rec_of(a, b), a.mu_max)[tid] = logf(clampp(dpw[tid] / ds3[tid]));
+    if (tid < Ub) store_wt4(rec_logp(rec_of(a, b), a.mu_max) + tid, logf(clampp(dpw[tid] / ds3[tid])));
     if (tid == 0) {
         ChainRec* rc = rec_of(a, b);
-        rc->Ucur = Ub;
-        rc->dist_prop = dist;
+        store_wt4(&rc->Ucur, Ub);
+        store_wt4(&rc->dist_prop, dist);
         if (a.tr_U) a.tr_U[(size_t)it * a.n + b] = Ub;
         for (int s = Ub; s < a.mu_max; ++s) {
-            rec_flat(rc)[s] = -1;
+            store_wt4(rec_flat(rc) + s, -1);
             if (a.tr_flat) a.tr_flat[((size_t)it * a.mu_max + s) * a.n + b] = -1;
         }
     }
@@ -1485,23 +1486,23 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
         const int l = R.l[r];
         const uint8_t v = (uint8_t)nv[r], w = (uint8_t)R.wt[r];
         const uint8_t rec = (a.rec_after_reset & reset) ? w : v;
-        if (better) a.best_state[(size_t)b * g.L + l] = rec;
+        if (better) store_wt1(a.best_state + (size_t)b * g.L + l, rec);
         if (b == a.random_chain) a.rtraj[(size_t)(it + 1) * g.L + l] = rec;
         store_letter(a.cur, a.curT, g, a.n_pad, b, l, reset ? w : v);
     }
     if (tid == 0) {
-        a.e_hist[(size_t)(it + 1) * a.n + b] = e_new;
-        a.f_hist[(size_t)(it + 1) * a.n + b] = f_new;
+        store_wt4(a.e_hist + (size_t)(it + 1) * a.n + b, e_new);
+        store_wt4(a.f_hist + (size_t)(it + 1) * a.n + b, f_new);
         ChainRec* rc = rec_of(a, b);
-        if (better) { rc->best_e = e_new; rc->best_f = f_new; rc->best_t = it + 1; }
-        rc->acc_last = acc ? 1 : 0;
-        rc->dist_cur = reset ? 0 : dist;
+        if (better) { store_wt4(&rc->best_e, e_new); store_wt4(&rc->best_f, f_new); store_wt4(&rc->best_t, it + 1); }
+        store_wt4(&rc->acc_last, acc ? 1 : 0);
+        store_wt4(&rc->dist_cur, reset ? 0 : dist);
         if (a.tr_acc) { a.tr_acc[(size_t)it * a.n + b] = acc ? 1 : 0; a.tr_logacc[(size_t)it * a.n + b] = log_acc; }
         if constexpr (DEV && !REV) { if (!(rp.s1max < INFINITY)) flag_error(a.err_flag, 1); }   // a reverse row overflowed against mref
         if (a.reuse) {                               // energy / fitness of the state the chain continues from
-            if (reset) { rc->cur_e = a.wt_e; rc->cur_f = a.wt_f; }
-            else if (acc) { rc->cur_e = e_y; rc->cur_f = f_y; }
-            else if (a.paper) { rc->cur_e = fb_e; rc->cur_f = fb_f; }
+            if (reset) { store_wt4(&rc->cur_e, a.wt_e); store_wt4(&rc->cur_f, a.wt_f); }
+            else if (acc) { store_wt4(&rc->cur_e, e_y); store_wt4(&rc->cur_f, f_y); }
+            else if (a.paper) { store_wt4(&rc->cur_e, fb_e); store_wt4(&rc->cur_f, fb_f); }
         }
     }
     PPDE_STAMP(a.dbg, 29, stamp);
@@ -1532,7 +1533,7 @@ __device__ __forceinline__ void commit_current_row(const PasArgs& a, const RowLd
             R.gv[r] = ((const float4*)src)[g4];
             if (restage) lds.G[g4] = R.gv[r];
         }
-        if (store) dst[g4] = R.gv[r];
+        if (store) store_wt16(dst + g4, R.gv[r]);
     }
 }
 
