@@ -515,29 +515,17 @@ __device__ __forceinline__ void mfma_strip(f32x4 (&acc)[RT], const float* A, int
 //       coming straight from L2 with a dozen loads in flight per thread, and applies the gate.
 // sM[f] = coefficient (0: not routed), sTs[f] = absolute arg-max row. sB (rows x ceil(FP/32) words) must be ZERO on
 // entry and may alias sD (it is dead before sD is written); rows <= 128. Ends with a barrier.
-// CNN_ROUTE_TAIL: 1 (default) = list entries of a row beyond the first four are fetched one by one; n > 1 = in batches of n with
-// all loads of a batch in flight before the first use (same sums, same order, same bits). Batches were built because rows collect
-// 7-9 routed features with seeded weights and 20-40 with the trained networks, and measured SLOWER, with either kind of weights
-// (k_experts 28.5 / 28.7 / 29.3 us for 1 / 4 / 8, A/B on one box: profiles/r05_experiments.md): the phase is bound by the
-// instructions it issues, not by that chain of L2 latencies.
-#ifndef CNN_ROUTE_TAIL
-#define CNN_ROUTE_TAIL 1
-#endif
+// The ungrouped form fetches a row's list entries beyond the first four one by one. Batches of n with all loads in flight before the
+// first use measured SLOWER (k_experts 28.5 / 28.7 / 29.3 us for 1 / 4 / 8, A/B on one box: profiles/r05_experiments.md): the
+// phase is bound by the instructions it issues, not by that chain of L2 latencies.
 
 // GROUPED (the single-launch split-precision kernels; sRows = `rows` bytes of LDS, sTot four ints): the row sums run over the rows
 // that RECEIVED a feature only (a quarter to a third of the rows receive none: their pieces are zeros and are written as such),
 // and one work item is a row and three consecutive 4-channel pieces, so that the row's extent, its first four list entries and
 // their coefficients are fetched once for three pieces (the same 12 L2 loads in flight per item as the ungrouped form has per
-// thread and round). A piece's sum still runs over its row's entries in list order: the same bits (CNN_ROUTE_GROUPED=0: A/B builds).
-#ifndef CNN_ROUTE_GROUPED_TAIL
-#define CNN_ROUTE_GROUPED_TAIL 4       // 1: entries beyond a row's first four one by one (A/B builds)
-#endif
-#ifndef CNN_ROUTE_PIECES
-#define CNN_ROUTE_PIECES 3            // 4-channel pieces per work item of the grouped row sums
-#endif
-#ifndef CNN_ROUTE_GROUPED
-#define CNN_ROUTE_GROUPED 2          // 0: ungrouped row sums; 1: grouped; 2: grouped + the backward over the compacted non-empty rows
-#endif
+// thread and round). A piece's sum still runs over its row's entries in list order: the same bits as the ungrouped form.
+// GROUPED: 0 = ungrouped row sums; 1 = grouped; 2 = grouped + the backward over the compacted non-empty rows.
+constexpr int CNN_ROUTE_PIECES = 3;            // 4-channel pieces per work item of the grouped row sums
 // acc += c * v, one rounding per term (explicit fma: the build runs with -ffp-contract=off), two components per packed instruction
 __device__ __forceinline__ void route_fma(float4& acc, const float c, const float4 v) {
     const f32x2 cc = {c, c};
@@ -667,17 +655,6 @@ __device__ __forceinline__ int cnn_route_rows(const CnnNet& net, const int rows,
 #pragma unroll
                 for (int q = 0; q < 4; ++q) route_fma(acc[j], cq[q], v[j][q]);
             }
-#if CNN_ROUTE_GROUPED_TAIL == 1
-            for (int q = 4; q < kk; ++q) {                           // rows with more than four routed features
-                const int fq = sList[rs + q];
-                const float cf = sM[fq];
-                float4 w[NP];
-#pragma unroll
-                for (int j = 0; j < NP; ++j) w[j] = We4[(size_t)fq * G4 + c4c[j]];
-#pragma unroll
-                for (int j = 0; j < NP; ++j) route_fma(acc[j], cf, w[j]);
-            }
-#else
             // rows with more than four routed features (the trained networks route 20-40 into a row): further entries four at a
             // time, exactly as the first four -- one L2 round trip per four entries instead of one per entry; same terms, same order
             for (int q0 = 4; q0 < kk; q0 += 4) {
@@ -698,7 +675,6 @@ __device__ __forceinline__ int cnn_route_rows(const CnnNet& net, const int rows,
 #pragma unroll
                     for (int q = 0; q < 4; ++q) route_fma(acc[j], cq[q], v[j][q]);
             }
-#endif
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
                 const int c4 = NP * k + j;
@@ -711,11 +687,7 @@ __device__ __forceinline__ int cnn_route_rows(const CnnNet& net, const int rows,
             }
         }
         if constexpr (GROUPED == 2) {
-#ifdef CNN_COMPACT_MIN_TILES                 // (diagnostic builds: never fewer than this many row tiles in the compacted image)
-            const int pad = min(rows, max((n_ne + 15) & ~15, 16 * CNN_COMPACT_MIN_TILES)) - n_ne;
-#else
             const int pad = ((n_ne + 15) & ~15) - n_ne;                // image rows behind the last non-empty one, up to a whole tile
-#endif
             for (int i = tid; i < pad * G4; i += NT) {
                 const int r = i / G4, c4 = i - r * G4;
                 put(n_ne + r, c4, make_float4(0.f, 0.f, 0.f, 0.f));
@@ -757,27 +729,12 @@ __device__ __forceinline__ int cnn_route_rows(const CnnNet& net, const int rows,
                 float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) route_fma(acc, c[j][q], v[j][q]);
-#if CNN_ROUTE_TAIL == 1
                 for (int q = 4; q < kk[j]; ++q) {                    // rows with more than four routed features
                     const int f = sList[rs[j] + q];
                     const float cq = sM[f];
                     const float4 w = We4[(size_t)f * G4 + c4[j]];
                     route_fma(acc, cq, w);
                 }
-#else
-                for (int q0 = 4; q0 < kk[j]; q0 += CNN_ROUTE_TAIL) {  // rows with more than four routed features: batches, in order
-                    float4 w[CNN_ROUTE_TAIL];
-                    float cq[CNN_ROUTE_TAIL];
-#pragma unroll
-                    for (int u = 0; u < CNN_ROUTE_TAIL; ++u) {
-                        const int f = min((unsigned)sList[min(rs[j] + q0 + u, last)], (unsigned)(FP - 1));
-                        w[u] = We4[(size_t)f * G4 + c4[j]];
-                        cq[u] = q0 + u < kk[j] ? sM[f] : 0.f;
-                    }
-#pragma unroll
-                    for (int u = 0; u < CNN_ROUTE_TAIL; ++u) route_fma(acc, cq[u], w[u]);
-                }
-#endif
                 const uint32_t nib = (sG[t[j] * BW + (c4[j] >> 3)] >> (4 * (c4[j] & 7))) & 0xFu;   // gate by relu'(pre1)
                 acc.x = (nib & 1u) ? acc.x : 0.f; acc.y = (nib & 2u) ? acc.y : 0.f;
                 acc.z = (nib & 4u) ? acc.z : 0.f; acc.w = (nib & 8u) ? acc.w : 0.f;
@@ -1028,12 +985,7 @@ __device__ __forceinline__ void cnn_body(const CnnArgs& a_, const int bx, const 
 // per position and 8-letter group next to the staged letters (sX[p][kq], 16 bytes with at most one bf16 1.0), so a fragment is
 // one ds_read_b128 at an immediate offset. In this orientation a lane's accumulator is (row t, 4 consecutive channels): the piece
 // bf_store4 splits into the three planes, with bias, ReLU and gate bits as in the gather form.
-#ifndef CNN_CONV_MFMA
-#define CNN_CONV_MFMA 1
-#endif
-#ifndef CNN_CONV_ROWS
-#define CNN_CONV_ROWS 1             // row tiles a wave convolves at a time
-#endif
+constexpr int CNN_CONV_ROWS = 1;    // row tiles a wave convolves at a time (three at a time was tried on top and not kept: profiles/r05_experiments.md)
 __host__ __device__ inline size_t cnn_conv_x_bytes(int T) { return (size_t)(cnn_rows(T) + CNN_MAX_K) * 64; }
 // the lane's share of the one-hot fragments of position p: letters 8 kq .. 8 kq + 7
 __device__ __forceinline__ uint4 conv_x_fragment(int letter, int kq) {
@@ -1143,7 +1095,7 @@ __device__ __forceinline__ void cnn_body_bf(const CnnArgs& a_, const int bx, con
     uint4* sX = (uint4*)(smem_raw + (((size_t)((unsigned char*)sSt - smem_raw) + ((g.L + CNN_MAX_K + 15) & ~15) + 15) & ~(size_t)15));
     int phase = 0;
     const int slot = a.slot;
-    constexpr bool CONV_MFMA = KT == 5 && CNN_CONV_MFMA;
+    constexpr bool CONV_MFMA = KT == 5;                             // (other tap counts: the gather form)
 
     [[maybe_unused]] const bool first_wg = bx == 0 && ni == 0;
     [[maybe_unused]] const bool stamp = first_wg || (bx == n_bx - 1 && ni == n_ni - 1);
@@ -1275,17 +1227,12 @@ __device__ __forceinline__ void cnn_body_bf(const CnnArgs& a_, const int bx, con
 
     // ---- route + gate (cnn_route_rows) -> the routed gradient's split planes
     uint8_t* sRows = (uint8_t*)(sX + (size_t)(rows + CNN_MAX_K) * 4);     // [rows] row order of the route + [rows] row -> image row
-    const int n_ne = cnn_route_rows<NT, true, CNN_ROUTE_GROUPED, false>(net, rows, 0, CP, 0, FP, BW, (float*)sP, sB, sG, sM, sTs, sStart, sList, (int*)(red + 12), a.dbg, first_wg, sRows);
+    const int n_ne = cnn_route_rows<NT, true, 2, false>(net, rows, 0, CP, 0, FP, BW, (float*)sP, sB, sG, sM, sTs, sStart, sList, (int*)(red + 12), a.dbg, first_wg, sRows);
     BfPre pre_b;                                                     // the backward contraction's first B fragments, across the route's closing barrier
     if constexpr (PABP) { bf_prefill(pre_b, net.WfB, KS, wave, NT / 64, JP / 16); lds_barrier(); }
     else __syncthreads();
-    // (CNN_ROUTE_GROUPED = 2: the routed gradient's image holds the non-empty rows only, in rtc row tiles)
-    constexpr bool COMPACT = CNN_ROUTE_GROUPED == 2;
-#ifdef CNN_COMPACT_MIN_TILES
-    const int rtc = COMPACT ? __builtin_amdgcn_readfirstlane(min(RT, max((n_ne + 15) >> 4, CNN_COMPACT_MIN_TILES))) : RT;
-#else
-    const int rtc = COMPACT ? __builtin_amdgcn_readfirstlane((n_ne + 15) >> 4) : RT;
-#endif
+    // (GROUPED = 2: the routed gradient's image holds the non-empty rows only, in rtc row tiles)
+    const int rtc = __builtin_amdgcn_readfirstlane((n_ne + 15) >> 4);
     PPDE_STAMP(a.dbg, sb + 5, stamp);
     PPDE_STAMP(a.dbg, sb + 7, stamp);
     PPDE_WG_STAMP(a.dbg, wg_lin, 2);
@@ -1300,8 +1247,7 @@ __device__ __forceinline__ void cnn_body_bf(const CnnArgs& a_, const int bx, con
             else keep[NKEEP - 1][rt] = acc[rt];
         }
     };
-    if constexpr (COMPACT) bf_strips_rows<RT, PABP>(sP, net.WfB, KS, wave, NT / 64, JP / 16, bwd_epi, rtc, pre_b);
-    else bf_strips_c<RT, RT, PABP>(sP, net.WfB, KS, wave, NT / 64, JP / 16, bwd_epi, pre_b);
+    bf_strips_rows<RT, PABP>(sP, net.WfB, KS, wave, NT / 64, JP / 16, bwd_epi, rtc, pre_b);
     __syncthreads();
     float* sO = (float*)sP;
 #pragma unroll
@@ -1325,18 +1271,17 @@ __device__ __forceinline__ void cnn_body_bf(const CnnArgs& a_, const int bx, con
     for (int it = tid; it < g.L * 5; it += NT) {
         const int p = it / 5, c4 = it - 5 * p;
         float4 x[KT];
-        [[maybe_unused]] int ri[KT];
+        int ri[KT];
 #pragma unroll
         for (int kp = 0; kp < KT; ++kp) {
             const int t = min(max(p - kp, 0), T - 1);
-            if constexpr (COMPACT) { ri[kp] = sRows[rows + t]; x[kp] = *(const float4*)(sO + (ri[kp] == 255 ? 0 : ri[kp]) * OS + kp * 20 + 4 * c4); }
-            else x[kp] = *(const float4*)(sO + t * OS + kp * 20 + 4 * c4);
+            ri[kp] = sRows[rows + t];
+            x[kp] = *(const float4*)(sO + (ri[kp] == 255 ? 0 : ri[kp]) * OS + kp * 20 + 4 * c4);
         }
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int kp = 0; kp < KT; ++kp) {
-            bool ok = p - kp >= 0 && p - kp < T;
-            if constexpr (COMPACT) ok = ok && ri[kp] != 255;          // (a row without a routed feature: its O row is +0 in the full form)
+            const bool ok = p - kp >= 0 && p - kp < T && ri[kp] != 255;   // (a row without a routed feature: its O row is +0 in the full form)
             v.x += ok ? x[kp].x : 0.f; v.y += ok ? x[kp].y : 0.f; v.z += ok ? x[kp].z : 0.f; v.w += ok ? x[kp].w : 0.f;
         }
         *(float4*)(out + (size_t)p * 20 + 4 * c4) = v;
@@ -1348,10 +1293,7 @@ __device__ __forceinline__ void cnn_body_bf(const CnnArgs& a_, const int bx, con
 // BF: the split-precision body (bf16 matrix pipe) instead of the exact-fp32 MFMA one
 template <int RT, int KT, int NT = CNN_NT, bool BF = false>
 // (two 512-thread workgroups share a CU up to six row tiles: four waves per SIMD, i.e. at most 128 registers)
-#ifndef CNN_BOUNDS_RELAX
-#define CNN_BOUNDS_RELAX 0
-#endif
-__global__ __launch_bounds__(NT, (RT <= 6 && NT == 512 && KT == 5 && !CNN_BOUNDS_RELAX) ? 4 : 2) void k_cnn(CnnArgs a) {
+__global__ __launch_bounds__(NT, (RT <= 6 && NT == 512 && KT == 5) ? 4 : 2) void k_cnn(CnnArgs a) {
     warm_kernargs<sizeof(CnnArgs)>();
     extern __shared__ unsigned char smem_raw[];
     if constexpr (BF) cnn_body_bf<RT, KT, NT>(a, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, smem_raw);
@@ -1370,17 +1312,11 @@ __global__ __launch_bounds__(NT, (RT <= 6 && NT == 512 && KT == 5 && !CNN_BOUNDS
 // Rows per chunk are chosen so that TWO workgroups fit a CU's LDS at GFP's width (256 padded channels): the
 // forward chunk holds [rows x channels] (64 rows: 66 KB), the backward chunk additionally [rows x 5*20] (48 rows:
 // 69 KB). With 96-row chunks a CU held one 4-wave workgroup at a time (fwd 341 us, bwd 300 us per launch at GFP).
-#ifndef CNN_CHUNK_NB
-#define CNN_CHUNK_NB 4                                // B fragment buffers of the chunk kernels' bf_strips
-#endif
+constexpr int CNN_CHUNK_NB = 4;                       // B fragment buffers of the chunk kernels' bf_strips
 #define CNN_FCH_RT 4                                  // forward: 64 rows per chunk
-#ifndef CNN_BCH_RT
-#define CNN_BCH_RT 4                                  // backward, split-precision kernels: 64-row windows (60 output positions each at five taps)
-#endif
+constexpr int CNN_BCH_RT = 4;                         // backward, split-precision kernels: 64-row windows (60 output positions each at five taps)
 #define CNN_BCH_RT_F32 3                              // backward, exact-fp32 kernels: 48-row windows (two workgroups per CU at GFP's width)
-#ifndef CNN_WIDE_FRT
-#define CNN_WIDE_FRT 4                                // forward row tiles per chunk above 128 channels
-#endif
+constexpr int CNN_WIDE_FRT = 4;                       // forward row tiles per chunk above 128 channels
 __host__ __device__ inline int cnn_fwd_chunks(int T, int RT = CNN_FCH_RT) { return (T + RT * 16 - 1) / (RT * 16); }
 __host__ __device__ inline int cnn_bwd_out_per_chunk(int KT, bool bf) { return (bf ? CNN_BCH_RT : CNN_BCH_RT_F32) * 16 - (KT - 1); }
 __host__ __device__ inline int cnn_bwd_chunks(int L, int KT, bool bf) { return (L + cnn_bwd_out_per_chunk(KT, bf) - 1) / cnn_bwd_out_per_chunk(KT, bf); }
@@ -1642,7 +1578,7 @@ __global__ __launch_bounds__(NT, 2) void k_cnn_bwd_chunk(CnnChunkArgs ca) {
     PPDE_STAMP(a.dbg, 42, stamp);
     // ---- route the features whose arg-max row lies in the window, gate (cnn_route_rows)
     // (split-precision kernels: row sums over the window's non-empty rows, three pieces per item; the row order in the slack behind sStart)
-    cnn_route_rows<NT, BF, (BF && CNN_ROUTE_GROUPED != 0) ? 1 : 0>(net, rows, r0, CP, AS, FP, BW, sD, (uint32_t*)sD, sG, sM, sTs, sStart, sList, sCnt,
+    cnn_route_rows<NT, BF, BF ? 1 : 0>(net, rows, r0, CP, AS, FP, BW, sD, (uint32_t*)sD, sG, sM, sTs, sStart, sList, sCnt,
                                                                    nullptr, false, (uint8_t*)(sStart + rows + 4));
     PPDE_STAMP(a.dbg, 43, stamp);
     // ---- O = dpre1 x Wf on the matrix cores

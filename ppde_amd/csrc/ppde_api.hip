@@ -28,6 +28,13 @@ static int fail(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
+// The environment knobs (tuning and diagnostics) are read here and nowhere else; every site keeps its value in a function-local
+// static, so a knob is read once per process, at its first use. Unset: nullptr / the default.
+static const char* env_str(const char* name) { return getenv(name); }
+static int env_int(const char* name, int dflt) {
+    const char* e = env_str(name);
+    return e ? atoi(e) : dflt;
+}
 #define HIPCHK(x)                                                                                   \
     do {                                                                                            \
         hipError_t e_ = (x);                                                                        \
@@ -219,67 +226,72 @@ struct EventPool {
 };
 static thread_local EventPool* g_potts_events = nullptr;
 
-static int launch_potts(const ppde_model* m, const States& st, int n, const EvalTargets& t, hipStream_t s,
-                        int b_off = 0, int n_sub = -1) {
-    if (n_sub < 0) n_sub = n;
-    hipEvent_t ev1 = g_potts_events ? g_potts_events->next(true) : nullptr;
-    // one launch form for every instantiation: plain, or with a stop event bound to the dispatch (in-situ timing)
-#define PPDE_PL(K) do { if (ev1) hipExtLaunchKernelGGL(K, grid, dim3(256), (uint32_t)lds, s, nullptr, ev1, 0, a, nby); \
-                        else hipLaunchKernelGGL(K, grid, dim3(256), lds, s, a, nby); } while (0)
-    ARGCHK(st.T && st.n_pad >= n + 256, "the states have no transposed copy for the Potts kernel");
+// One launch form for every expert and chain kernel: plain, or with a stop event bound to the dispatch (in-situ timing).
+template <typename... P>
+static void launch_kernel(void (*k)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, hipEvent_t stop, const P&... a) {
+    if (stop) hipExtLaunchKernelGGL(k, grid, block, (uint32_t)lds, s, nullptr, stop, 0, a...);
+    else hipLaunchKernelGGL(k, grid, block, lds, s, a...);
+}
+// A run-time int as a compile-time one: f(std::integral_constant<int, V>{}) for the V among Vs that equals v; false if none does.
+// (Kernels come out in the library in the order the source first names them. The deduced return type has this helper instantiated
+// where it is called, and the left fold instantiates f for Vs from first to last: source order here too.)
+template <int... Vs, typename F>
+static auto with_int(int v, F&& f) {
+    return (... || (v == Vs && (f(std::integral_constant<int, Vs>{}), true)));
+}
+
+static PottsArgs potts_args(const ppde_model* m, const States& st, int n, const EvalTargets& t, int b_off, int n_sub) {
     PottsArgs a{};
     a.b_off = b_off; a.n_sub = n_sub; a.dbg = t.dbg;
     a.Jt = m->d_Jt; a.h = m->d_h; a.idxT = st.T; a.n_pad = st.n_pad; a.grad = t.grad; a.epart = t.epart;
     a.slot = t.slot; a.n = n;
     a.g = m->g;
+    return a;
+}
+
+static int launch_potts(const ppde_model* m, const States& st, int n, const EvalTargets& t, hipStream_t s,
+                        int b_off = 0, int n_sub = -1) {
+    if (n_sub < 0) n_sub = n;
+    hipEvent_t ev1 = g_potts_events ? g_potts_events->next(true) : nullptr;
+    ARGCHK(st.T && st.n_pad >= n + 256, "the states have no transposed copy for the Potts kernel");
+    const PottsArgs a = potts_args(m, st, n, t, b_off, n_sub);
     int NG = potts_ng_for(n_sub);
-    static const int ng_override = []() { const char* e = getenv("PPDE_POTTS_NG"); return e ? atoi(e) : 0; }();   // tuning knob
+    static const int ng_override = env_int("PPDE_POTTS_NG", 0);   // tuning knob
     if (ng_override == 1 || ng_override == 2 || ng_override == 4) NG = ng_override;
-    static const int ring_override = []() { const char* e = getenv("PPDE_POTTS_RING"); return e ? atoi(e) : -1; }();   // tuning knob
+    static const int ring_override = env_int("PPDE_POTTS_RING", -1);   // tuning knob
     const bool ring = ring_override >= 0 ? ring_override != 0 : m->g.NC > 8;   // long windows stream through a ring
     const int tiles = m->g.Lp * 5;
     // Every window of up to 256 residues (chunk counts 1..16) has an instantiation with its chunk count as a compile-time
     // constant (potts.h NCC): trip counts, DMA piece counts and counted waits are immediates there. Resident slab 5.12 ->
     // 4.96 us at PABP size, ring 17.7 -> 16.0 us at GFP size. PPDE_POTTS_SPEC=0: the general kernels (run-time chunk count).
-    static const bool nc_spec = []() { const char* e = getenv("PPDE_POTTS_SPEC"); return !e || atoi(e) != 0; }();   // tuning knob
+    static const bool nc_spec = env_int("PPDE_POTTS_SPEC", 1) != 0;   // tuning knob
+    if (ring) NG = std::min(NG, 2);
+    const size_t lds = ring ? potts_ring_lds_bytes() : potts_lds_bytes(m->g.NC, NG);
+    const int nby = (n_sub + NG * 64 - 1) / (NG * 64);
+    auto go = [&](auto k) { launch_kernel(k, dim3(tiles * nby), dim3(256), lds, s, ev1, a, nby); };
     if (ring) {
-        NG = std::min(NG, 2);
-        const size_t lds = potts_ring_lds_bytes();
-        const int nby = (n_sub + NG * 64 - 1) / (NG * 64);
-        const dim3 grid(tiles * nby);
         ARGCHK(m->g.NC <= 32, "Potts window longer than 512 residues");
         const bool g4 = potts_groups(m->g.NC) <= 4;             // letters of <= 4 chunk groups per wave: 5 workgroups per CU
-        bool launched = false;
-        if (nc_spec && g4) {
-#define PPDE_PR(v) case v: if (NG == 1) PPDE_PL((potts_energy_grad_kernel<1, true, 4, v>)); \
-                           else PPDE_PL((potts_energy_grad_kernel<2, true, 4, v>)); launched = true; break;
-            switch (m->g.NC) { PPDE_PR(9) PPDE_PR(10) PPDE_PR(11) PPDE_PR(12) PPDE_PR(13) PPDE_PR(14) PPDE_PR(15) PPDE_PR(16) default: break; }
-#undef PPDE_PR
-        }
-        if (launched) { }
-        else if (NG == 1 && g4) PPDE_PL((potts_energy_grad_kernel<1, true, 4>));
-        else if (NG == 1) PPDE_PL((potts_energy_grad_kernel<1, true, 8>));
-        else if (g4) PPDE_PL((potts_energy_grad_kernel<2, true, 4>));
-        else PPDE_PL((potts_energy_grad_kernel<2, true, 8>));
+        const bool pinned = nc_spec && g4 && with_int<9, 10, 11, 12, 13, 14, 15, 16>(m->g.NC, [&](auto nc) {
+            constexpr int NC = decltype(nc)::value;
+            go(NG == 1 ? potts_energy_grad_kernel<1, true, 4, NC> : potts_energy_grad_kernel<2, true, 4, NC>);
+        });
+        if (pinned) { }
+        else if (NG == 1 && g4) go(potts_energy_grad_kernel<1, true, 4>);
+        else if (NG == 1) go(potts_energy_grad_kernel<1, true, 8>);
+        else if (g4) go(potts_energy_grad_kernel<2, true, 4>);
+        else go(potts_energy_grad_kernel<2, true, 8>);
     } else {
         ARGCHK(m->g.NC <= 8, "Potts window too long for the resident-slab kernel (the ring variant takes it)");
-        const size_t lds = potts_lds_bytes(m->g.NC, NG);
-        const int nby = (n_sub + NG * 64 - 1) / (NG * 64);
-        const dim3 grid(tiles * nby);
-        bool launched = false;
-        if (nc_spec && NG <= 2) {
-#define PPDE_PS(v) case v: if (NG == 1) PPDE_PL((potts_energy_grad_kernel<1, false, 2, v>)); \
-                           else PPDE_PL((potts_energy_grad_kernel<2, false, 2, v>)); launched = true; break;
-            switch (m->g.NC) { PPDE_PS(1) PPDE_PS(2) PPDE_PS(3) PPDE_PS(4) PPDE_PS(5) PPDE_PS(6) PPDE_PS(7) PPDE_PS(8) default: break; }
-#undef PPDE_PS
-        }
-        if (!launched) switch (NG) {
-            case 1: PPDE_PL(potts_energy_grad_kernel<1>); break;
-            case 2: PPDE_PL(potts_energy_grad_kernel<2>); break;
-            default: PPDE_PL(potts_energy_grad_kernel<4>); break;
-        }
+        const bool pinned = nc_spec && NG <= 2 && with_int<1, 2, 3, 4, 5, 6, 7, 8>(m->g.NC, [&](auto nc) {
+            constexpr int NC = decltype(nc)::value;
+            go(NG == 1 ? potts_energy_grad_kernel<1, false, 2, NC> : potts_energy_grad_kernel<2, false, 2, NC>);
+        });
+        if (pinned) { }
+        else if (NG == 1) go(potts_energy_grad_kernel<1>);
+        else if (NG == 2) go(potts_energy_grad_kernel<2>);
+        else go(potts_energy_grad_kernel<4>);
     }
-#undef PPDE_PL
     HIPCHK(hipGetLastError());
     return PPDE_OK;
 }
@@ -287,7 +299,7 @@ static int launch_potts(const ppde_model* m, const States& st, int n, const Eval
 // Both dense contractions of the CNN on the bf16 matrix pipe (split-precision, cnn.h bf_strips): the default.
 // PPDE_CNN_BF16=0 keeps the exact-fp32 MFMA kernels (v_mfma_f32_16x16x4_f32).
 static bool cnn_bf16() {
-    static const bool on = []() { const char* e = getenv("PPDE_CNN_BF16"); return !e || atoi(e) != 0; }();   // tuning knob
+    static const bool on = env_int("PPDE_CNN_BF16", 1) != 0;   // tuning knob
     return on;
 }
 static size_t cnn_single_lds(const ppde_model* m) {
@@ -295,7 +307,7 @@ static size_t cnn_single_lds(const ppde_model* m) {
 }
 // launch form of a supervised expert of this (padded) shape: single launch, or the forward / backward chunk kernels
 static bool cnn_single_launch_shape(int T, int CP, int FP, int J, int L) {
-    static const int chunked_override = []() { const char* e = getenv("PPDE_CNN_CHUNKED"); return e ? atoi(e) : -1; }();   // tuning knob
+    static const int chunked_override = env_int("PPDE_CNN_CHUNKED", -1);   // tuning knob
     if (chunked_override == 1) return false;
     const size_t lds = cnn_bf16() ? cnn_bf_lds_bytes(T, CP, FP, J, L) : cnn_lds_bytes(T, CP, FP, J, L);
     if (cnn_rows(T) > 16 * CNN_MAX_RT || lds > 160 * 1024 || FP > 512) return false;   // (cnn_body keeps two features per thread)
@@ -337,7 +349,7 @@ static std::string cnn_chunk_refusal(int C, int CP, int F, int FP, int J) {
 // two (45 us) at 128 chains x 3 networks; with 2 whole + 2 half units per chain every CU pairs a whole unit with a half
 // one. The cut does not depend on the batch (a chain's numbers never depend on the batch it sits in).
 static int cnn_parts(const ppde_model* m) {
-    static const bool split = []() { const char* e = getenv("PPDE_CNN_SPLIT"); return !e || atoi(e) != 0; }();   // tuning knob
+    static const bool split = env_int("PPDE_CNN_SPLIT", 1) != 0;   // tuning knob
     if (!m->has_cnn) return std::max(m->n_nets, 1);
     return (split && cnn_single_launch(m) && m->n_nets <= 3 && m->FP >= 32) ? m->n_nets + 1 : m->n_nets;
 }
@@ -374,9 +386,7 @@ static void cnn_grad_scale(float scale, float* gsc, float* gun) {
     *gun = ldexpf(1.f, e);
 }
 
-static int launch_cnn(const ppde_model* m, const States& st, int n, const EvalTargets& t, int want_grad,
-                      float scale, hipStream_t s, int b_off = 0, int n_sub = -1) {
-    if (n_sub < 0) n_sub = n;
+static CnnArgs cnn_args(const ppde_model* m, const States& st, int n, const EvalTargets& t, int want_grad, float scale, int b_off) {
     CnnArgs a{};
     a.b_off = b_off; a.dbg = t.dbg;
     for (int k = 0; k < m->n_nets; ++k) a.net[k] = m->nets[k];
@@ -385,10 +395,33 @@ static int launch_cnn(const ppde_model* m, const States& st, int n, const EvalTa
     a.slot = t.slot; a.n = n; a.want_grad = want_grad; a.scale = scale;
     cnn_grad_scale(scale, &a.gsc, &a.gun);
     a.g = m->g;
+    return a;
+}
+
+// The network shapes that have shape-pinned instantiations (PPDE_CNN_SPEC=0: the general kernels everywhere). The host selects
+// a pinned kernel only for exactly its shape: every trip count in it is a compile-time constant.
+static bool cnn_shape_spec() {
+    static const bool on = env_int("PPDE_CNN_SPEC", 1) != 0;   // tuning knob
+    return on;
+}
+static bool cnn_five_taps(const ppde_model* m) { return m->KT == 5 && m->K == 5 && m->J == 100 && m->JP == 112; }
+// backward chunks (cnn.h CnnChunkShape): 1 = the UBE4B networks, 2 = the GFP networks
+static bool cnn_is_ube4b_shape(const ppde_model* m) { return cnn_five_taps(m) && m->T == 100 && m->CP == 128 && m->F == 208 && m->FP == 208; }
+static bool cnn_is_gfp_shape(const ppde_model* m) { return cnn_five_taps(m) && m->T == 233 && m->CP == 256 && m->F == 474 && m->FP == 480; }
+// the fused launch: the PABP_YEAST networks (three in four output rows) beside a five-chunk Potts window, two chain groups
+static bool experts_is_pabp_shape(const ppde_model* m, int NG, int n_parts) {
+    return NG == 2 && m->L == 96 && m->g.NC == 5 && m->C == 96 && m->CP == 96 && m->K == 5 && m->F == 192 && m->FP == 192 && m->T == 92 &&
+           m->J == 100 && m->JP == 112 && m->n_nets == 3 && n_parts == 4;
+}
+
+static int launch_cnn(const ppde_model* m, const States& st, int n, const EvalTargets& t, int want_grad,
+                      float scale, hipStream_t s, int b_off = 0, int n_sub = -1) {
+    if (n_sub < 0) n_sub = n;
+    const CnnArgs a = cnn_args(m, st, n, t, want_grad, scale, b_off);
+    const bool bf = cnn_bf16(), k5 = m->KT == 5;
     if (!cnn_single_launch(m)) {
         // long sequences: forward chunks, then merge + backward chunks
         ARGCHK(t.cmax && t.carg && t.cgate && t.cnn_cap >= n, "CNN chunk scratch not allocated for this batch size");
-        const bool bf = cnn_bf16();
         const int frt = cnn_fwd_rt(m);
         const size_t lds_f = bf ? cnn_bf_fwd_chunk_lds(m->CP, m->FP) : cnn_fwd_chunk_lds(m->CP);
         const size_t lds_b = bf ? cnn_bf_bwd_chunk_lds(m->CP, m->FP, m->J) : cnn_bwd_chunk_lds(m->CP, m->FP, m->J);
@@ -396,77 +429,48 @@ static int launch_cnn(const ppde_model* m, const States& st, int n, const EvalTa
         ARGCHK(lds_f <= 160 * 1024 && lds_b <= 160 * 1024, cnn_chunk_refusal(m->C, m->CP, m->F, m->FP, m->J));
         CnnChunkArgs ca{a, t.cmax, t.carg, t.cgate, cnn_fwd_chunks(m->T, frt), frt * 16};
         const dim3 gf(n_sub, m->n_nets, ca.NCH), gb(n_sub, m->n_nets, want_grad ? cnn_bwd_chunks(m->L, m->KT, bf) : 1);
-        // the two long real proteins have instantiations with their network shape pinned (cnn.h CnnChunkShape)
-        static const bool shape_spec = []() { const char* e = getenv("PPDE_CNN_SPEC"); return !e || atoi(e) != 0; }();   // tuning knob
-        const bool five = m->KT == 5 && m->K == 5 && m->J == 100 && m->JP == 112;
-        const int shape = !shape_spec || !five ? 0
-                          : (m->T == 100 && m->CP == 128 && m->F == 208 && m->FP == 208) ? 1
-                          : (m->T == 233 && m->CP == 256 && m->F == 474 && m->FP == 480) ? 2 : 0;
-        if (bf) {
-            // split-precision chunks (16-bit matrix pipe): forward chunks and backward windows of 64 rows
-            // Networks of more than 128 channels (GFP: two chunk workgroups per CU by LDS) run the chunk kernels with 512 threads:
-            // four waves per SIMD hide what a block's instruction stream costs better than the second A register set of the
-            // 256-thread form (GFP + CNN 505 -> 446 us per step, A/B on one box); up to 128 channels three 256-thread workgroups
-            // share a CU and 512 threads lose (UBE4B 104.2 -> 106.6). PPDE_CNN_CHUNK_512=0 keeps 256 threads everywhere. Same bits.
-            static const bool allow512 = []() { const char* e = getenv("PPDE_CNN_CHUNK_512"); return !e || atoi(e) != 0; }();
-            const bool wide = allow512 && m->CP > 128;
-            if (wide) {
-                if (m->KT == 5) hipLaunchKernelGGL((k_cnn_fwd_chunk<5, 0, CNN_WIDE_FRT, true, 512>), gf, dim3(512), lds_f, s, ca);
-                else hipLaunchKernelGGL((k_cnn_fwd_chunk<CNN_MAX_K, 0, CNN_WIDE_FRT, true, 512>), gf, dim3(512), lds_f, s, ca);
-                if (shape == 2) hipLaunchKernelGGL((k_cnn_bwd_chunk<5, 2, true, 512>), gb, dim3(512), lds_b, s, ca);
-                else if (m->KT == 5) hipLaunchKernelGGL((k_cnn_bwd_chunk<5, 0, true, 512>), gb, dim3(512), lds_b, s, ca);
-                else hipLaunchKernelGGL((k_cnn_bwd_chunk<CNN_MAX_K, 0, true, 512>), gb, dim3(512), lds_b, s, ca);
-                HIPCHK(hipGetLastError());
-                return PPDE_OK;
-            }
-            if (m->KT == 5 && frt == 4) hipLaunchKernelGGL((k_cnn_fwd_chunk<5, 0, 4, true>), gf, dim3(256), lds_f, s, ca);
-            else if (m->KT == 5) hipLaunchKernelGGL((k_cnn_fwd_chunk<5, 0, 3, true>), gf, dim3(256), lds_f, s, ca);
-            else if (frt == 4) hipLaunchKernelGGL((k_cnn_fwd_chunk<CNN_MAX_K, 0, 4, true>), gf, dim3(256), lds_f, s, ca);
-            else hipLaunchKernelGGL((k_cnn_fwd_chunk<CNN_MAX_K, 0, 3, true>), gf, dim3(256), lds_f, s, ca);
-            if (shape == 1) hipLaunchKernelGGL((k_cnn_bwd_chunk<5, 1, true>), gb, dim3(256), lds_b, s, ca);
-            else if (shape == 2) hipLaunchKernelGGL((k_cnn_bwd_chunk<5, 2, true>), gb, dim3(256), lds_b, s, ca);
-            else if (m->KT == 5) hipLaunchKernelGGL((k_cnn_bwd_chunk<5, 0, true>), gb, dim3(256), lds_b, s, ca);
-            else hipLaunchKernelGGL((k_cnn_bwd_chunk<CNN_MAX_K, 0, true>), gb, dim3(256), lds_b, s, ca);
-            HIPCHK(hipGetLastError());
-            return PPDE_OK;
-        }
-        // (only the BACKWARD chunks: with the trip counts known the forward chunk kernel is
-        //  measured slower -- UBE4B 32.1 -> 47.3 us, GFP 244 -> 674 us per launch; the backward gains: 33.9 -> 30.1 and 125.8 -> 116.3)
-        if (shape == 1) {
-            hipLaunchKernelGGL(k_cnn_fwd_chunk<5>, gf, dim3(256), lds_f, s, ca);
-            hipLaunchKernelGGL((k_cnn_bwd_chunk<5, 1>), gb, dim3(256), lds_b, s, ca);
-        } else if (shape == 2) {
-            hipLaunchKernelGGL(k_cnn_fwd_chunk<5>, gf, dim3(256), lds_f, s, ca);
-            hipLaunchKernelGGL((k_cnn_bwd_chunk<5, 2>), gb, dim3(256), lds_b, s, ca);
-        } else if (m->KT == 5) {
-            hipLaunchKernelGGL(k_cnn_fwd_chunk<5>, gf, dim3(256), lds_f, s, ca);
-            hipLaunchKernelGGL(k_cnn_bwd_chunk<5>, gb, dim3(256), lds_b, s, ca);
+        // the two long real proteins have instantiations with their network shape pinned (cnn.h CnnChunkShape). Only the BACKWARD
+        // chunks: with the trip counts known the forward chunk kernel is measured slower -- UBE4B 32.1 -> 47.3 us, GFP 244 -> 674 us
+        // per launch; the backward gains: 33.9 -> 30.1 and 125.8 -> 116.3.
+        const int shape = !cnn_shape_spec() ? 0 : cnn_is_ube4b_shape(m) ? 1 : cnn_is_gfp_shape(m) ? 2 : 0;
+        // Split-precision chunks (16-bit matrix pipe): forward chunks and backward windows of 64 rows.
+        // Networks of more than 128 channels (GFP: two chunk workgroups per CU by LDS) run the chunk kernels with 512 threads:
+        // four waves per SIMD hide what a block's instruction stream costs better than the second A register set of the
+        // 256-thread form (GFP + CNN 505 -> 446 us per step, A/B on one box); up to 128 channels three 256-thread workgroups
+        // share a CU and 512 threads lose (UBE4B 104.2 -> 106.6). PPDE_CNN_CHUNK_512=0 keeps 256 threads everywhere. Same bits.
+        static const bool allow512 = env_int("PPDE_CNN_CHUNK_512", 1) != 0;
+        const bool wide = bf && allow512 && m->CP > 128;
+        void (*fwd)(CnnChunkArgs);
+        void (*bwd)(CnnChunkArgs);
+        if (wide) {
+            fwd = k5 ? k_cnn_fwd_chunk<5, 0, CNN_WIDE_FRT, true, 512> : k_cnn_fwd_chunk<CNN_MAX_K, 0, CNN_WIDE_FRT, true, 512>;
+            bwd = k5 ? (shape == 2 ? k_cnn_bwd_chunk<5, 2, true, 512> : k_cnn_bwd_chunk<5, 0, true, 512>) : k_cnn_bwd_chunk<CNN_MAX_K, 0, true, 512>;
+        } else if (bf) {
+            fwd = k5 ? (frt == 4 ? k_cnn_fwd_chunk<5, 0, 4, true> : k_cnn_fwd_chunk<5, 0, 3, true>)
+                     : (frt == 4 ? k_cnn_fwd_chunk<CNN_MAX_K, 0, 4, true> : k_cnn_fwd_chunk<CNN_MAX_K, 0, 3, true>);
+            bwd = shape ? (shape == 1 ? k_cnn_bwd_chunk<5, 1, true> : k_cnn_bwd_chunk<5, 2, true>)
+                        : k5 ? k_cnn_bwd_chunk<5, 0, true> : k_cnn_bwd_chunk<CNN_MAX_K, 0, true>;
+        } else if (k5) {
+            fwd = k_cnn_fwd_chunk<5>;
+            bwd = shape ? (shape == 1 ? k_cnn_bwd_chunk<5, 1> : k_cnn_bwd_chunk<5, 2>) : k_cnn_bwd_chunk<5>;
         } else {
-            hipLaunchKernelGGL((k_cnn_fwd_chunk<CNN_MAX_K>), gf, dim3(256), lds_f, s, ca);
-            hipLaunchKernelGGL((k_cnn_bwd_chunk<CNN_MAX_K>), gb, dim3(256), lds_b, s, ca);
+            fwd = k_cnn_fwd_chunk<CNN_MAX_K>;
+            bwd = k_cnn_bwd_chunk<CNN_MAX_K>;
         }
+        const dim3 block(wide ? 512 : 256);
+        launch_kernel(fwd, gf, block, lds_f, s, nullptr, ca);
+        launch_kernel(bwd, gb, block, lds_b, s, nullptr, ca);
         HIPCHK(hipGetLastError());
         return PPDE_OK;
     }
-    size_t lds = cnn_single_lds(m);
+    const size_t lds = cnn_single_lds(m);
     const dim3 grid(n_sub, a.n_parts);
-    const bool bf = cnn_bf16();
-#define PPDE_CNN(RTV)                                                                           \
-    if (bf && m->KT == 5) hipLaunchKernelGGL((k_cnn<RTV, 5, CNN_NT, true>), grid, dim3(CNN_NT), lds, s, a);           \
-    else if (bf) hipLaunchKernelGGL((k_cnn<RTV, CNN_MAX_K, CNN_NT, true>), grid, dim3(CNN_NT), lds, s, a); \
-    else if (m->KT == 5) hipLaunchKernelGGL((k_cnn<RTV, 5>), grid, dim3(CNN_NT), lds, s, a);           \
-    else hipLaunchKernelGGL((k_cnn<RTV, CNN_MAX_K>), grid, dim3(CNN_NT), lds, s, a);
-    switch (cnn_rows(m->T) / 16) {
-        case 1: PPDE_CNN(1) break;
-        case 2: PPDE_CNN(2) break;
-        case 3: PPDE_CNN(3) break;
-        case 4: PPDE_CNN(4) break;
-        case 5: PPDE_CNN(5) break;
-        case 6: PPDE_CNN(6) break;
-        case 7: PPDE_CNN(7) break;
-        default: PPDE_CNN(8) break;
-    }
-#undef PPDE_CNN
+    const int rt = cnn_rows(m->T) / 16;
+    with_int<1, 2, 3, 4, 5, 6, 7, 8>(rt >= 1 && rt <= 7 ? rt : 8, [&](auto rtc) {
+        constexpr int RT = decltype(rtc)::value;
+        launch_kernel(bf ? (k5 ? k_cnn<RT, 5, CNN_NT, true> : k_cnn<RT, CNN_MAX_K, CNN_NT, true>) : (k5 ? k_cnn<RT, 5> : k_cnn<RT, CNN_MAX_K>),
+                      grid, dim3(CNN_NT), lds, s, nullptr, a);
+    });
     HIPCHK(hipGetLastError());
     return PPDE_OK;
 }
@@ -486,50 +490,28 @@ struct ExpertsArgs {
 };
 // PABP: the CNN's shape pinned to the PABP_YEAST networks' (L = 96: 96 channels, 192 features, 5 taps, three networks in four
 // output rows, gradients wanted), so that every trip count of cnn_body is a compile-time constant (as pin_config in pas.h)
-// Block order of the fused launch. 1 (default): the two HALF units of every chain first, the whole units second -- a CU's first
-// workgroup is the older one and wins the issue arbitration (priority, then age: MI355X_MICROARCH.md), so the unit with less work
-// finishes early and the whole unit has the CU to itself for its remainder (k_experts 28.7 -> 28.1 us, A/B on one box; with the
-// whole units first the half unit crawls beside them and finishes last). 0: units in part order; 2 / 3: the Potts tiles in front
-// (measured slower). Outputs do not depend on it. PPDE_EXPERTS_PRIO: s_setprio experiments, none kept (r05_experiments.md).
-#ifndef PPDE_EXPERTS_ORDER
-#define PPDE_EXPERTS_ORDER 1
-#endif
-#ifndef PPDE_EXPERTS_PRIO
-#define PPDE_EXPERTS_PRIO 0
-#endif
-#ifndef PPDE_EXPERTS_WAVES
-#define PPDE_EXPERTS_WAVES 4                      // waves per SIMD the shape-pinned split-precision instantiation is compiled for (tuning builds: 6 = three workgroups per CU)
-#endif
+// Block order of the fused launch: the two HALF units of every chain first, the whole units second -- a CU's first workgroup is
+// the older one and wins the issue arbitration (priority, then age), so the unit with less work finishes early and the whole unit
+// has the CU to itself for its remainder (k_experts 28.7 -> 28.1 us, A/B on one box; with the whole units first the half unit
+// crawls beside them and finishes last). The Potts tiles in front measured slower, and no s_setprio experiment was kept
+// (profiles/r05_experiments.md). Outputs do not depend on the order.
+// Waves per SIMD the shape-pinned split-precision instantiation is compiled for. (Six -- 80 registers, three workgroups per CU --
+// returned wrong gradients a few times in thousands of evaluations: DESIGN.md.)
+constexpr int PPDE_EXPERTS_WAVES = 4;
 template <int RT, int NG, bool PABP = false, bool BF = false>
-__global__ __launch_bounds__(CNN_NT, (PABP && BF) ? PPDE_EXPERTS_WAVES : ((RT <= 6 && !CNN_BOUNDS_RELAX) ? 4 : 2)) void k_experts(ExpertsArgs a) {
+__global__ __launch_bounds__(CNN_NT, (PABP && BF) ? PPDE_EXPERTS_WAVES : (RT <= 6 ? 4 : 2)) void k_experts(ExpertsArgs a) {
     warm_kernargs<sizeof(ExpertsArgs)>();
 
     extern __shared__ float4 smem_experts[];
     const int n_cnn = a.cnn_bx * a.cnn_ni;
-#if PPDE_EXPERTS_ORDER >= 2                      // (tuning builds: the Potts tiles first in block order)
-    const int w = (int)blockIdx.x < a.potts_items ? n_cnn + (int)blockIdx.x : (int)blockIdx.x - a.potts_items;
-#else
     const int w = blockIdx.x;
-#endif
     if (w < n_cnn) {
         const int nw = w / a.cnn_bx;
-#if PPDE_EXPERTS_ORDER == 1 || PPDE_EXPERTS_ORDER == 3   // (tuning builds: the half units first in block order)
-        const int ni = a.cnn_ni == 4 ? ((nw + 2) & 3) : nw;
-#else
-        const int ni = nw;
-#endif
-#if PPDE_EXPERTS_PRIO == 1                       // (tuning builds: the workgroups dispatched second get the higher issue priority)
-        if (2 * w >= n_cnn) __builtin_amdgcn_s_setprio(1);
-#elif PPDE_EXPERTS_PRIO == 2
-        if (2 * w < n_cnn) __builtin_amdgcn_s_setprio(1);
-#endif
+        const int ni = a.cnn_ni == 4 ? ((nw + 2) & 3) : nw;       // (the half units first in block order)
         if constexpr (BF) cnn_body_bf<RT, 5, CNN_NT, PABP>(a.c, w - nw * a.cnn_bx, ni, a.cnn_bx, a.cnn_ni, (unsigned char*)smem_experts);
         else cnn_body<RT, 5, CNN_NT, PABP>(a.c, w - nw * a.cnn_bx, ni, a.cnn_bx, a.cnn_ni, (unsigned char*)smem_experts);
     } else {
         if (threadIdx.x >= 256) return;          // a Potts tile is the work of four waves (the barrier counts live waves only)
-#if PPDE_EXPERTS_PRIO == 3
-        __builtin_amdgcn_s_setprio(2);
-#endif
         const int v = xcd_contiguous(w - n_cnn, a.potts_items);
         potts_body<NG, false, 2, PABP ? 5 : 0>(a.p, v / a.potts_nby, v % a.potts_nby, smem_experts);
     }
@@ -538,56 +520,31 @@ __global__ __launch_bounds__(CNN_NT, (PABP && BF) ? PPDE_EXPERTS_WAVES : ((RT <=
 static int launch_experts_fused(const ppde_model* m, const States& st, int n, const EvalTargets& t, float scale,
                                 hipStream_t s, int b_off, int n_sub, bool* done) {
     *done = false;
-    static const bool enabled = []() { const char* e = getenv("PPDE_FUSE_EXPERTS"); return !e || atoi(e) != 0; }();
+    static const bool enabled = env_int("PPDE_FUSE_EXPERTS", 1) != 0;
     const int NG = potts_ng_for(n_sub);
     if (!enabled || !cnn_single_launch(m) || m->KT != 5 || NG > 2 || g_potts_events) return PPDE_OK;
     const size_t lds_c = cnn_single_lds(m), lds_p = potts_lds_bytes(m->g.NC, NG);
     const bool bf = cnn_bf16();
     if (lds_p > lds_c || 2 * lds_c > 160 * 1024 || m->g.NC > 8) return PPDE_OK;   // (needs the free second slot)
     ExpertsArgs a{};
-    CnnArgs& c = a.c;
-    c.b_off = b_off; c.dbg = t.dbg;
-    for (int k = 0; k < m->n_nets; ++k) c.net[k] = m->nets[k];
-    c.n_nets = m->n_nets; c.n_parts = cnn_parts(m); c.C = m->C; c.CP = m->CP; c.K = m->K; c.KT = m->KT; c.F = m->F; c.FP = m->FP; c.T = m->T; c.J = m->J; c.JP = m->JP;
-    c.idx = st.rows; c.gradC = t.gradC; c.fitC = t.fitC;
-    c.slot = t.slot; c.n = n; c.want_grad = 1; c.scale = scale;
-    cnn_grad_scale(scale, &c.gsc, &c.gun);
-    c.g = m->g;
-    PottsArgs& p = a.p;
-    p.b_off = b_off; p.n_sub = n_sub; p.dbg = t.dbg; p.dbg_wg_base = 1024;
-    p.Jt = m->d_Jt; p.h = m->d_h; p.idxT = st.T; p.n_pad = st.n_pad; p.grad = t.grad; p.epart = t.epart;
-    p.slot = t.slot; p.n = n;
-    p.g = m->g;
-    a.cnn_bx = n_sub; a.cnn_ni = c.n_parts;
+    a.c = cnn_args(m, st, n, t, 1, scale, b_off);
+    a.p = potts_args(m, st, n, t, b_off, n_sub);
+    a.p.dbg_wg_base = 1024;
+    a.cnn_bx = n_sub; a.cnn_ni = a.c.n_parts;
     const int CPB = NG * 64;
     a.potts_nby = (n_sub + CPB - 1) / CPB;
     a.potts_items = m->g.Lp * 5 * a.potts_nby;
     const dim3 grid(a.cnn_bx * a.cnn_ni + a.potts_items);
-    static const bool shape_spec = []() { const char* e = getenv("PPDE_CNN_SPEC"); return !e || atoi(e) != 0; }();   // tuning knob
-    if (shape_spec && NG == 2 && m->L == 96 && m->g.NC == 5 && c.C == 96 && c.CP == 96 && c.K == 5 && c.F == 192 && c.FP == 192 && c.T == 92 && c.J == 100 &&
-        c.JP == 112 && c.n_nets == 3 && c.n_parts == 4) {
-        if (bf) hipLaunchKernelGGL((k_experts<6, 2, true, true>), grid, dim3(CNN_NT), lds_c, s, a);
-        else hipLaunchKernelGGL((k_experts<6, 2, true>), grid, dim3(CNN_NT), lds_c, s, a);
-        HIPCHK(hipGetLastError());
-        *done = true;
-        return PPDE_OK;
+    auto go = [&](auto k) { launch_kernel(k, grid, dim3(CNN_NT), lds_c, s, nullptr, a); };
+    if (cnn_shape_spec() && experts_is_pabp_shape(m, NG, a.c.n_parts)) {
+        go(bf ? k_experts<6, 2, true, true> : k_experts<6, 2, true>);
+    } else {
+        const int rt = cnn_rows(m->T) / 16;
+        with_int<1, 2, 3, 4, 5, 6, 7, 8>(rt >= 1 && rt <= 7 ? rt : 8, [&](auto rtc) {
+            constexpr int RT = decltype(rtc)::value;
+            go(bf ? (NG == 1 ? k_experts<RT, 1, false, true> : k_experts<RT, 2, false, true>) : (NG == 1 ? k_experts<RT, 1> : k_experts<RT, 2>));
+        });
     }
-#define PPDE_EX(RTV)                                                                              \
-    if (bf && NG == 1) hipLaunchKernelGGL((k_experts<RTV, 1, false, true>), grid, dim3(CNN_NT), lds_c, s, a);         \
-    else if (bf) hipLaunchKernelGGL((k_experts<RTV, 2, false, true>), grid, dim3(CNN_NT), lds_c, s, a); \
-    else if (NG == 1) hipLaunchKernelGGL((k_experts<RTV, 1>), grid, dim3(CNN_NT), lds_c, s, a);         \
-    else hipLaunchKernelGGL((k_experts<RTV, 2>), grid, dim3(CNN_NT), lds_c, s, a);
-    switch (cnn_rows(m->T) / 16) {
-        case 1: PPDE_EX(1) break;
-        case 2: PPDE_EX(2) break;
-        case 3: PPDE_EX(3) break;
-        case 4: PPDE_EX(4) break;
-        case 5: PPDE_EX(5) break;
-        case 6: PPDE_EX(6) break;
-        case 7: PPDE_EX(7) break;
-        default: PPDE_EX(8) break;
-    }
-#undef PPDE_EX
     HIPCHK(hipGetLastError());
     *done = true;
     return PPDE_OK;
@@ -725,7 +682,7 @@ int ppde_transformer_time_gemm(int device, int M, int N, int K, int reps, int ep
     HIPCHK(hipSetDevice(device));
     // PPDE_TF_TIME_ROTATE=r (diagnostic): r sets of the [M][*] operands used in rotation, so that a launch finds its A rows and
     // second epilogue operand in HBM, as inside an evaluation, and not in the 256 MiB Infinity Cache the previous launch left them in
-    static const int rot = []() { const char* e = getenv("PPDE_TF_TIME_ROTATE"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : v > 8 ? 8 : v; }();
+    static const int rot = std::min(std::max(env_int("PPDE_TF_TIME_ROTATE", 1), 1), 8);
     DevBuf<half_t> A[8], B, C[8], C2[8];
     DevBuf<float> bias;
     for (int r = 0; r < rot; ++r) {
@@ -1452,7 +1409,7 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
     const size_t lds = pas_lds_bytes(m->g) + (lib ? pas_lib_lds_bytes(m->g) : 0);
     const int gpt = (m->g.N / 4 + PPDE_BLOCK - 1) / PPDE_BLOCK;
     // specialised instantiation for the common configurations (pas.h pin_config), the general kernel otherwise
-    static const bool spec_on = []() { const char* e = getenv("PPDE_CHAIN_SPEC"); return !e || atoi(e) != 0; }();   // tuning knob
+    static const bool spec_on = env_int("PPDE_CHAIN_SPEC", 1) != 0;   // tuning knob
     int spec = 0;
     if (spec_on && a.rng_mode == 1 && !a.paper && !a.rec_after_reset && !a.tr_flat && a.which == a.gwhich &&
         (a.which == 1 || a.which == 3))
@@ -1477,47 +1434,45 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
         }
     };
     hipEvent_t evs = g_potts_events ? g_potts_events->next(false) : nullptr;       // (in-situ timing: this kernel's end = the next Potts launch's start)
-#define PPDE_CL(K) do { if (evs) hipExtLaunchKernelGGL(K, dim3(n_sub), dim3(PPDE_BLOCK), (uint32_t)lds, s, nullptr, evs, 0, a); \
-                        else hipLaunchKernelGGL(K, dim3(n_sub), dim3(PPDE_BLOCK), lds, s, a); } while (0)
+    auto go = [&](auto k) { launch_kernel(k, dim3(n_sub), dim3(PPDE_BLOCK), lds, s, evs, a); };
     with_gpt([&](auto G) {
         constexpr int GP = decltype(G)::value;
         if (c->temper.on() || c->anneal.on()) {          // tempering, annealing (reversible mode): general instantiations, rows and ratio on beta[b] * E
             if (which == KP_PROPOSE) {
-                if (a.rng_mode == 0) { if (lib) PPDE_CL((k_propose_temp<GP, true, true>)); else PPDE_CL((k_propose_temp<GP, true, false>)); }
-                else { if (lib) PPDE_CL((k_propose_temp<GP, false, true>)); else PPDE_CL((k_propose_temp<GP, false, false>)); }
-            } else if (a.rng_mode == 1) { if (lib) PPDE_CL((k_accept_temp<GP, true, true>)); else PPDE_CL((k_accept_temp<GP, true, false>)); }
-            else { if (lib) PPDE_CL((k_accept_temp<GP, false, true>)); else PPDE_CL((k_accept_temp<GP, false, false>)); }
+                if (a.rng_mode == 0) { if (lib) go(k_propose_temp<GP, true, true>); else go(k_propose_temp<GP, true, false>); }
+                else { if (lib) go(k_propose_temp<GP, false, true>); else go(k_propose_temp<GP, false, false>); }
+            } else if (a.rng_mode == 1) { if (lib) go(k_accept_temp<GP, true, true>); else go(k_accept_temp<GP, true, false>); }
+            else { if (lib) go(k_accept_temp<GP, false, true>); else go(k_accept_temp<GP, false, false>); }
             return;
         }
         if (rev) {                                   // general instantiations only; the forward path keeps its kernels
-            if (which == KP_ACCEPT_PROPOSE) { if (lib) PPDE_CL((k_accept_propose_rev<GP, true>)); else PPDE_CL((k_accept_propose_rev<GP, false>)); }
-            else if (a.rng_mode == 1) { if (lib) PPDE_CL((k_accept_rev<GP, true, true>)); else PPDE_CL((k_accept_rev<GP, true, false>)); }
-            else { if (lib) PPDE_CL((k_accept_rev<GP, false, true>)); else PPDE_CL((k_accept_rev<GP, false, false>)); }
+            if (which == KP_ACCEPT_PROPOSE) { if (lib) go(k_accept_propose_rev<GP, true>); else go(k_accept_propose_rev<GP, false>); }
+            else if (a.rng_mode == 1) { if (lib) go(k_accept_rev<GP, true, true>); else go(k_accept_rev<GP, true, false>); }
+            else { if (lib) go(k_accept_rev<GP, false, true>); else go(k_accept_rev<GP, false, false>); }
             return;
         }
         if (lib) {
-            if (which == KP_ACCEPT_PROPOSE) PPDE_CL((k_accept_propose_lib<GP>));
-            else if (a.rng_mode == 0) PPDE_CL((k_propose_lib<GP, true>));
-            else PPDE_CL((k_propose_lib<GP, false>));
+            if (which == KP_ACCEPT_PROPOSE) go(k_accept_propose_lib<GP>);
+            else if (a.rng_mode == 0) go(k_propose_lib<GP, true>);
+            else go(k_propose_lib<GP, false>);
             return;
         }
         if (which == KP_PROPOSE && a.rng_mode == 0) {
-            PPDE_CL((k_propose<GP, true, 0>));
+            go(k_propose<GP, true, 0>);
             return;
         }
         with_spec([&](auto S) {
             constexpr int SP = decltype(S)::value;
             constexpr bool policy = (SP & (PAS_SPEC_REEVAL | PAS_SPEC_REUSE)) != 0;
             if (which == KP_ACCEPT_PROPOSE) {
-                if constexpr (!policy) PPDE_CL((k_accept_propose<GP, SP>));
+                if constexpr (!policy) go(k_accept_propose<GP, SP>);
             } else if constexpr (policy || SP == 0) {
-                if (which == KP_PROPOSE) PPDE_CL((k_propose<GP, false, SP>));
-                else if (SP != 0 || a.rng_mode == 1) PPDE_CL((k_accept<GP, SP, true>));
-                else PPDE_CL((k_accept<GP, 0, false>));   // replay: the reference's bits
+                if (which == KP_PROPOSE) go(k_propose<GP, false, SP>);
+                else if (SP != 0 || a.rng_mode == 1) go(k_accept<GP, SP, true>);
+                else go(k_accept<GP, 0, false>);   // replay: the reference's bits
             }
         });
     });
-#undef PPDE_CL
     HIPCHK(hipGetLastError());
     return PPDE_OK;
 }
@@ -1612,7 +1567,7 @@ static int capture_segment(ppde_chains* c, int len, bool inside_run) {
 static int capture_segments(ppde_chains* c) {
     if (!c->cfg.use_graph || c->cfg.rng_mode != 1 || !c->graphs.empty()) return PPDE_OK;
     if (c->cfg.which & 4) return PPDE_OK;           // ~900 launches per iteration, tens of milliseconds each way: nothing to gain from replay
-    static const int gl_env = []() { const char* e = getenv("PPDE_GRAPH_LEN"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 1000 ? v : 0; }();
+    static const int gl_read = env_int("PPDE_GRAPH_LEN", 0), gl_env = gl_read >= 1 && gl_read <= 1000 ? gl_read : 0;
     const int lens_default[2] = {100, 20};
     for (int k = 0; k < (gl_env ? 1 : 2); ++k) {
         const int len = gl_env ? gl_env : lens_default[k];

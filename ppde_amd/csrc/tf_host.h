@@ -137,13 +137,13 @@ static int tf_build_model(TfModel* t, int L, const ppde_tf_weights* w) {
 // 20 GiB) and larger populations are evaluated in chunks of that many chains (tf_eval): same numbers, chain by chain.
 // attention backward with the dK / dV products handed to key owners (tf_attn_bwd_ko: three workgroups per CU; 117 us per launch
 // against 151 at config 5's shape); PPDE_TF_ATT_KO=0: every wave accumulates dK / dV of all keys (tf_attn_bwd)
-static bool tf_att_key_owner() { static const bool on = []() { const char* e = getenv("PPDE_TF_ATT_KO"); return !e || atoi(e) != 0; }(); return on; }
-static bool tf_use_160() { static const bool on = []() { const char* e = getenv("PPDE_TF_160"); return !e || atoi(e) != 0; }(); return on; }
+static bool tf_att_key_owner() { static const bool on = env_int("PPDE_TF_ATT_KO", 1) != 0; return on; }
+static bool tf_use_160() { static const bool on = env_int("PPDE_TF_160", 1) != 0; return on; }
 // rows of the padded token dimension: whole 128-row tiles, whole 160-row tiles too where those are in use (640 = lcm), and whole
 // 256-row tiles only when the opt-in 256-row GEMM is on (PPDE_TF_BIG: 1280 = lcm(160, 256)); a wild-type evaluation (104 rows)
 // then runs 640 rows instead of 1280
 static int tf_pad_rows(int M) {
-    static const bool big = []() { const char* e = getenv("PPDE_TF_BIG"); return e && atoi(e) != 0; }();
+    static const bool big = env_int("PPDE_TF_BIG", 0) != 0;
     const int g = tf_use_160() ? (big ? 1280 : 640) : (big ? 256 : 128);
     return (M + g - 1) / g * g;
 }
@@ -155,7 +155,7 @@ static size_t tf_bytes_per_chain(const TfModel* t) {
     return t->layers * per_layer + shared;
 }
 static int tf_chunk_cap(const TfModel* t) {
-    static const double gb = []() { const char* e = getenv("PPDE_TF_WORK_GB"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 48.0; }();
+    static const double gb = []() { const char* e = env_str("PPDE_TF_WORK_GB"); const double v = e ? atof(e) : 0.0; return v > 0.0 ? v : 48.0; }();
     const double cap = gb * 1073741824.0 / (double)tf_bytes_per_chain(t);
     return cap < 1.0 ? 1 : cap > 1048576.0 ? 1048576 : (int)cap;
 }
@@ -203,7 +203,7 @@ static int tf_gemm(hipStream_t s, const half_t* A, const half_t* B, half_t* C, i
     // 256-row tiles (tf_gemm_big): one 8-wave workgroup per CU, half (TN = 256) or three quarters (TN = 128) of the L2 -> LDS
     // traffic per flop of the 128 x 128 kernel. Opt-in tuning knob (measured level with or behind the 128 x 128 kernel, tf.h):
     // PPDE_TF_BIG=1 uses it wherever the shape allows, =256 / =128 only with that column tile. Same bits either way.
-    static const int big = []() { const char* e = getenv("PPDE_TF_BIG"); return e ? atoi(e) : 0; }();
+    static const int big = env_int("PPDE_TF_BIG", 0);
     if (big && M % 256 == 0 && K % 128 == 0 && N >= 256) {
         // (the GELU epilogue has two results per element since it stores GELU' for the backward: next to the 128 accumulators of
         //  a 256-wide tile that spills, so this epilogue takes the 128-wide tile)
@@ -230,7 +230,7 @@ static int tf_gemm(hipStream_t s, const half_t* A, const half_t* B, half_t* C, i
         // the A rows touched ahead into L2 (tf_gemm160<EPI, true>): in situ -10 us on the q|k|v input gradient, -6 on the output
         // projection's, -2..-5 on the forward GEMMs, +4.5 on the GELU' epilogue (which therefore keeps the plain loop);
         // PPDE_TF_TOUCH=0 switches it off. Same bits.
-        static const int touch = []() { const char* e = getenv("PPDE_TF_TOUCH"); return e ? atoi(e) : 1; }();
+        static const int touch = env_int("PPDE_TF_TOUCH", 1);
         if (touch >= 2 || (touch && EPI != TF_EPI_GELU_BWD)) hipLaunchKernelGGL((tf_gemm160<EPI, true>), dim3(std::min(tiles8, 512)), dim3(256), tf_gemm160_lds(), s, g);
         else hipLaunchKernelGGL((tf_gemm160<EPI, false>), dim3(std::min(tiles8, 512)), dim3(256), tf_gemm160_lds(), s, g);
         HIPCHK(hipGetLastError());
@@ -238,7 +238,7 @@ static int tf_gemm(hipStream_t s, const half_t* A, const half_t* B, half_t* C, i
     }
     // staged k depth x LDS buffers (tuning knob PPDE_TF_GEMM=64x2|64x3|32x2|32x3|32x4|64x2w8|32x3w8; default: the measured optimum)
     static const int variant = []() {
-        const char* e = getenv("PPDE_TF_GEMM");
+        const char* e = env_str("PPDE_TF_GEMM");
         if (!e) return TF_GEMM_DEFAULT;
         if (!strcmp(e, "64x2")) return 0; if (!strcmp(e, "64x3")) return 1; if (!strcmp(e, "32x2")) return 2;
         if (!strcmp(e, "32x3")) return 3; if (!strcmp(e, "32x4")) return 4; if (!strcmp(e, "64x2w8")) return 5;
@@ -246,7 +246,7 @@ static int tf_gemm(hipStream_t s, const half_t* A, const half_t* B, half_t* C, i
         return TF_GEMM_DEFAULT;
     }();
     // persistent workgroups: at most two per CU (tuning knob PPDE_TF_PERSIST=0: one workgroup per tile), a multiple of 8
-    static const bool persist = []() { const char* e = getenv("PPDE_TF_PERSIST"); return !e || atoi(e) != 0; }();
+    static const bool persist = env_int("PPDE_TF_PERSIST", 1) != 0;
     const int tiles = (M >> 7) * (N >> 7), tiles8 = (tiles + 7) & ~7;
     const dim3 grid(persist ? std::min(tiles8, 512) : tiles8);
 #define TF_LAUNCH(BKV, STV) { constexpr size_t lds_ = tf_gemm_lds<BKV, STV>(); hipLaunchKernelGGL((tf_gemm_nt<EPI, BKV, STV, 4>), grid, dim3(256), lds_, s, g); }
@@ -270,7 +270,7 @@ static int tf_ln(hipStream_t s, bool bwd, const half_t* x, half_t* y, const floa
     TfLnArgs a{x, y, gamma, beta, mean, rstd, dy, gres, M, D, ld, out_scale};
     ARGCHK(D % 8 == 0 && D <= TF_LN_MAXD, "layer-norm width");
     // sixteen lanes per row (tf_ln_fwd16 / tf_ln_bwd16) where a lane's share is at most 10 chunks; PPDE_TF_LN16=0: one row per wavefront
-    static const bool ln16 = []() { const char* e = getenv("PPDE_TF_LN16"); return !e || atoi(e) != 0; }();
+    static const bool ln16 = env_int("PPDE_TF_LN16", 1) != 0;
     const int nch = ((D >> 3) + 15) / 16;
     // (measured at D = 640: forward 15.6 -> 14.0 us per launch, backward 24.7 either way -- it moves 136 MB at 5.5 TB/s; the
     //  backward keeps the sixteen-lane form only while a lane's three row copies fit 128 registers)
