@@ -339,6 +339,61 @@ int ppde_chains_annealing_read(ppde_chains* c, int first_event, int n_events,
                                double* log_mean_w /* [n_events][n / D] */, double* ess /* [n_events][n / D] */,
                                float* beta_now /* [n] */);
 
+/* Recombination (off by default; needs reversible mode): every `every`-th iteration the chains of a deme are paired and each
+ * pair proposes to exchange a segment of open residues -- a Metropolis move on the pair with a symmetric proposal, which keeps
+ * the product law prod_i exp(E(x_i)) / Z of the reversible chains invariant (the crossover of evolutionary Monte Carlo, Liang &
+ * Wong 2000; DNA shuffling in the laboratory). It excludes tempering, annealing, paper_results and n_streams > 1.
+ *   demes: D chains with consecutive GLOBAL indices g = chain_offset + local index; D even, D >= 2;
+ *   open list: the residues l of [min_pos, max_pos] in increasing order -- with a design library only those whose word is not 0;
+ *     S_o = their number. Only these are ever exchanged; frozen residues stay with their chain;
+ *   events: iteration `it` (0-based) is event s = (it + 1) / every - 1 when (it + 1) % every == 0; events_cap = max_steps / every.
+ *     The event runs behind the accept phase of that iteration and in front of the observers;
+ *   pairing (round robin, circle method): m = D - 1, r = s mod m; slot m of the deme pairs with slot r, slot i < m, i != r with
+ *     (2r - i) mod m. A perfect matching; every two slots meet once in m consecutive events. The lower slot of a pair is a, the
+ *     other b;
+ *   draw, one per pair: Philox4x32-10 at counter (global index of a, it, 0x40000002, 0) -- a stream nothing else draws from, in
+ *     both rng_modes -- gives x, y, z, w; i1 = mulhi32(x, S_o), i2 = mulhi32(y, S_o), lo = min, hi = max, u = the 24-bit uniform
+ *     of z; the segment = the open residues open[lo..hi];
+ *   children: a' = a with b's letters at the segment's residues, b' = b with a's. The same draw on (a', b') gives (a, b) back.
+ *     differ = the segment residues at which a and b differ; child_dist = each child's mutation count against the wild type;
+ *   evaluation: both children's whole rows go to the proposal slot and the run's expert evaluation of that slot follows (the same
+ *     `which`); E', f' = the proposal slot's energy and fitness;
+ *   decision, in fp32 and in this order, E_a, E_b = the post-accept energies (history row it + 1): d = (E'_a - E_a) + (E'_b - E_b);
+ *     outcome 3: an E' is not finite (rejected); 2: a mutation cap is set and a child_dist >= nmut_threshold (rejected, never through
+ *     u); 1: expf(d) >= u (accepted); 0: rejected by u. A pair with differ = 0 takes the same path (d = 0: accepted);
+ *   on acceptance each of the two slots takes from its child everything the next iteration and the observers read for a chain: the
+ *     state (and its transposed copy), the energy, fitness and mutation count it continues from, its gradient row under gradient
+ *     reuse, row it + 1 of both histories and of the random trajectory for the recorded chain, the running best by the accept
+ *     phase's strict rule. The last accept bit and the traces stay the slot's own Metropolis result. Row it + 1 and
+ *     ppde_chains_peek describe the population AFTER the event;
+ *   recorded per event, [events_cap] rows of [n]: partner int32 (LOCAL index), lo, hi int32 (indices into the open list), differ,
+ *     child_dist int32, outcome uint8, log_ratio fp32 (d, the same in both slots of a pair), pre_energy, child_energy fp32;
+ *   results do not depend on the sharding.
+ * The host decides which iterations are events: only there are three more launches enqueued (ppde_amd/csrc/recombine.h: the
+ * children, the experts on the proposal slot, the decision), behind a plain accept kernel; nothing fuses across an event. Captured
+ * graph segments have lengths that are multiples of `every` (every * floor(100 / every) and `every` itself up to 100, `every` up
+ * to 1000, none beyond; PPDE_GRAPH_LEN only when it is such a multiple) and are replayed only from positions that are multiples of
+ * `every`; ppde_chains_run issues iterations eagerly up to the next such position. A run without the mode enqueues nothing new and
+ * makes no additional runtime call. Valid between ppde_chains_create and ppde_chains_init, and after ppde_chains_set_library;
+ * NULL clears it. PPDE_ERR_INVALID with a message, the object unchanged: after init; reversible mode not on; tempering or
+ * annealing set; deme odd or < 2; n_chains or chain_offset no multiple of deme; every < 1; events_cap == 0; n_streams > 1. While it
+ * is set, ppde_chains_set_library, ppde_chains_set_tempering, ppde_chains_set_annealing and ppde_chains_set_reversible(c, 0) are
+ * PPDE_ERR_INVALID. A failed allocation is PPDE_ERR_HIP and leaves nothing half-set. */
+typedef struct {
+    int32_t deme;        /* D, even, >= 2 */
+    int32_t every;       /* >= 1 */
+} ppde_recombine_config;
+int ppde_chains_set_recombination(ppde_chains* c, const ppde_recombine_config* cfg /* NULL clears */);
+/* Deme size, the open list, event capacity and the events that have happened (follows ppde_chains_steps_done). Synchronises; any
+ * pointer may be NULL. PPDE_ERR_INVALID without the mode or before init. */
+int ppde_chains_recombination_shape(ppde_chains* c, int32_t* deme, int32_t* n_open, int32_t* open_sites /* [n_open] or NULL */,
+                                    int32_t* events_cap, int32_t* events_done);
+/* Events [first_event, first_event + n_events) to the host, [n_events][n] each. Synchronises; any pointer may be NULL.
+ * PPDE_ERR_INVALID without the mode, before init, or for events beyond events_done. */
+int ppde_chains_recombination_read(ppde_chains* c, int first_event, int n_events,
+                                   int32_t* partner, int32_t* lo, int32_t* hi, int32_t* differ, int32_t* child_dist,
+                                   uint8_t* outcome, float* log_ratio, float* pre_energy, float* child_energy);
+
 /* Recorder (off by default): thinned samples of the population and per-site letter counts, written on the device inside the
  * iteration loop (one more kernel behind the accept phase -- behind the swap, with tempering -- of every iteration of a recording
  * run; no host round trip; valid under graph replay and eager issue alike). A run without a recorder enqueues nothing new.

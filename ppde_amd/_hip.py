@@ -49,6 +49,11 @@ class AnnealConfig(C.Structure):
     _fields_ = [("deme", C.c_int32), ("every", C.c_int32), ("n_stages", C.c_int32), ("beta", C.POINTER(C.c_float))]
 
 
+class RecombineConfig(C.Structure):
+    """ppde_recombine_config (include/ppde_hip.h)."""
+    _fields_ = [("deme", C.c_int32), ("every", C.c_int32)]
+
+
 class TfWeights(C.Structure):
     """ppde_tf_weights (include/ppde_hip.h): host pointers to ESM-2's fp32 parameters."""
     _PER_LAYER = ("q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "o_w", "o_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b",
@@ -89,6 +94,9 @@ SIGNATURES = {
     "ppde_chains_set_annealing": (_i, [_p, C.POINTER(AnnealConfig)]),
     "ppde_chains_annealing_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ppde_chains_annealing_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
+    "ppde_chains_set_recombination": (_i, [_p, C.POINTER(RecombineConfig)]),
+    "ppde_chains_recombination_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ppde_chains_recombination_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "ppde_chains_set_recorder": (_i, [_p, C.POINTER(RecordConfig)]),
     "ppde_chains_recorder_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ppde_chains_recorder_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),

@@ -21,6 +21,7 @@
 #include "archive.h"
 #include "stats.h"
 #include "anneal.h"
+#include "recombine.h"
 
 static thread_local std::string g_err;
 
@@ -1159,6 +1160,19 @@ struct Annealing {
     int events_done(int steps_done) const { return std::min(cap, steps_done / every); }
 };
 
+// recombination (ppde_chains_set_recombination)
+struct Recombination {
+    int D = 0, every = 0, cap = 0;               // deme size, iterations per event, events_cap
+    std::vector<int32_t> open;                   // the open list: residues of [min_pos, max_pos] the library leaves open, increasing
+    DevBuf<int> open_dev;                        // [n_open]
+    DevBuf<int> partner, lo, hi, differ, child_dist;   // [events_cap][n] each
+    DevBuf<uint8_t> outcome;
+    DevBuf<float> log_ratio, pre, child;
+    bool on() const { return open_dev.p != nullptr; }
+    int events_done(int steps_done) const { return std::min(cap, steps_done / every); }
+    bool event(int it) const { return (it + 1) % every == 0; }   // (it: absolute, or relative to a multiple of every)
+};
+
 // recorder (ppde_chains_set_recorder)
 struct Recorder {
     ppde_record_config cfg{};
@@ -1253,6 +1267,7 @@ struct ppde_chains {
     bool reversible = false;                     // ppde_chains_set_reversible: the accept phases run the *_rev kernels
     Tempering temper;
     Annealing anneal;
+    Recombination recomb;
     Recorder recorder;
     PairCounts pairs;
     Archive archive;
@@ -1396,6 +1411,25 @@ static EvalTargets chain_targets(const ppde_chains* c, int slot) {
     return t;
 }
 
+// the recombination event behind the accept phase of iteration it_base + it_local (recombine.h): the children of every pair into
+// the proposal slot, the run's expert evaluation of that slot, the decision and the hand-over. Every chain of the object.
+static int launch_cross(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
+    const Recombination& rc = c->recomb;
+    CrossArgs r{};
+    r.p = chain_args(c);
+    r.p.it_base = it_base; r.p.it_local = it_local;
+    r.D = rc.D; r.every = rc.every; r.cap = rc.cap; r.n_open = (int)rc.open.size();
+    r.open = rc.open_dev; r.partner = rc.partner; r.lo = rc.lo; r.hi = rc.hi; r.differ = rc.differ; r.child_dist = rc.child_dist;
+    r.outcome = rc.outcome; r.log_ratio = rc.log_ratio; r.pre_energy = rc.pre; r.child_energy = rc.child;
+    hipLaunchKernelGGL(k_cross_propose, dim3(c->n / 2), dim3(CROSS_BLOCK), 0, s, r);
+    HIPCHK(hipGetLastError());
+    int e = eval_experts(c->m, c->cfg.which, prop_states(c), c->n, chain_targets(c, 1), 1, s, 0, c->n);
+    if (e) return e;
+    hipLaunchKernelGGL(k_cross_accept, dim3(c->n / 2), dim3(CROSS_BLOCK), 0, s, r);
+    HIPCHK(hipGetLastError());
+    return PPDE_OK;
+}
+
 enum ChainKernel { KP_PROPOSE, KP_ACCEPT, KP_ACCEPT_PROPOSE };
 
 static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs& a, int n_sub, hipStream_t s) {
@@ -1481,6 +1515,8 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
 // Re-evaluating mode: EG(x) P EG(y) A per iteration. Reuse mode: P, then EG(y) + fused [accept | next propose].
 // Tempering: [EG(x)] P EG(y) A S, never fused: the next proposal must see the post-swap beta, the swap the post-accept energy.
 // Annealing: the same flow with the two selection kernels in the swap's place.
+// Recombination: on the host-chosen event iterations the event's three launches follow a plain accept kernel, and the next iteration
+// starts with a plain propose launch (nothing fuses across an event); everywhere else the flow is that of the run without the mode.
 static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int first_local, int count, const int* U,
                               const float* q, const float* u, int mu_cap = 0) {
     const ppde_model* m = c->m;
@@ -1491,21 +1527,24 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
     if (mu_cap > 0) a.mu_cap = mu_cap;              // caller-supplied noise holds only max_u[i] sub-steps of variates
     const bool fuse = c->cfg.reuse_grad && c->cfg.rng_mode == 1 && !c->temper.on() && !c->anneal.on();
     int rc;
+    bool after_event = false;                       // the previous iteration of this call ended with a recombination event
     for (int i = 0; i < count; ++i) {
         a.it_local = first_local + i;
+        const bool event = c->recomb.on() && c->recomb.event(a.it_local);
         if (!c->cfg.reuse_grad) {   // energy and gradient at the current state (ppde.py:79)
             rc = eval_experts(m, c->cfg.which, cur_states(c), c->n, chain_targets(c, 0), 1, s, b_off, n_sub);
             if (rc) return rc;
         }
-        if (!fuse || i == 0) {
+        if (!fuse || i == 0 || after_event) {
             rc = launch_chain_kernel(c, KP_PROPOSE, a, n_sub, s);
             if (rc) return rc;
         }
         // energy and gradient at the proposal (ppde.py:119)
         rc = eval_experts(m, c->cfg.which, prop_states(c), c->n, chain_targets(c, 1), 1, s, b_off, n_sub);
         if (rc) return rc;
-        rc = launch_chain_kernel(c, (fuse && i + 1 < count) ? KP_ACCEPT_PROPOSE : KP_ACCEPT, a, n_sub, s);
+        rc = launch_chain_kernel(c, (fuse && i + 1 < count && !event) ? KP_ACCEPT_PROPOSE : KP_ACCEPT, a, n_sub, s);
         if (rc) return rc;
+        after_event = event;
         // what follows runs on the object's one stream and covers every chain of it: the swap or the selection, then the observers,
         // which see the population those left
         if (c->temper.on()) {
@@ -1513,6 +1552,7 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
             HIPCHK(hipGetLastError());
         }
         if (c->anneal.on() && (rc = launch_select(c, it_base, a.it_local, s))) return rc;
+        if (event && (rc = launch_cross(c, it_base, a.it_local, s))) return rc;
         if (c->recorder.on() && (rc = launch_record(c, it_base, a.it_local, s))) return rc;
         if (c->pairs.on() && (rc = launch_pairs(c, it_base, a.it_local, s))) return rc;      // (set only next to a recorder)
         if (c->archive.on() && (rc = launch_archive(c, it_base, a.it_local, s))) return rc;
@@ -1568,6 +1608,20 @@ static int capture_segments(ppde_chains* c) {
     if (!c->cfg.use_graph || c->cfg.rng_mode != 1 || !c->graphs.empty()) return PPDE_OK;
     if (c->cfg.which & 4) return PPDE_OK;           // ~900 launches per iteration, tens of milliseconds each way: nothing to gain from replay
     static const int gl_read = env_int("PPDE_GRAPH_LEN", 0), gl_env = gl_read >= 1 && gl_read <= 1000 ? gl_read : 0;
+    if (c->recomb.on()) {
+        // a segment holds its events at fixed places: its length is a multiple of `every`, and it is replayed from such positions only
+        const int every = c->recomb.every;
+        std::vector<int> lens;
+        if (gl_env) { if (gl_env % every == 0) lens.push_back(gl_env); }
+        else if (every <= 100) { lens.push_back(every * (100 / every)); if (lens[0] != every) lens.push_back(every); }
+        else if (every <= 1000) lens.push_back(every);
+        for (int len : lens) {
+            if (len > c->T) continue;
+            int rc = capture_segment(c, len, false);
+            if (rc) return rc;
+        }
+        return PPDE_OK;
+    }
     const int lens_default[2] = {100, 20};
     for (int k = 0; k < (gl_env ? 1 : 2); ++k) {
         const int len = gl_env ? gl_env : lens_default[k];
@@ -1677,6 +1731,8 @@ int ppde_chains_destroy(ppde_chains* c) {
 int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host) {
     ARGCHK(c, "null argument");
     ARGCHK(!c->initialised, "ppde_chains_set_library: the library must be set before ppde_chains_init (its graphs hold the pointer)");
+    ARGCHK(!c->recomb.on(), "ppde_chains_set_library: recombination is set and holds the open list of the library there was; clear it first "
+                            "(ppde_chains_set_recombination(c, NULL))");
     const ppde_model* m = c->m;
     HIPCHK(hipSetDevice(c->device));
     if (!allowed_host) {                            // clear
@@ -1712,6 +1768,8 @@ int ppde_chains_set_reversible(ppde_chains* c, int on) {
                                   "ppde_chains_set_tempering(c, 0, NULL, 0) first)");
     ARGCHK(on || !c->anneal.on(), "ppde_chains_set_reversible: annealing is set and needs reversible mode (clear it with "
                                   "ppde_chains_set_annealing(c, NULL) first)");
+    ARGCHK(on || !c->recomb.on(), "ppde_chains_set_reversible: recombination is set and needs reversible mode (clear it with "
+                                  "ppde_chains_set_recombination(c, NULL) first)");
     c->reversible = on != 0;
     return PPDE_OK;
 }
@@ -1725,6 +1783,8 @@ int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_hos
                            "(ppde_chains_set_stats(c, NULL))");
     ARGCHK(!c->anneal.on(), "ppde_chains_set_tempering: annealing is set (a schedule and a ladder cannot be combined); clear it first "
                             "(ppde_chains_set_annealing(c, NULL))");
+    ARGCHK(!c->recomb.on(), "ppde_chains_set_tempering: recombination is set (its decision takes no beta per chain); clear it first "
+                            "(ppde_chains_set_recombination(c, NULL))");
     HIPCHK(hipSetDevice(c->device));
     if (n_rungs == 0 || !beta_host) {               // clear
         c->temper = {};
@@ -1767,6 +1827,8 @@ int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_hos
 int ppde_chains_set_annealing(ppde_chains* c, const ppde_anneal_config* cfg) {
     ARGCHK(c, "null argument");
     ARGCHK(!c->initialised, "ppde_chains_set_annealing: the schedule must be set before ppde_chains_init (its graphs hold the kernel choice)");
+    ARGCHK(!c->recomb.on(), "ppde_chains_set_annealing: recombination is set (its decision takes no beta per chain); clear it first "
+                            "(ppde_chains_set_recombination(c, NULL))");
     if (!cfg) {                                     // clear
         HIPCHK(hipSetDevice(c->device));
         c->anneal = {};
@@ -1836,6 +1898,99 @@ int ppde_chains_annealing_read(ppde_chains* c, int first_event, int n_events, in
     if (log_mean_w && k) HIPCHK(hipMemcpy(log_mean_w, c->anneal.lmw + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
     if (ess && k) HIPCHK(hipMemcpy(ess, c->anneal.ess + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
     if (beta_now) HIPCHK(hipMemcpy(beta_now, c->anneal.beta, n * sizeof(float), hipMemcpyDeviceToHost));
+    return PPDE_OK;
+}
+
+int ppde_chains_set_recombination(ppde_chains* c, const ppde_recombine_config* cfg) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_recombination: the mode must be set before ppde_chains_init (its graphs hold the events)");
+    if (!cfg) {                                     // clear
+        HIPCHK(hipSetDevice(c->device));
+        c->recomb = {};
+        return PPDE_OK;
+    }
+    ARGCHK(c->reversible, "ppde_chains_set_recombination: recombination needs reversible mode (ppde_chains_set_reversible): only there "
+                          "do the chains have the law exp(E)/Z whose product the exchange keeps");
+    ARGCHK(!c->temper.on(), "ppde_chains_set_recombination: tempering is set (the decision takes no beta per chain); clear it first "
+                            "(ppde_chains_set_tempering(c, 0, NULL, 0))");
+    ARGCHK(!c->anneal.on(), "ppde_chains_set_recombination: annealing is set (the decision takes no beta per chain); clear it first "
+                            "(ppde_chains_set_annealing(c, NULL))");
+    ARGCHK(!c->cfg.paper_results, "ppde_chains_set_recombination: paper_results is not supported");
+    ARGCHK(cfg->deme >= 2 && cfg->deme % 2 == 0, "ppde_chains_set_recombination: deme must be even and >= 2 (the chains of a deme are paired)");
+    ARGCHK(c->n % cfg->deme == 0, "ppde_chains_set_recombination: n_chains must be a multiple of deme (demes of consecutive chains)");
+    ARGCHK(c->cfg.chain_offset % (uint64_t)cfg->deme == 0, "ppde_chains_set_recombination: chain_offset must be a multiple of deme (a deme "
+                                                           "may not straddle two shards)");
+    ARGCHK(cfg->every >= 1, "ppde_chains_set_recombination: every must be >= 1");
+    const int cap = c->T / cfg->every;
+    ARGCHK(cap >= 1, "ppde_chains_set_recombination: no event would fit (events_cap = max_steps / every is 0)");
+    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_recombination: n_streams > 1 is not supported (the exchange "
+                                                            "couples the chains of a deme)");
+    HIPCHK(hipSetDevice(c->device));
+    // allocate everything first: a failure leaves the object as it was
+    const int L = c->m->L;
+    std::vector<uint32_t> words;
+    if (c->allowed) {
+        words.resize((size_t)L);
+        HIPCHK(hipMemcpy(words.data(), c->allowed, (size_t)L * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    Recombination t;
+    t.D = cfg->deme; t.every = cfg->every; t.cap = cap;
+    for (int l = c->cfg.min_pos; l <= c->cfg.max_pos; ++l)
+        if (words.empty() || words[(size_t)l]) t.open.push_back(l);
+    ARGCHK(!t.open.empty(), "ppde_chains_set_recombination: no open residue in [min_pos, max_pos]");
+    const size_t cells = (size_t)cap * c->n;
+    hipError_t e = t.open_dev.alloc(t.open.size());
+    if (e == hipSuccess) e = hipMemcpy(t.open_dev, t.open.data(), t.open.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = t.partner.alloc(cells);
+    if (e == hipSuccess) e = t.lo.alloc(cells);
+    if (e == hipSuccess) e = t.hi.alloc(cells);
+    if (e == hipSuccess) e = t.differ.alloc(cells);
+    if (e == hipSuccess) e = t.child_dist.alloc(cells);
+    if (e == hipSuccess) e = t.outcome.alloc(cells);
+    if (e == hipSuccess) e = t.log_ratio.alloc(cells);
+    if (e == hipSuccess) e = t.pre.alloc(cells);
+    if (e == hipSuccess) e = t.child.alloc(cells);
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_recombination: device allocation: ") + hipGetErrorString(e));
+    c->recomb = std::move(t);
+    return PPDE_OK;
+}
+
+int ppde_chains_recombination_shape(ppde_chains* c, int32_t* deme, int32_t* n_open, int32_t* open_sites, int32_t* events_cap,
+                                    int32_t* events_done) {
+    ARGCHK(c, "null argument");
+    ARGCHK(c->recomb.on(), "ppde_chains_recombination_shape: no recombination was set (ppde_chains_set_recombination)");
+    ARGCHK(c->initialised, "chains not initialised");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    if (deme) *deme = c->recomb.D;
+    if (n_open) *n_open = (int32_t)c->recomb.open.size();
+    if (open_sites) std::copy(c->recomb.open.begin(), c->recomb.open.end(), open_sites);
+    if (events_cap) *events_cap = c->recomb.cap;
+    if (events_done) *events_done = c->recomb.events_done(c->steps_done);
+    return PPDE_OK;
+}
+
+int ppde_chains_recombination_read(ppde_chains* c, int first_event, int n_events, int32_t* partner, int32_t* lo, int32_t* hi,
+                                   int32_t* differ, int32_t* child_dist, uint8_t* outcome, float* log_ratio, float* pre_energy,
+                                   float* child_energy) {
+    ARGCHK(c && c->recomb.on(), "ppde_chains_recombination_read: no recombination was set (ppde_chains_set_recombination)");
+    ARGCHK(c->initialised, "chains not initialised");
+    ARGCHK(first_event >= 0 && n_events >= 0 && first_event + n_events <= c->recomb.events_done(c->steps_done),
+           "ppde_chains_recombination_read: events beyond those that have happened (ppde_chains_recombination_shape)");
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    const Recombination& r = c->recomb;
+    const size_t o = (size_t)first_event * c->n, k = (size_t)n_events * c->n;
+    if (!k) return PPDE_OK;
+    if (partner) HIPCHK(hipMemcpy(partner, r.partner + o, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (lo) HIPCHK(hipMemcpy(lo, r.lo + o, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (hi) HIPCHK(hipMemcpy(hi, r.hi + o, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (differ) HIPCHK(hipMemcpy(differ, r.differ + o, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (child_dist) HIPCHK(hipMemcpy(child_dist, r.child_dist + o, k * sizeof(int), hipMemcpyDeviceToHost));
+    if (outcome) HIPCHK(hipMemcpy(outcome, r.outcome + o, k, hipMemcpyDeviceToHost));
+    if (log_ratio) HIPCHK(hipMemcpy(log_ratio, r.log_ratio + o, k * sizeof(float), hipMemcpyDeviceToHost));
+    if (pre_energy) HIPCHK(hipMemcpy(pre_energy, r.pre + o, k * sizeof(float), hipMemcpyDeviceToHost));
+    if (child_energy) HIPCHK(hipMemcpy(child_energy, r.child + o, k * sizeof(float), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 
@@ -1960,6 +2115,35 @@ int ppde_chains_run(ppde_chains* c, int steps, const int32_t* U_dev, const float
         return PPDE_OK;
     }
     int done = 0;
+    if (c->recomb.on() && !c->graphs.empty()) {
+        // segments start at multiples of `every` only: eager iterations up to the next such position, then the longest segment that
+        // fits, and the rest eagerly
+        const int every = c->recomb.every;
+        while (done < steps) {
+            const int pos = c->steps_done + done, left = steps - done;
+            const ppde_chains::GraphSeg* seg = nullptr;
+            if (pos % every == 0)
+                for (const auto& gs : c->graphs) if (gs.len <= left) { seg = &gs; break; }       // longest first
+            if (seg) {
+                if (c->d_it_val != (long long)pos) {
+                    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->d_it, pos, 1, c->stream));
+                    c->d_it_val = (long long)pos;
+                }
+                HIPCHK(hipGraphLaunch(seg->exec, c->stream));
+                done += seg->len;
+                c->d_it_val += seg->len;
+                c->n_replayed_steps += seg->len;
+                continue;
+            }
+            const int k = pos % every == 0 ? left : std::min(left, every - pos % every);
+            int rc = enqueue_block(c, nullptr, pos, k);
+            if (rc) return rc;
+            c->n_eager_steps += k;
+            done += k;
+        }
+        c->steps_done += steps;
+        return PPDE_OK;
+    }
     if (!c->graphs.empty()) {
         for (const auto& gs : c->graphs) {          // longest segment first
             while (steps - done >= gs.len) {

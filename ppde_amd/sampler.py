@@ -46,6 +46,14 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         untempered energy. After run(), `sampler.annealing` holds betas, deme, every, parent [events, n] (GLOBAL
                         chain index of the ancestor), pre_energy [events, n], log_mean_w and ess [events, n / deme], beta_now [n]
                         and `summary` (ppde_amd/anneal.py: summarise).
+    ppde_recombine_every 0 (default): off. k > 0: behind every k-th iteration the chains of each deme of ppde_recombine_deme
+                        consecutive chains (default 0: all chains of the run; even) are paired and every pair proposes to exchange
+                        a segment of open residues, accepted by Metropolis on the pair (include/ppde_hip.h,
+                        ppde_chains_set_recombination). Needs ppde_reversible; not with ppde_betas, ppde_anneal_betas,
+                        paper_results or ppde_streams > 1; the population (and every shard boundary) must be a multiple of the
+                        deme. After run(), `sampler.recombination` holds deme, every, open_sites, events, partner (GLOBAL chain
+                        index), lo, hi, cut [events, n, 2], differ, child_dist, outcome, log_ratio, pre_energy, child_energy
+                        [events, n] and `summary` (ppde_amd/recombine.py: summarise; lineage gives the mosaic of founders).
     ppde_sample_every   0 (default): off. k > 0: the population after every k-th iteration (counted from ppde_sample_burn_in,
                         default 0) is recorded on the device (include/ppde_hip.h, ppde_chains_set_recorder): no host round trip,
                         nothing else of the run changes. With a ladder the recorder follows rung ppde_sample_rung (default 0, the
@@ -86,7 +94,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import _hip, anneal as chain_anneal, archive as chain_archive, library as design_library, stats as chain_stats
+from . import _hip, anneal as chain_anneal, recombine as chain_recombine, archive as chain_archive, library as design_library, stats as chain_stats
 from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
@@ -260,6 +268,49 @@ def check_demes(n_global, deme, num_steps, every, n_stages, shard_starts=(0,)):
     return D
 
 
+def check_recombination(every, deme, reversible, ladder, schedule, paper_results, n_streams):
+    """(every, deme) of the ppde_recombine_* arguments (every 0: off; deme 0 = all chains of the run, resolved with the
+    population); ValueError for what the ABI would refuse and can be seen without the population."""
+    every, deme = int(every or 0), int(deme or 0)
+    if every < 0:
+        raise ValueError("ppde_recombine_every must be >= 0 (0: no recombination)")
+    if every == 0:
+        if deme:
+            raise ValueError("ppde_recombine_deme needs ppde_recombine_every > 0")
+        return 0, 0
+    if not reversible:
+        raise ValueError("ppde_recombine_every: recombination needs ppde_reversible (only there do the chains have the law whose "
+                         "product the exchange keeps)")
+    if ladder is not None or schedule is not None:
+        raise ValueError("ppde_recombine_every: recombination cannot be combined with a ladder (ppde_betas) or a schedule "
+                         "(ppde_anneal_betas): its decision takes no beta per chain")
+    if paper_results:
+        raise ValueError("ppde_recombine_every: paper_results is not supported")
+    if deme < 0 or deme % 2:
+        raise ValueError("ppde_recombine_deme must be even and >= 2 (0: all chains of the run)")
+    if int(n_streams) > 1:
+        raise ValueError("ppde_recombine_every: ppde_streams > 1 is not supported (the exchange couples the chains of a deme)")
+    return every, deme
+
+
+def check_recombination_demes(n_global, deme, num_steps, every, shard_starts=(0,)):
+    """The deme size of a recombination run of n_global chains (deme 0: all of them), or ValueError: an odd size, a population or
+    a shard boundary that cuts a deme, a run too short for one event."""
+    D = int(n_global) if int(deme) == 0 else int(deme)
+    if D < 2 or D % 2:
+        raise ValueError(f"ppde_recombine_deme: a deme has an even number of chains, at least 2, got {D}" +
+                         (" (ppde_recombine_deme 0 = all chains of the run)" if int(deme) == 0 else ""))
+    if n_global % D:
+        raise ValueError(f"ppde_recombine_deme: the population of {n_global} chains is no multiple of the deme of {D}")
+    cut = boundary_cut(shard_starts, D)
+    if cut:
+        raise ValueError(f"ppde_recombine_deme: the shard boundary at chain {cut[1]} (rank {cut[0]} of {len(shard_starts)}) cuts a "
+                         f"deme of {D} chains")
+    if int(num_steps) // int(every) == 0:
+        raise ValueError(f"ppde_recombine_every: no event fits into {int(num_steps)} iterations (every {int(every)})")
+    return D
+
+
 def check_recorder(every, burn_in, rung, counts_only, pairs, ladder, n_streams):
     """(every, burn_in, rung, counts_only, pairs) of the ppde_sample_* arguments (every 0: no recorder; rung None without a ladder,
     default 0 with one; pairs as check_pair_spec); ValueError for what the ABI would refuse and can be seen without the run length."""
@@ -389,6 +440,42 @@ class Chains:
                    beta=np.empty(self.n, np.float32))
         self._call("annealing_read", first, count, *[_hip.ptr(out[k_]) for k_ in ("parent", "pre_energy", "log_mean_w", "ess", "beta")])
         out["events"] = done
+        return out
+
+    RECOMBINATION_FIELDS = (("partner", np.int32), ("lo", np.int32), ("hi", np.int32), ("differ", np.int32), ("child_dist", np.int32),
+                            ("outcome", np.uint8), ("log_ratio", np.float32), ("pre_energy", np.float32), ("child_energy", np.float32))
+
+    def set_recombination(self, every, deme=0):
+        """Recombination (include/ppde_hip.h, ppde_chains_set_recombination): behind every `every`-th iteration the chains of each
+        deme of `deme` consecutive chains (0 or None: all chains of the object) are paired and every pair proposes to exchange a
+        segment of open residues. every None or 0 clears it. Needs reversible mode; only before init() and after set_library()."""
+        if not every:
+            self._call("set_recombination", None)
+            self.recombination = None
+            return
+        D = self.n if not deme else int(deme)
+        cfg = _hip.RecombineConfig(deme=D, every=int(every))
+        self._call("set_recombination", C.byref(cfg))
+        self.recombination = dict(every=int(every), deme=D)
+
+    def recombination_shape(self):
+        """(deme size, open residues int32 [S_o], event capacity, events that have happened)."""
+        d, n_open, cap, done = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._call("recombination_shape", C.byref(d), C.byref(n_open), None, C.byref(cap), C.byref(done))
+        sites = np.empty(n_open.value, np.int32)
+        self._call("recombination_shape", None, None, _hip.ptr(sites), None, None)
+        return d.value, sites, cap.value, done.value
+
+    def recombination_state(self, first=0, count=None):
+        """Events [first, first + count) (default: all so far), [count, n] each: partner (LOCAL index), lo, hi (indices into
+        open_sites), differ, child_dist int32, outcome uint8 (0 rejected by u, 1 accepted, 2 a child at the mutation cap, 3 a
+        non-finite child energy), log_ratio, pre_energy, child_energy fp32; deme, every, open_sites, events."""
+        D, sites, _, done = self.recombination_shape()
+        first = int(first)
+        count = done - first if count is None else int(count)
+        out = {k_: np.empty((max(count, 0), self.n), t) for k_, t in self.RECOMBINATION_FIELDS}
+        self._call("recombination_read", first, count, *[_hip.ptr(out[k_]) for k_, _ in self.RECOMBINATION_FIELDS])
+        out.update(deme=D, every=self.recombination["every"], open_sites=sites, events=done)
         return out
 
     def set_recorder(self, every, burn_in=0, rung=None, keep_samples=True):
@@ -616,6 +703,12 @@ class PPDE_PAS(BaseSampler):
         self.anneal_betas, self.anneal_every, self.deme = check_annealing(
             getattr(args, "ppde_anneal_betas", None), getattr(args, "ppde_anneal_every", 1) or 1, getattr(args, "ppde_deme", 0) or 0,
             self.reversible, self.betas, self.n_streams)
+        self.recombine_every, self.recombine_deme = check_recombination(
+            getattr(args, "ppde_recombine_every", 0), getattr(args, "ppde_recombine_deme", 0), self.reversible, self.betas,
+            self.anneal_betas, self.paper_results, self.n_streams)
+        self.recombination = None
+        self._recomb_logged = 0     # recombination events the periodic log has reported
+        self._recomb_pairs = np.zeros(3, np.int64)   # so far: pairs with differ > 0, accepted ones of them, identical pairs
         self.sample_every, self.sample_burn_in, self.sample_rung, self.sample_counts_only, self.sample_pairs = check_recorder(
             getattr(args, "ppde_sample_every", 0), getattr(args, "ppde_sample_burn_in", 0), getattr(args, "ppde_sample_rung", None),
             getattr(args, "ppde_sample_counts_only", False), getattr(args, "ppde_sample_pairs", None), self.betas, self.n_streams)
@@ -665,7 +758,10 @@ class PPDE_PAS(BaseSampler):
         D = 0
         if self.anneal_betas is not None:
             D = check_demes(n_global, self.deme, num_steps, self.anneal_every, self.anneal_betas.size - 1, shard.starts)
-        return SimpleNamespace(L=L, lib_words=lib_words, R=R, D=D, pair_sites=pair_sites, random_idx=random_idx, shard=shard)
+        X = 0
+        if self.recombine_every:
+            X = check_recombination_demes(n_global, self.recombine_deme, num_steps, self.recombine_every, shard.starts)
+        return SimpleNamespace(L=L, lib_words=lib_words, R=R, D=D, X=X, pair_sites=pair_sites, random_idx=random_idx, shard=shard)
 
     def _configured_chains(self, model, which, plan, num_steps, min_pos, max_pos, random_idx, seed):
         """This rank's Chains with every mode of the run set, before init()."""
@@ -688,6 +784,8 @@ class PPDE_PAS(BaseSampler):
             chains.set_tempering(self.betas, self.swap_every)
         if plan.D:
             chains.set_annealing(self.anneal_betas, self.anneal_every, plan.D)
+        if plan.X:
+            chains.set_recombination(self.recombine_every, plan.X)
         if self.sample_every:
             chains.set_recorder(self.sample_every, self.sample_burn_in, self.sample_rung, not self.sample_counts_only)
         if self.sample_pairs is not None:
@@ -738,6 +836,8 @@ class PPDE_PAS(BaseSampler):
             print(f'   # swaps accepted = {int(ts["swap_accepts"].sum())} / {int(ts["swap_attempts"].sum())}')
         if D:
             self._log_annealing(chains, shard, D)
+        if plan.X:
+            self._log_recombination(chains, shard)
         if self.stats_spec is not None:
             print(chain_stats.log_line(gather_stats(shard, chains.stats())))
 
@@ -752,6 +852,33 @@ class PPDE_PAS(BaseSampler):
             print(f'   # annealing: stage {ev} of {self.anneal_betas.size - 1}, beta = {float(self.anneal_betas[ev]):.6g}, '
                   f'min ESS = {float(ess.min()):.2f} of {D}, slots replaced = {replaced}')
             self._anneal_logged = ev
+
+    def _log_recombination(self, chains, shard):
+        """One line when events happened since the last log: acceptance so far over the pairs with differ > 0, and the share of
+        identical pairs."""
+        ev = chains.recombination_shape()[3]
+        if ev > self._recomb_logged:
+            st = chains.recombination_state(self._recomb_logged, ev - self._recomb_logged)
+            first = np.arange(shard.n)[None] < st["partner"]
+            real = first & (st["differ"] > 0)
+            new = np.array([real.sum(), (real & (st["outcome"] == 1)).sum(), (first & (st["differ"] == 0)).sum()], np.int64)
+            self._recomb_pairs = self._recomb_pairs + shard.sum(new)
+            real_n, acc_n, same_n = (int(v) for v in self._recomb_pairs)
+            print(f'   # recombination: event {ev}, accepted {acc_n} / {real_n} of the pairs that differ'
+                  f'{f" ({acc_n / real_n:.3f})" if real_n else ""}, identical pairs {same_n / max(real_n + same_n, 1):.3f}')
+            self._recomb_logged = ev
+
+    def _collect_recombination(self, chains, shard, X):
+        """Per-chain rows [events, n_global] in global chain order, partners as GLOBAL indices; cut [events, n, 2]; the summary."""
+        if not X:
+            return None
+        st = chains.recombination_state()
+        st["partner"] = shard.to_global(st["partner"])
+        rc = {k: shard.gather(st[k], dim=1) for k, _ in Chains.RECOMBINATION_FIELDS}
+        rc.update(deme=X, every=self.recombine_every, open_sites=st["open_sites"], events=st["events"],
+                  cut=np.stack([rc["lo"], rc["hi"]], -1))
+        rc["summary"] = chain_recombine.summarise(rc)
+        return rc
 
     @staticmethod
     def _swap_counts(chains, shard, R):
@@ -836,7 +963,8 @@ class PPDE_PAS(BaseSampler):
         t_log = 0.0
         chains = self._configured_chains(model, energy_function.which, plan, num_steps, min_pos, max_pos, random_idx, seed)
         chains.init(idx0[shard.lo:shard.hi])
-        self._anneal_logged = 0
+        self._anneal_logged = self._recomb_logged = 0
+        self._recomb_pairs = np.zeros(3, np.int64)
         chains.sync()
         t_setup = time.perf_counter() - t_begin
         # ---- iterations, with the log
@@ -870,6 +998,7 @@ class PPDE_PAS(BaseSampler):
         best_e, best_f = shard.gather(res["best_energy"]), shard.gather(res["best_fitness"])
         self.tempering = self._collect_tempering(chains, shard, R)
         self.annealing = self._collect_annealing(chains, shard, D)
+        self.recombination = self._collect_recombination(chains, shard, plan.X)
         self.samples = self._collect_samples(chains, shard, R)
         self.archive = self._collect_archive(chains, shard)
         self.stats = self._collect_stats(chains, shard)

@@ -20,6 +20,11 @@ CHILD = r"""
 import sys, time, json
 sys.path.insert(0, sys.argv[1])
 import numpy as np, torch
+import ctypes
+from ppde_amd import _hip
+_old = ctypes.CDLL(_hip.LIB_PATH)                  # an older build lacks the entry points added since; nothing here calls them
+for _name in [k for k in _hip.SIGNATURES if not hasattr(_old, k)]:
+    _hip.SIGNATURES.pop(_name)
 from bench import build_model
 from ppde_amd.sampler import Chains
 m, wt, J, h, i0, Lp, cnn = build_model("potts", "cuda:0", "PABP")

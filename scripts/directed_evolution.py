@@ -141,6 +141,10 @@ def main(args):
         if annealing is not None:
             for name in ("parent", "pre_energy", "log_mean_w", "ess", "betas"):
                 np.save(results_path / f"anneal_{name}.npy", annealing[name])
+        recombination = getattr(sampler, "recombination", None)
+        if recombination is not None:
+            for name in ("partner", "cut", "differ", "outcome", "log_ratio", "pre_energy", "child_energy", "open_sites"):
+                np.save(results_path / f"recomb_{name}.npy", recombination[name])
         samples = getattr(sampler, "samples", None)
         if samples is not None:
             np.save(results_path / "site_counts.npy", samples["site_counts"])
@@ -255,6 +259,15 @@ def build_parser():
     pp.add_argument("--ppde_anneal_every", type=int, default=1, help="with --ppde_anneal_betas: iterations per stage of the schedule")
     pp.add_argument("--ppde_deme", type=int, default=0,
                     help="with --ppde_anneal_betas: chains per deme, 2..1024 (0: all chains of the run); consecutive chains form a "
+                         "deme, --n_chains must be a multiple of it")
+    pp.add_argument("--ppde_recombine_every", type=int, default=0,
+                    help="recombination (needs --ppde_reversible; not with --ppde_betas or --ppde_anneal_betas): behind every this "
+                         "many iterations the chains of a deme are paired and each pair proposes to exchange a segment of open "
+                         "residues (0: off). Writes recomb_partner.npy, recomb_differ.npy, recomb_outcome.npy, recomb_log_ratio.npy, "
+                         "recomb_pre_energy.npy, recomb_child_energy.npy [events, n], recomb_cut.npy [events, n, 2] and "
+                         "recomb_open_sites.npy; the periodic log gains a line when events happened")
+    pp.add_argument("--ppde_recombine_deme", type=int, default=0,
+                    help="with --ppde_recombine_every: chains per deme, even (0: all chains of the run); consecutive chains form a "
                          "deme, --n_chains must be a multiple of it")
     pp.add_argument("--ppde_sample_every", type=int, default=0,
                     help="record the population on the device after every this many iterations (0: off): samples.npy, "
