@@ -339,6 +339,54 @@ int ppde_chains_annealing_read(ppde_chains* c, int first_event, int n_events,
                                double* log_mean_w /* [n_events][n / D] */, double* ess /* [n_events][n / D] */,
                                float* beta_now /* [n] */);
 
+/* Adaptive population annealing: the same mode (the same demes, events, plan, slot rule, copies, records and observers as above),
+ * except that no schedule is given: at every event each deme chooses its own next beta, the largest step whose incremental weights
+ * still leave an effective sample size of ess_target times the deme (Jasra et al. 2011; Zhou, Johansen & Aston 2016). All
+ * arithmetic is fp64 on the fp32 inputs, on the device, inside the captured iteration graph:
+ *   run: every chain starts at beta_start; iteration `it` is event s = (it + 1) / every - 1 when (it + 1) % every == 0 and
+ *     s < events_cap = min(max_stages, max_steps / every). Past events_cap nothing happens and each deme keeps the beta it has;
+ *   step of one deme at an event: beta_cur = beta[first chain of the deme], b0 = (double)beta_cur; e_i the post-accept energies
+ *     (history row it + 1), F the number of finite ones, E_max the largest finite one, x_i = (double)e_i - E_max.
+ *     F == 0: beta stays (and the plan's no-finite-energy rule applies: identity, log_mean_w = -inf, ess = 0).
+ *     dmax = (double)beta_end - b0 <= 0: the deme has arrived, beta_next = beta_cur, and the event runs the plan with dbeta = 0, as
+ *     equal neighbours of a fixed schedule do. Otherwise, with ESS(d) = (sum w_i)^2 / sum w_i^2, w_i = exp(d x_i) over the finite
+ *     e_i (ESS(0) = F, non-increasing in d >= 0) and target = (double)ess_target F:
+ *       if ESS(dmax) >= target: d = dmax; otherwise lo = 0, hi = dmax and 48 times mid = 0.5 (lo + hi), ESS(mid) >= target ?
+ *       lo = mid : hi = mid; then d = max(lo, (double)min_step);
+ *     beta_next = beta_end if d >= dmax or (float)(b0 + d) >= beta_end, otherwise (float)(b0 + d), rounded to nearest;
+ *   the event then runs the plan above unchanged with dbeta = (double)beta_next - b0 -- weights, systematic resampling on the
+ *     same Philox stream, slot rule, parent, pre_energy, log_mean_w, ess -- and sets beta = beta_next for the deme's chains;
+ *   recorded in addition, per event and deme: beta_before = beta_cur and beta_after = beta_next.
+ * What follows: deme by deme the adaptive run IS the fixed-schedule run on that deme's recorded beta path (beta_start,
+ * beta_after[0], beta_after[1], ...), bit for bit; its estimate of log(Z_end / Z_start) is the sum of the same log_mean_w, but
+ * with steps that depend on the states that estimate is consistent in D and no longer unbiased, and only demes that have arrived
+ * at beta_end estimate the same ratio. ESS >= 1 always, so with ess_target <= 1 / D the first event jumps to beta_end (D = 2 with
+ * ess_target = 0.5 always jumps). min_step bounds the number of stages by (beta_end - beta_start) / min_step and is what moves a
+ * deme whose ESS falls below the target at any d > 0.
+ * The adaptive form and ppde_chains_set_annealing are one mode: a successful call of either replaces what either set, NULL to
+ * either clears it, ppde_chains_annealing_shape and ppde_chains_annealing_read serve both, and while either is set the other
+ * setters refuse as described above. PPDE_ERR_INVALID with a message, the object unchanged: every refusal of
+ * ppde_chains_set_annealing that concerns the object, deme and every (after init; reversible mode not on; tempering or
+ * recombination set; deme outside 2..1024; n_chains or chain_offset no multiple of deme; every < 1; events_cap == 0;
+ * n_streams > 1); max_stages outside 1..4096; beta_start or beta_end not finite and positive; beta_start >= beta_end; ess_target
+ * not finite or outside (0, 1); min_step not finite or < beta_end * 2^-20 (so that every step changes beta in fp32). A failed
+ * allocation is PPDE_ERR_HIP and leaves nothing half-set. */
+typedef struct {
+    int32_t deme;        /* D, 2..1024 */
+    int32_t every;       /* >= 1 */
+    int32_t max_stages;  /* 1..4096 */
+    float beta_start;    /* finite, > 0, < beta_end */
+    float beta_end;
+    float ess_target;    /* rho, inside (0, 1) */
+    float min_step;      /* >= beta_end * 2^-20 */
+} ppde_anneal_adaptive_config;
+int ppde_chains_set_annealing_adaptive(ppde_chains* c, const ppde_anneal_adaptive_config* cfg /* NULL clears */);
+/* The inverse temperature every deme held before and after events [first_event, first_event + n_events). Under a fixed schedule
+ * these are beta[s] and beta[s + 1] for every deme. Synchronises; either pointer may be NULL. PPDE_ERR_INVALID without annealing,
+ * before init, or for events beyond events_done. */
+int ppde_chains_annealing_read_betas(ppde_chains* c, int first_event, int n_events,
+                                     float* beta_before /* [n_events][n / D] */, float* beta_after /* [n_events][n / D] */);
+
 /* Recombination (off by default; needs reversible mode): every `every`-th iteration the chains of a deme are paired and each
  * pair proposes to exchange a segment of open residues -- a Metropolis move on the pair with a symmetric proposal, which keeps
  * the product law prod_i exp(E(x_i)) / Z of the reversible chains invariant (the crossover of evolutionary Monte Carlo, Liang &

@@ -49,6 +49,12 @@ class AnnealConfig(C.Structure):
     _fields_ = [("deme", C.c_int32), ("every", C.c_int32), ("n_stages", C.c_int32), ("beta", C.POINTER(C.c_float))]
 
 
+class AnnealAdaptiveConfig(C.Structure):
+    """ppde_anneal_adaptive_config (include/ppde_hip.h)."""
+    _fields_ = [("deme", C.c_int32), ("every", C.c_int32), ("max_stages", C.c_int32), ("beta_start", C.c_float),
+                ("beta_end", C.c_float), ("ess_target", C.c_float), ("min_step", C.c_float)]
+
+
 class RecombineConfig(C.Structure):
     """ppde_recombine_config (include/ppde_hip.h)."""
     _fields_ = [("deme", C.c_int32), ("every", C.c_int32)]
@@ -94,6 +100,8 @@ SIGNATURES = {
     "ppde_chains_set_annealing": (_i, [_p, C.POINTER(AnnealConfig)]),
     "ppde_chains_annealing_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ppde_chains_annealing_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),
+    "ppde_chains_set_annealing_adaptive": (_i, [_p, C.POINTER(AnnealAdaptiveConfig)]),
+    "ppde_chains_annealing_read_betas": (_i, [_p, _i, _i, _p, _p]),
     "ppde_chains_set_recombination": (_i, [_p, C.POINTER(RecombineConfig)]),
     "ppde_chains_recombination_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ppde_chains_recombination_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -15,6 +15,15 @@
 //   integer prefix sums; the k-th dead slot takes the k-th entry of the surplus list, everyone else is its own parent.
 //   Writes row s of parent / pre_energy / log_mean_w / ess, and beta[b] = schedule[s + 1] for its chains (nobody reads beta in
 //   this launch).
+// k_select_plan_adaptive (ppde_chains_set_annealing_adaptive; both plan kernels are the text of anneal_plan.h, included twice
+//   below): the same plan behind a step the deme chooses itself. With
+//   b0 = beta[first chain of the deme], x_i = e_i - E_max, F finite energies and ESS(d) = (sum w)^2 / sum w^2, w_i = exp(d x_i), it
+//   takes the largest d in (0, beta_end - b0] with ESS(d) >= rho F: the whole remainder if that passes, otherwise 48 bisection steps,
+//   and at least min_step. Every ESS is one workgroup reduction: per-wave DPP sums, the waves' partials through LDS (two buffers
+//   in turns: one barrier per evaluation), read and added by EVERY thread in the same order, so all threads hold the same bits
+//   and the loop branches uniformly. beta_next = (float)(b0 + d), or beta_end once that is reached; the plan then runs on
+//   db = (double)beta_next - b0, exactly as k_select_plan runs on the schedule's difference, and records (beta, beta_next) of the
+//   event. Static LDS: k_select_plan 16 480 bytes, the adaptive form 16 624 (+ 2 x 8 doubles, + 4 ints).
 // k_select_copy: one workgroup per chain, returns unless parent[b] != b. A replaced slot takes from its parent everything the
 //   next iteration and the observers read for a chain: the state row and its T4 bytes, ChainRec::cur_e / cur_f / dist_cur, the
 //   grad_cur row under gradient reuse, row it + 1 of both histories (and of rtraj for the recorded chain), and moves its running
@@ -55,6 +64,13 @@ struct AnnealArgs {
     double* ess;
 };
 
+// what k_select_plan_adaptive takes besides (a.sched is not read there)
+struct AnnealStepArgs {
+    float beta_end, rho, min_step;
+    int cap;                    // events_cap
+    float* beta_pair;           // [2][events_cap][n / D]: beta before / after every event
+};
+
 // stage of the event behind iteration `it`, or -1
 __device__ __forceinline__ int anneal_stage(const AnnealArgs& a, int& it) {
     typedef const __attribute__((address_space(4))) int* cptr;
@@ -92,123 +108,35 @@ __device__ __forceinline__ int anneal_scan_excl_i(int v, int* xw, int& total) {
     return off + incl - v;
 }
 
-__global__ __launch_bounds__(ANNEAL_BLOCK) void k_select_plan(AnnealArgs a) {
-    int it;
-    const int s = anneal_stage(a, it);
-    if (s < 0) return;
-    __shared__ double C[ANNEAL_DMAX];                // inclusive prefix sums of the weights
-    __shared__ int cnt[ANNEAL_DMAX];                 // offspring counts
-    __shared__ int lst[ANNEAL_DMAX];                 // the surplus list
-    __shared__ double xd[2 * ANNEAL_NW];
-    __shared__ float xf[ANNEAL_NW];
-    __shared__ int xi[ANNEAL_NW];
-    const int D = a.D, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int first = blockIdx.x * D;                // local index of the deme's first chain
-    const int i0 = tid * ANNEAL_CPT;
-    const float* erow = a.e_hist + (size_t)(it + 1) * a.n + first;
-    const double db = (double)a.sched[s + 1] - (double)a.sched[s];
-
-    float e[ANNEAL_CPT];
-    bool fin[ANNEAL_CPT];
-    float mx = -INFINITY;
+// ESS numerator and denominator of the adaptive step at increment d: tot = sum w, sq = sum w^2 over the deme, the same bits in
+// every thread (all threads add the waves' partials in the order of the waves). xa: 2 x 2 ANNEAL_NW doubles, used in turns -- a
+// thread may write the next evaluation's buffer while others still read this one's, and the barrier in between orders the rest.
+__device__ __forceinline__ void anneal_ess_sums(double d, const double (&x)[ANNEAL_CPT], const bool (&fin)[ANNEAL_CPT], double* xa,
+                                                int& turn, double& tot, double& sq) {
+    double t = 0.0, q = 0.0;
 #pragma unroll
     for (int r = 0; r < ANNEAL_CPT; ++r) {
-        const int i = i0 + r;
-        e[r] = i < D ? erow[i] : -INFINITY;
-        fin[r] = i < D && fabsf(e[r]) < INFINITY;    // (false for NaN and both infinities)
-        if (fin[r]) mx = fmaxf(mx, e[r]);
-        cnt[i] = 0;
+        const double w = fin[r] ? exp(d * x[r]) : 0.0;
+        t += w;
+        q += w * w;
     }
-    mx = wave_max(mx);
-    if (lane == 0) xf[wave] = mx;
+    t = wave_sum_d(t);
+    q = wave_sum_d(q);
+    double* buf = xa + 2 * ANNEAL_NW * (turn & 1);
+    if ((threadIdx.x & 63) == 0) { buf[threadIdx.x >> 6] = t; buf[ANNEAL_NW + (threadIdx.x >> 6)] = q; }
     __syncthreads();
-    float emax_f = xf[0];
+    ++turn;
+    tot = 0.0; sq = 0.0;
 #pragma unroll
-    for (int w = 1; w < ANNEAL_NW; ++w) emax_f = fmaxf(emax_f, xf[w]);
-    const bool any = emax_f > -INFINITY;             // a finite energy in the deme
-    const double emax = (double)emax_f;
-
-    double w[ANNEAL_CPT], tot = 0.0, sq = 0.0;
-    int last = -1;
-#pragma unroll
-    for (int r = 0; r < ANNEAL_CPT; ++r) {
-        w[r] = fin[r] ? exp(db * ((double)e[r] - emax)) : 0.0;
-        tot += w[r];
-        sq += w[r] * w[r];
-        if (w[r] > 0.0) last = i0 + r;
-    }
-    const double incl = wave_scan_incl_d(tot);
-    const double sq_w = wave_sum_d(sq);
-    last = (int)wave_max((float)last);               // (indices below 2^24: exact in fp32)
-    if (lane == 63) xd[wave] = incl;
-    if (lane == 0) { xd[ANNEAL_NW + wave] = sq_w; xi[wave] = last; }
-    __syncthreads();
-    double off = 0.0, sumsq = 0.0;
-    int last_pos = -1;
-#pragma unroll
-    for (int k = 0; k < ANNEAL_NW; ++k) {
-        off += k < wave ? xd[k] : 0.0;
-        sumsq += xd[ANNEAL_NW + k];
-        last_pos = max(last_pos, xi[k]);
-    }
-    {
-        double c = off + incl - tot;                 // exclusive prefix of this thread
-#pragma unroll
-        for (int r = 0; r < ANNEAL_CPT; ++r) { c += w[r]; C[i0 + r] = c; }
-    }
-    __syncthreads();
-    const double W = C[D - 1];
-    const bool select = any && W > 0.0;
-
-    if (select) {
-        const U4 rnd = philox4x32_10(U4{a.key.chain_lo + (uint32_t)first, (uint32_t)it, ANNEAL_STREAM, 0u}, a.key.k0, a.key.k1);
-        const double u = (double)unif_from_bits(rnd.x), step = W / (double)D;
-#pragma unroll
-        for (int r = 0; r < ANNEAL_CPT; ++r) {
-            const int j = i0 + r;
-            if (j >= D) continue;
-            const double tau = ((double)j + u) * step;
-            int lo = 0, hi = D;                      // first i with C_i > tau = #{i : C_i <= tau}
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (C[mid] <= tau) lo = mid + 1; else hi = mid;
-            }
-            atomicAdd(&cnt[min(lo, last_pos)], 1);
-        }
-    }
-    __syncthreads();
-    int nd = 0, ns = 0, c_i[ANNEAL_CPT];
-#pragma unroll
-    for (int r = 0; r < ANNEAL_CPT; ++r) {
-        c_i[r] = (select && i0 + r < D) ? cnt[i0 + r] : 1;
-        nd += c_i[r] == 0 ? 1 : 0;
-        ns += c_i[r] > 1 ? c_i[r] - 1 : 0;
-    }
-    int total_dead, total_surplus;
-    int dx = anneal_scan_excl_i(nd, xi, total_dead);
-    int sx = anneal_scan_excl_i(ns, xi, total_surplus);
-#pragma unroll
-    for (int r = 0; r < ANNEAL_CPT; ++r)
-        for (int k = 1; k < c_i[r]; ++k) lst[min(sx++, ANNEAL_DMAX - 1)] = i0 + r;     // (sum (n_i - 1)+ = dead slots <= D - 1)
-    __syncthreads();
-    const size_t row = (size_t)s * a.n + first;
-    const float b_next = a.sched[s + 1];
-#pragma unroll
-    for (int r = 0; r < ANNEAL_CPT; ++r) {
-        const int i = i0 + r;
-        if (i >= D) continue;
-        int p = i;
-        if (c_i[r] == 0) { p = lst[min(dx, ANNEAL_DMAX - 1)]; ++dx; }
-        a.parent[row + i] = first + p;
-        a.pre_energy[row + i] = e[r];
-        a.beta[first + i] = b_next;
-    }
-    if (tid == 0) {
-        const size_t cell = (size_t)s * (a.n / D) + blockIdx.x;
-        a.log_mean_w[cell] = select ? log(W / (double)D) + db * emax : -INFINITY;
-        a.ess[cell] = select ? W * W / sumsq : 0.0;
-    }
+    for (int k = 0; k < ANNEAL_NW; ++k) { tot += buf[k]; sq += buf[ANNEAL_NW + k]; }
 }
+
+#define ANNEAL_PLAN_ADAPTIVE 0
+#include "anneal_plan.h"
+#undef ANNEAL_PLAN_ADAPTIVE
+#define ANNEAL_PLAN_ADAPTIVE 1
+#include "anneal_plan.h"
+#undef ANNEAL_PLAN_ADAPTIVE
 
 __global__ __launch_bounds__(ANNEAL_BLOCK) void k_select_copy(AnnealArgs a) {
     int it;

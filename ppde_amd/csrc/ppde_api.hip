@@ -1149,11 +1149,14 @@ struct Tempering {
     bool on() const { return beta.p != nullptr; }
 };
 
-// population annealing (ppde_chains_set_annealing)
+// population annealing (ppde_chains_set_annealing, ppde_chains_set_annealing_adaptive)
 struct Annealing {
-    int D = 0, every = 0, S = 0, cap = 0;        // deme size, iterations per stage, stages, events_cap
-    std::vector<float> sched;                    // beta[0] <= ... <= beta[S]
-    DevBuf<float> sched_dev, beta, pre;          // [S+1], [n], [events_cap][n]
+    int D = 0, every = 0, S = 0, cap = 0;        // deme size, iterations per stage, stages (adaptive: max_stages), events_cap
+    std::vector<float> sched;                    // beta[0] <= ... <= beta[S] (adaptive: beta_start, beta_end)
+    DevBuf<float> sched_dev, beta, pre;          // [S+1] (adaptive: [2]), [n], [events_cap][n]
+    bool adaptive = false;                       // the deme chooses each step (k_select_plan_adaptive)
+    float rho = 0.f, min_step = 0.f;             // its ESS target and its smallest step
+    DevBuf<float> beta_pair;                     // [2][events_cap][n/D] beta before / after every event (adaptive only)
     DevBuf<int> parent;                          // [events_cap][n]
     DevBuf<double> lmw, ess;                     // [events_cap][n/D]
     bool on() const { return sched_dev.p != nullptr; }
@@ -1395,7 +1398,12 @@ static int launch_select(ppde_chains* c, const int* it_base, int it_local, hipSt
     r.sched = c->anneal.sched_dev; r.beta = c->anneal.beta; r.rec = c->rec; r.cur = c->cur; r.curT = (uint8_t*)c->curT;
     r.grad_cur = c->grad_cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist; r.best_state = c->best_state; r.rtraj = c->rtraj;
     r.parent = c->anneal.parent; r.pre_energy = c->anneal.pre; r.log_mean_w = c->anneal.lmw; r.ess = c->anneal.ess;
-    hipLaunchKernelGGL(k_select_plan, dim3(c->n / c->anneal.D), dim3(ANNEAL_BLOCK), 0, s, r);
+    if (c->anneal.adaptive) {
+        const AnnealStepArgs x{c->anneal.sched[1], c->anneal.rho, c->anneal.min_step, c->anneal.cap, c->anneal.beta_pair};
+        hipLaunchKernelGGL(k_select_plan_adaptive, dim3(c->n / c->anneal.D), dim3(ANNEAL_BLOCK), 0, s, r, x);
+    } else {
+        hipLaunchKernelGGL(k_select_plan, dim3(c->n / c->anneal.D), dim3(ANNEAL_BLOCK), 0, s, r);
+    }
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_select_copy, dim3(c->n), dim3(ANNEAL_BLOCK), 0, s, r);
     HIPCHK(hipGetLastError());
@@ -1875,6 +1883,56 @@ int ppde_chains_set_annealing(ppde_chains* c, const ppde_anneal_config* cfg) {
     return PPDE_OK;
 }
 
+int ppde_chains_set_annealing_adaptive(ppde_chains* c, const ppde_anneal_adaptive_config* cfg) {
+    ARGCHK(c, "null argument");
+    ARGCHK(!c->initialised, "ppde_chains_set_annealing_adaptive: the mode must be set before ppde_chains_init (its graphs hold the kernel choice)");
+    ARGCHK(!c->recomb.on(), "ppde_chains_set_annealing_adaptive: recombination is set (its decision takes no beta per chain); clear it first "
+                            "(ppde_chains_set_recombination(c, NULL))");
+    if (!cfg) {                                     // clear
+        HIPCHK(hipSetDevice(c->device));
+        c->anneal = {};
+        return PPDE_OK;
+    }
+    ARGCHK(c->reversible, "ppde_chains_set_annealing_adaptive: annealing needs reversible mode (ppde_chains_set_reversible): only there is "
+                          "the law at beta, exp(beta E)/Z, defined");
+    ARGCHK(!c->temper.on(), "ppde_chains_set_annealing_adaptive: tempering is set (a schedule and a ladder cannot be combined); clear it "
+                            "first (ppde_chains_set_tempering(c, 0, NULL, 0))");
+    ARGCHK(cfg->deme >= 2 && cfg->deme <= ANNEAL_DMAX, "ppde_chains_set_annealing_adaptive: deme must be in 2..1024");
+    ARGCHK(c->n % cfg->deme == 0, "ppde_chains_set_annealing_adaptive: n_chains must be a multiple of deme (demes of consecutive chains)");
+    ARGCHK(c->cfg.chain_offset % (uint64_t)cfg->deme == 0, "ppde_chains_set_annealing_adaptive: chain_offset must be a multiple of deme (a "
+                                                           "deme may not straddle two shards)");
+    ARGCHK(cfg->every >= 1, "ppde_chains_set_annealing_adaptive: every must be >= 1");
+    ARGCHK(cfg->max_stages >= 1 && cfg->max_stages <= 4096, "ppde_chains_set_annealing_adaptive: max_stages must be in 1..4096");
+    const int cap = std::min(cfg->max_stages, c->T / cfg->every);
+    ARGCHK(cap >= 1, "ppde_chains_set_annealing_adaptive: no event would fit (events_cap = min(max_stages, max_steps / every) is 0)");
+    ARGCHK(cfg->beta_start > 0.f && cfg->beta_start < INFINITY, "ppde_chains_set_annealing_adaptive: beta_start must be finite and positive");
+    ARGCHK(cfg->beta_end > 0.f && cfg->beta_end < INFINITY, "ppde_chains_set_annealing_adaptive: beta_end must be finite and positive");
+    ARGCHK(cfg->beta_start < cfg->beta_end, "ppde_chains_set_annealing_adaptive: beta_start must be below beta_end");
+    ARGCHK(cfg->ess_target > 0.f && cfg->ess_target < 1.f, "ppde_chains_set_annealing_adaptive: ess_target must be inside (0, 1)");
+    ARGCHK(cfg->min_step < INFINITY && cfg->min_step >= cfg->beta_end * 0x1p-20f,
+           "ppde_chains_set_annealing_adaptive: min_step must be finite and >= beta_end * 2^-20 (a step that changes beta in fp32)");
+    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_annealing_adaptive: n_streams > 1 is not supported (the "
+                                                            "selection couples the chains of a deme)");
+    HIPCHK(hipSetDevice(c->device));
+    // allocate everything first: a failure leaves the object as it was
+    const size_t n = c->n, demes = n / cfg->deme;
+    Annealing t;
+    t.D = cfg->deme; t.every = cfg->every; t.S = cfg->max_stages; t.cap = cap;
+    t.adaptive = true; t.rho = cfg->ess_target; t.min_step = cfg->min_step;
+    t.sched = {cfg->beta_start, cfg->beta_end};
+    hipError_t e = t.sched_dev.alloc(2);
+    if (e == hipSuccess) e = hipMemcpy(t.sched_dev, t.sched.data(), 2 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = t.beta.alloc(n);
+    if (e == hipSuccess) e = t.pre.alloc((size_t)cap * n);
+    if (e == hipSuccess) e = t.parent.alloc((size_t)cap * n);
+    if (e == hipSuccess) e = t.lmw.alloc((size_t)cap * demes);
+    if (e == hipSuccess) e = t.ess.alloc((size_t)cap * demes);
+    if (e == hipSuccess) e = t.beta_pair.alloc(2 * (size_t)cap * demes);
+    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_annealing_adaptive: device allocation: ") + hipGetErrorString(e));
+    c->anneal = std::move(t);
+    return PPDE_OK;
+}
+
 int ppde_chains_annealing_shape(ppde_chains* c, int32_t* deme, int32_t* events_cap, int32_t* events_done) {
     ARGCHK(c, "null argument");
     ARGCHK(c->anneal.on(), "ppde_chains_annealing_shape: no annealing was set (ppde_chains_set_annealing)");
@@ -1898,6 +1956,29 @@ int ppde_chains_annealing_read(ppde_chains* c, int first_event, int n_events, in
     if (log_mean_w && k) HIPCHK(hipMemcpy(log_mean_w, c->anneal.lmw + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
     if (ess && k) HIPCHK(hipMemcpy(ess, c->anneal.ess + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
     if (beta_now) HIPCHK(hipMemcpy(beta_now, c->anneal.beta, n * sizeof(float), hipMemcpyDeviceToHost));
+    return PPDE_OK;
+}
+
+int ppde_chains_annealing_read_betas(ppde_chains* c, int first_event, int n_events, float* beta_before, float* beta_after) {
+    ARGCHK(c && c->anneal.on(), "ppde_chains_annealing_read_betas: no annealing was set (ppde_chains_set_annealing)");
+    ARGCHK(c->initialised, "chains not initialised");
+    ARGCHK(first_event >= 0 && n_events >= 0 && first_event + n_events <= c->anneal.events_done(c->steps_done),
+           "ppde_chains_annealing_read_betas: events beyond those that have happened (ppde_chains_annealing_shape)");
+    const Annealing& an = c->anneal;
+    const size_t demes = (size_t)c->n / an.D, f = (size_t)first_event, k = (size_t)n_events;
+    if (!an.adaptive) {                             // a fixed schedule: every deme walks it
+        for (size_t ev = 0; ev < k; ++ev)
+            for (size_t d = 0; d < demes; ++d) {
+                if (beta_before) beta_before[ev * demes + d] = an.sched[f + ev];
+                if (beta_after) beta_after[ev * demes + d] = an.sched[f + ev + 1];
+            }
+        return PPDE_OK;
+    }
+    int rc = ppde_chains_sync(c);
+    if (rc) return rc;
+    if (beta_before && k) HIPCHK(hipMemcpy(beta_before, an.beta_pair + f * demes, k * demes * sizeof(float), hipMemcpyDeviceToHost));
+    if (beta_after && k)
+        HIPCHK(hipMemcpy(beta_after, an.beta_pair + ((size_t)an.cap + f) * demes, k * demes * sizeof(float), hipMemcpyDeviceToHost));
     return PPDE_OK;
 }
 

@@ -46,6 +46,15 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         untempered energy. After run(), `sampler.annealing` holds betas, deme, every, parent [events, n] (GLOBAL
                         chain index of the ancestor), pre_energy [events, n], log_mean_w and ess [events, n / deme], beta_now [n]
                         and `summary` (ppde_amd/anneal.py: summarise).
+    ppde_anneal_ess     None (default): off. rho in (0, 1): ADAPTIVE population annealing (include/ppde_hip.h,
+                        ppde_chains_set_annealing_adaptive) in place of a schedule: every deme starts at ppde_anneal_beta_start
+                        and behind every ppde_anneal_every-th iteration takes the largest step towards ppde_anneal_beta_end
+                        (default 1) that keeps the ESS of its incremental weights at rho times the deme, at least
+                        ppde_anneal_min_step (default (end - start) / 4096), for at most ppde_anneal_max_stages events (default
+                        4096). ppde_deme and the conditions of ppde_anneal_betas apply; not together with ppde_anneal_betas.
+                        `sampler.annealing` then holds betas = (start, end), ess_target, min_step, max_stages, the same arrays and
+                        beta_path [events + 1, n / deme], the inverse temperature of every deme before the first and after each
+                        event; its summary adds arrived and stages per deme.
     ppde_recombine_every 0 (default): off. k > 0: behind every k-th iteration the chains of each deme of ppde_recombine_deme
                         consecutive chains (default 0: all chains of the run; even) are paired and every pair proposes to exchange
                         a segment of open residues, accepted by Metropolis on the pair (include/ppde_hip.h,
@@ -252,6 +261,42 @@ def check_annealing(betas, every, deme, reversible, ladder, n_streams):
     return sched, int(every), int(deme)
 
 
+def check_annealing_adaptive(ess, beta_start, beta_end, min_step, max_stages, every, deme, betas, reversible, ladder, n_streams):
+    """None (ess None: off), or dict(ess_target, beta_start, beta_end, min_step, max_stages) of the adaptive ppde_anneal_*
+    arguments in fp32 (min_step None: (beta_end - beta_start) / 4096); ValueError for what the ABI would refuse and can be seen
+    without the population."""
+    if ess is None:
+        return None
+    if betas is not None and len(betas) > 0:
+        raise ValueError("ppde_anneal_ess: an ESS target and a schedule (ppde_anneal_betas) cannot be combined")
+    if not reversible:
+        raise ValueError("ppde_anneal_ess: annealing needs ppde_reversible (only there is the law at beta, exp(beta energy)/Z, defined)")
+    if ladder is not None:
+        raise ValueError("ppde_anneal_ess: annealing and a ladder (ppde_betas) cannot be combined")
+    if beta_start is None:
+        raise ValueError("ppde_anneal_ess needs ppde_anneal_beta_start")
+    rho, b0, b1 = np.float32(ess), np.float32(beta_start), np.float32(1.0 if beta_end is None else beta_end)
+    if not (np.isfinite(rho) and 0 < rho < 1):
+        raise ValueError("ppde_anneal_ess must be inside (0, 1)")
+    if not (np.isfinite(b0) and np.isfinite(b1) and b0 > 0 and b1 > 0):
+        raise ValueError("ppde_anneal_beta_start and ppde_anneal_beta_end must be finite and positive")
+    if not b0 < b1:
+        raise ValueError("ppde_anneal_beta_start must be below ppde_anneal_beta_end")
+    step = np.float32((float(b1) - float(b0)) / 4096.0) if min_step is None else np.float32(min_step)
+    if not (np.isfinite(step) and step >= b1 * np.float32(2.0 ** -20)):
+        raise ValueError("ppde_anneal_min_step must be finite and >= ppde_anneal_beta_end * 2^-20 (a step that changes beta in fp32)")
+    stages = 4096 if max_stages is None else int(max_stages)
+    if not 1 <= stages <= 4096:
+        raise ValueError("ppde_anneal_max_stages must be in 1..4096")
+    if int(every) < 1:
+        raise ValueError("ppde_anneal_every must be >= 1")
+    if int(deme) != 0 and not 2 <= int(deme) <= 1024:
+        raise ValueError("ppde_deme must be in 2..1024 (0: all chains of the run)")
+    if int(n_streams) > 1:
+        raise ValueError("ppde_anneal_ess: ppde_streams > 1 is not supported (the selection couples the chains of a deme)")
+    return dict(ess_target=float(rho), beta_start=float(b0), beta_end=float(b1), min_step=float(step), max_stages=stages)
+
+
 def check_demes(n_global, deme, num_steps, every, n_stages, shard_starts=(0,)):
     """The deme size of a run of n_global chains (deme 0: all of them), or ValueError: a size outside 2..1024, a population or a
     shard boundary that cuts a deme, a run too short for one event."""
@@ -422,6 +467,25 @@ class Chains:
         self._call("set_annealing", C.byref(cfg))
         self.anneal = dict(betas=sched, every=int(every), deme=D)
 
+    def set_annealing_adaptive(self, beta_start, beta_end, ess_target, every=1, deme=None, max_stages=4096, min_step=None):
+        """Adaptive population annealing (include/ppde_hip.h, ppde_chains_set_annealing_adaptive): every deme of `deme` consecutive
+        chains (None: all chains of the object) starts at beta_start and, behind every `every`-th iteration, takes the largest
+        step towards beta_end that keeps the ESS of its incremental weights at ess_target times the deme -- at least min_step
+        (None: (beta_end - beta_start) / 4096), for at most max_stages events. beta_start None clears the mode. Replaces a fixed
+        schedule and is replaced by one. Needs reversible mode; only before init()."""
+        if beta_start is None:
+            self._call("set_annealing_adaptive", None)
+            self.anneal = None
+            return
+        b0, b1 = np.float32(beta_start), np.float32(beta_end)
+        step = np.float32((float(b1) - float(b0)) / 4096.0) if min_step is None else np.float32(min_step)
+        D = self.n if deme is None else int(deme)
+        cfg = _hip.AnnealAdaptiveConfig(deme=D, every=int(every), max_stages=int(max_stages), beta_start=float(b0), beta_end=float(b1),
+                                        ess_target=float(ess_target), min_step=float(step))
+        self._call("set_annealing_adaptive", C.byref(cfg))
+        self.anneal = dict(betas=np.array([b0, b1], np.float32), every=int(every), deme=D, adaptive=True,
+                           ess_target=float(np.float32(ess_target)), min_step=float(step), max_stages=int(max_stages))
+
     def annealing_shape(self):
         """(deme size, event capacity, events that have happened)."""
         d, cap, done = C.c_int32(), C.c_int32(), C.c_int32()
@@ -430,15 +494,18 @@ class Chains:
 
     def annealing_state(self, first=0, count=None):
         """Events [first, first + count) (default: all so far): parent int32 [count, n] (local index of the ancestor), pre_energy
-        fp32 [count, n], log_mean_w / ess fp64 [count, n / D]; beta fp32 [n] each chain holds now; events = how many have happened."""
+        fp32 [count, n], log_mean_w / ess fp64 [count, n / D]; beta_before / beta_after fp32 [count, n / D], the inverse temperature
+        of every deme around each event; beta fp32 [n] each chain holds now; events = how many have happened."""
         D, _, done = self.annealing_shape()
         first = int(first)
         count = done - first if count is None else int(count)
         k = max(count, 0)
         out = dict(parent=np.empty((k, self.n), np.int32), pre_energy=np.empty((k, self.n), np.float32),
                    log_mean_w=np.empty((k, self.n // D), np.float64), ess=np.empty((k, self.n // D), np.float64),
-                   beta=np.empty(self.n, np.float32))
+                   beta=np.empty(self.n, np.float32), beta_before=np.empty((k, self.n // D), np.float32),
+                   beta_after=np.empty((k, self.n // D), np.float32))
         self._call("annealing_read", first, count, *[_hip.ptr(out[k_]) for k_ in ("parent", "pre_energy", "log_mean_w", "ess", "beta")])
+        self._call("annealing_read_betas", first, count, _hip.ptr(out["beta_before"]), _hip.ptr(out["beta_after"]))
         out["events"] = done
         return out
 
@@ -703,9 +770,13 @@ class PPDE_PAS(BaseSampler):
         self.anneal_betas, self.anneal_every, self.deme = check_annealing(
             getattr(args, "ppde_anneal_betas", None), getattr(args, "ppde_anneal_every", 1) or 1, getattr(args, "ppde_deme", 0) or 0,
             self.reversible, self.betas, self.n_streams)
+        self.anneal_adaptive = check_annealing_adaptive(
+            getattr(args, "ppde_anneal_ess", None), getattr(args, "ppde_anneal_beta_start", None), getattr(args, "ppde_anneal_beta_end", 1.0),
+            getattr(args, "ppde_anneal_min_step", None), getattr(args, "ppde_anneal_max_stages", None), self.anneal_every, self.deme,
+            getattr(args, "ppde_anneal_betas", None), self.reversible, self.betas, self.n_streams)
         self.recombine_every, self.recombine_deme = check_recombination(
             getattr(args, "ppde_recombine_every", 0), getattr(args, "ppde_recombine_deme", 0), self.reversible, self.betas,
-            self.anneal_betas, self.paper_results, self.n_streams)
+            self.anneal_betas if self.anneal_adaptive is None else self.anneal_adaptive, self.paper_results, self.n_streams)
         self.recombination = None
         self._recomb_logged = 0     # recombination events the periodic log has reported
         self._recomb_pairs = np.zeros(3, np.int64)   # so far: pairs with differ > 0, accepted ones of them, identical pairs
@@ -758,6 +829,8 @@ class PPDE_PAS(BaseSampler):
         D = 0
         if self.anneal_betas is not None:
             D = check_demes(n_global, self.deme, num_steps, self.anneal_every, self.anneal_betas.size - 1, shard.starts)
+        elif self.anneal_adaptive is not None:
+            D = check_demes(n_global, self.deme, num_steps, self.anneal_every, self.anneal_adaptive["max_stages"], shard.starts)
         X = 0
         if self.recombine_every:
             X = check_recombination_demes(n_global, self.recombine_deme, num_steps, self.recombine_every, shard.starts)
@@ -782,7 +855,11 @@ class PPDE_PAS(BaseSampler):
             chains.set_reversible(True)
         if plan.R:
             chains.set_tempering(self.betas, self.swap_every)
-        if plan.D:
+        if plan.D and self.anneal_adaptive is not None:
+            ad = self.anneal_adaptive
+            chains.set_annealing_adaptive(ad["beta_start"], ad["beta_end"], ad["ess_target"], self.anneal_every, plan.D, ad["max_stages"],
+                                          ad["min_step"])
+        elif plan.D:
             chains.set_annealing(self.anneal_betas, self.anneal_every, plan.D)
         if plan.X:
             chains.set_recombination(self.recombine_every, plan.X)
@@ -849,6 +926,13 @@ class PPDE_PAS(BaseSampler):
             ess = shard.gather(st["ess"], dim=1, size=D)
             replaced = sum(int((row != np.arange(shard.n)).sum()) for row in st["parent"])
             replaced = int(shard.sum(np.array([replaced], np.int64))[0])
+            if self.anneal_adaptive is not None:         # every deme at its own beta: their spread and how many have arrived
+                b = shard.gather(st["beta_after"], dim=1, size=D)[-1]
+                print(f'   # annealing: stage {ev}, beta min / median / max = {float(b.min()):.6g} / {float(np.median(b)):.6g} / '
+                      f'{float(b.max()):.6g}, arrived = {int((b >= np.float32(self.anneal_adaptive["beta_end"])).sum())} of {b.size} '
+                      f'demes, min ESS = {float(ess.min()):.2f} of {D}, slots replaced = {replaced}')
+                self._anneal_logged = ev
+                return
             print(f'   # annealing: stage {ev} of {self.anneal_betas.size - 1}, beta = {float(self.anneal_betas[ev]):.6g}, '
                   f'min ESS = {float(ess.min()):.2f} of {D}, slots replaced = {replaced}')
             self._anneal_logged = ev
@@ -897,11 +981,19 @@ class PPDE_PAS(BaseSampler):
         if not D:
             return None
         st = chains.annealing_state()
-        an = dict(betas=self.anneal_betas.copy(), deme=D, every=self.anneal_every,
+        ad = self.anneal_adaptive
+        betas = self.anneal_betas.copy() if ad is None else np.array([ad["beta_start"], ad["beta_end"]], np.float32)
+        an = dict(betas=betas, deme=D, every=self.anneal_every,
                   parent=shard.gather(shard.to_global(st["parent"]), dim=1), pre_energy=shard.gather(st["pre_energy"], dim=1),
                   log_mean_w=shard.gather(st["log_mean_w"], dim=1, size=D), ess=shard.gather(st["ess"], dim=1, size=D),
                   beta_now=shard.gather(st["beta"]))
-        an["summary"] = chain_anneal.summarise(an["parent"], an["log_mean_w"], an["ess"], an["betas"])
+        if ad is None:
+            an["summary"] = chain_anneal.summarise(an["parent"], an["log_mean_w"], an["ess"], an["betas"])
+            return an
+        after = shard.gather(st["beta_after"], dim=1, size=D)
+        an.update(ess_target=ad["ess_target"], min_step=ad["min_step"], max_stages=ad["max_stages"],
+                  beta_path=np.concatenate([np.full((1, after.shape[1]), betas[0], np.float32), after], 0))
+        an["summary"] = chain_anneal.summarise(an["parent"], an["log_mean_w"], an["ess"], an["beta_path"], beta_end=betas[1])
         return an
 
     def _collect_samples(self, chains, shard, R):

@@ -10,6 +10,14 @@ whose code this mode does not touch.
   sparse       set_annealing(linspace(0.25, 1, 41), every 50): the way the mode is meant to be run
   events       set_annealing(4096 stages of 0.25 -> 1, every 1): a selection behind EVERY timed iteration: the event's own time
                (a schedule has at most 4096 stages, so this variant's rounds are shorter: warm-up + rounds x steps <= 4096)
+  fixed10, fixed100        set_annealing(0.25 -> 1 in as many stages as events fit, every 10 / 100)
+  adaptive, adaptive10, adaptive100   set_annealing_adaptive(0.25, 1, --ess, every 1 / 10 / 100, min_step 2^-20): DESIGN.md §4.2k, the
+               same number of events as events / fixed10 / fixed100. An event of a deme that has not arrived costs one fp64
+               workgroup reduction (the whole remainder passes) or 49 (the bisection); which of the two each timed event was is
+               read back from the recorded beta pairs and reported next to the time
+  adaptive_search          set_annealing_adaptive(0.25, 64, 0.999999, every 1, min_step 64 x 2^-20): a target and an end chosen so that
+               the deme never arrives and every timed event runs all 49 reductions -- against `events`, which has an event behind
+               every iteration too, the difference is the search itself
 
   python scripts/anneal_cost.py [--steps 2000] [--rounds 5] [--out profiles/anneal_step_cost.md]
 
@@ -32,6 +40,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--chains", type=int, default=128)
+    ap.add_argument("--ess", type=float, default=0.999, help="ESS target of the adaptive variants (close to 1: many small steps, so "
+                                                             "that most timed events run the bisection)")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "anneal_step_cost.md"))
     a = ap.parse_args()
     import numpy as np
@@ -54,7 +64,16 @@ def main():
         "idle": lambda ch: ch.set_annealing((1.0, 1.0), 1, n),
         "sparse": lambda ch: ch.set_annealing(np.linspace(0.25, 1.0, 41), 50, n),
         "events": lambda ch: ch.set_annealing(np.linspace(0.25, 1.0, 4097), 1, n),
+        "adaptive": lambda ch: ch.set_annealing_adaptive(0.25, 1.0, a.ess, 1, n, 4096, 2.0 ** -20),
+        "adaptive_search": lambda ch: ch.set_annealing_adaptive(0.25, 64.0, 0.999999, 1, n, 4096, 64 * 2.0 ** -20),
     }
+    every_of = {k: 1 for k in variants}
+    every_of["sparse"] = 50
+    for k in (10, 100):
+        stages = min(4096, T // k)
+        variants[f"fixed{k}"] = lambda ch, k=k, stages=stages: ch.set_annealing(np.linspace(0.25, 1.0, stages + 1), k, n)
+        variants[f"adaptive{k}"] = lambda ch, k=k: ch.set_annealing_adaptive(0.25, 1.0, a.ess, k, n, 4096, 2.0 ** -20)
+        every_of[f"fixed{k}"] = every_of[f"adaptive{k}"] = k
     chains = {}
     for name, setup in variants.items():
         ch = Chains(m, n, T, 2, 0, False, 0, L - 1, 3, 1, reuse_grad=True, random_chain=-1, seed=1, use_graph=True)
@@ -67,7 +86,7 @@ def main():
         chains[name] = ch
     us = {k: [] for k in variants}
     steps_of = {k: a.steps for k in variants}
-    steps_of["events"] = min(a.steps, (4096 - a.warmup) // a.rounds)          # every timed iteration of it has an event
+    steps_of["events"] = steps_of["adaptive"] = steps_of["adaptive_search"] = min(a.steps, (4096 - a.warmup) // a.rounds)   # every timed iteration of them has an event
     for _ in range(a.rounds):
         for name, ch in chains.items():
             t0 = time.perf_counter()
@@ -75,9 +94,20 @@ def main():
             ch.sync()
             us[name].append((time.perf_counter() - t0) / steps_of[name] * 1e6)
     notes = {}
-    for name in ("idle", "sparse", "events"):
+    timed = {}                                                               # adaptive variants: (events, bisected, one reduction) in the timed iterations
+    for name in variants:
+        if name == "tempering1":
+            continue
         st = chains[name].annealing_state()
         notes[name] = f"{st['events']} events, {int((st['parent'] != np.arange(n)[None]).sum())} slots replaced, smallest ESS {st['ess'].min():.1f}"
+        if name.startswith("adaptive"):
+            k, first = every_of[name], a.warmup // every_of[name]            # (events 0 .. first - 1 lie in the warm-up)
+            last = min(st["events"], (a.warmup + a.rounds * steps_of[name]) // k)
+            before, after = st["beta_before"][first:last, 0], st["beta_after"][first:last, 0]
+            end = 64.0 if name == "adaptive_search" else 1.0
+            timed[name] = (last - first, int((after < end).sum()), int(((before < end) & (after >= end)).sum()))
+            notes[name] += (f"; timed: {timed[name][0]} events, {timed[name][1]} bisected (49 reductions), {timed[name][2]} arrivals (1 to 49), "
+                            f"{timed[name][0] - timed[name][1] - timed[name][2]} after arrival (none)")
     notes["tempering1"] = "-"
     med = {k: float(np.median(v)) for k, v in us.items()}
     lines = ["# Cost of population annealing per iteration (scripts/anneal_cost.py)", "",
@@ -102,6 +132,26 @@ def main():
               f"`events` pays a selection behind every iteration: the event's own time is {med['events'] - med['idle']:.2f} us (events - idle), the plan",
               "of one deme of 128 (one workgroup) and the copy launch (128 workgroups, the replaced ones copying a row).",
               f"`sparse` ({sparse_events} events in {a.warmup + a.rounds * a.steps} iterations) is the mode as it is meant to be run."]
+    lines += ["", "## The adaptive form (DESIGN.md §4.2k)", "",
+              f"`adaptive*` choose each step on the device (ESS target {a.ess:g}, 0.25 -> 1, min_step 2^-20) and are set against the fixed-schedule",
+              "run with the same number of events at the same `every`. The difference is what the search costs; an event after the deme's",
+              "arrival searches nothing, so the difference is also given per bisected event (difference x timed iterations / bisected events;",
+              "`-` when no timed event bisected).", "",
+              "| every | fixed us / iteration | adaptive us / iteration | difference per iteration | per event (x every) | per bisected event |",
+              "|---|---|---|---|---|---|"]
+    for k, fx, ad in ((1, "events", "adaptive"), (10, "fixed10", "adaptive10"), (100, "fixed100", "adaptive100")):
+        d = med[ad] - med[fx]
+        bis = timed[ad][1]
+        per_bis = f"{d * a.rounds * steps_of[ad] / bis:.2f}" if bis else "-"
+        lines.append(f"| {k} | {med[fx]:.2f} ({min(us[fx]):.2f} .. {max(us[fx]):.2f}) | {med[ad]:.2f} ({min(us[ad]):.2f} .. {max(us[ad]):.2f}) | "
+                     f"{d:+.2f} | {d * k:+.2f} | {per_bis} |")
+    d = med["adaptive_search"] - med["events"]
+    ev, bis, _ = timed["adaptive_search"]
+    lines += ["",
+              f"`adaptive_search` (0.25 -> 64 at an ESS target of 0.999999: {bis} of its {ev} timed events ran the bisection, the deme at beta = "
+              f"{float(chains['adaptive_search'].annealing_state()['beta'][0]):.4g} at the end) against `events`: {med['adaptive_search']:.2f} "
+              f"({min(us['adaptive_search']):.2f} .. {max(us['adaptive_search']):.2f}) - {med['events']:.2f} = {d:+.2f} us per event for the search of "
+              f"one deme of {n}, {d / 49:.3f} us per fp64 workgroup reduction (4 fp64 exp per thread, two DPP wave sums, one barrier)."]
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)

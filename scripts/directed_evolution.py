@@ -139,7 +139,8 @@ def main(args):
                 np.save(results_path / f"{name}.npy", tempering[name])
         annealing = getattr(sampler, "annealing", None)
         if annealing is not None:
-            for name in ("parent", "pre_energy", "log_mean_w", "ess", "betas"):
+            # (an adaptive run has no schedule: the path every deme chose takes the place of anneal_betas.npy)
+            for name in ("parent", "pre_energy", "log_mean_w", "ess", "beta_path" if "beta_path" in annealing else "betas"):
                 np.save(results_path / f"anneal_{name}.npy", annealing[name])
         recombination = getattr(sampler, "recombination", None)
         if recombination is not None:
@@ -256,7 +257,18 @@ def build_parser():
                          "resampled with weights exp(dbeta energy) and moves to the next. Writes anneal_parent.npy [events, n], "
                          "anneal_pre_energy.npy [events, n], anneal_log_mean_w.npy and anneal_ess.npy [events, demes] and "
                          "anneal_betas.npy; the periodic log gains a line when a stage was passed")
-    pp.add_argument("--ppde_anneal_every", type=int, default=1, help="with --ppde_anneal_betas: iterations per stage of the schedule")
+    pp.add_argument("--ppde_anneal_ess", type=float, default=None,
+                    help="adaptive population annealing (needs --ppde_reversible; not with --ppde_anneal_betas or --ppde_betas): no "
+                         "schedule; at each event every deme takes the largest step in beta whose incremental weights keep an "
+                         "effective sample size of this fraction of the deme, inside (0, 1). Writes the anneal_*.npy files of "
+                         "--ppde_anneal_betas with anneal_beta_path.npy [events + 1, demes] in place of anneal_betas.npy")
+    pp.add_argument("--ppde_anneal_beta_start", type=float, default=None, help="with --ppde_anneal_ess: the beta every chain starts at")
+    pp.add_argument("--ppde_anneal_beta_end", type=float, default=1.0, help="with --ppde_anneal_ess: the beta the demes climb to")
+    pp.add_argument("--ppde_anneal_min_step", type=float, default=None,
+                    help="with --ppde_anneal_ess: the smallest step in beta (default (end - start) / 4096; at least end * 2^-20)")
+    pp.add_argument("--ppde_anneal_max_stages", type=int, default=4096, help="with --ppde_anneal_ess: events at most, 1..4096")
+    pp.add_argument("--ppde_anneal_every", type=int, default=1,
+                    help="with --ppde_anneal_betas or --ppde_anneal_ess: iterations per stage of the schedule / between two events")
     pp.add_argument("--ppde_deme", type=int, default=0,
                     help="with --ppde_anneal_betas: chains per deme, 2..1024 (0: all chains of the run); consecutive chains form a "
                          "deme, --n_chains must be a multiple of it")
