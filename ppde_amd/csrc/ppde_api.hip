@@ -1,5 +1,6 @@
-// Host side of the C ABI declared in include/ppde_hip.h: device memory ownership, weight re-layout,
-// kernel launches, hipGraph capture of the iteration loop.
+// Host side of the C ABI declared in include/ppde_hip.h, the one translation unit of the library. Here: device memory ownership,
+// the model and its weight re-layout, the expert launch layer, ppde_energy_grad. The chains object (ppde_chains_*, hipGraph capture
+// and replay of the iteration loop) is in chains.h and the *_host.h it includes, at the end of this file.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
@@ -1133,1640 +1134,4 @@ int ppde_energy_grad(ppde_model* m, const uint8_t* idx_dev, int n, int which, fl
 }  // extern "C"
 
 // --------------------------------------------------------------------------------------------
-// The optional modes of a chains object, one struct each: what the mode was set with, its device buffers and the sizes that follow
-// from them. A mode is on while it holds its buffers. ppde_chains_set_* builds a local one and moves it into the object once
-// everything is allocated (a failure on the way leaves the object as it was and the local's destructor releases what there is);
-// assigning {} clears it.
-
-// parallel tempering (ppde_chains_set_tempering)
-struct Tempering {
-    int n_rungs = 0, swap_every = 0;
-    std::vector<float> ladder;                   // beta[0] > beta[1] > ... > 0
-    DevBuf<float> beta;                          // [n]
-    DevBuf<int> rung, slot;                      // [n], [n/R][R]
-    DevBuf<long long> swap_attempts, swap_accepts;   // [n/R][R-1]
-    DevBuf<uint8_t> rung_hist;                   // [T+1][n]
-    bool on() const { return beta.p != nullptr; }
-};
-
-// population annealing (ppde_chains_set_annealing, ppde_chains_set_annealing_adaptive)
-struct Annealing {
-    int D = 0, every = 0, S = 0, cap = 0;        // deme size, iterations per stage, stages (adaptive: max_stages), events_cap
-    std::vector<float> sched;                    // beta[0] <= ... <= beta[S] (adaptive: beta_start, beta_end)
-    DevBuf<float> sched_dev, beta, pre;          // [S+1] (adaptive: [2]), [n], [events_cap][n]
-    bool adaptive = false;                       // the deme chooses each step (k_select_plan_adaptive)
-    float rho = 0.f, min_step = 0.f;             // its ESS target and its smallest step
-    DevBuf<float> beta_pair;                     // [2][events_cap][n/D] beta before / after every event (adaptive only)
-    DevBuf<int> parent;                          // [events_cap][n]
-    DevBuf<double> lmw, ess;                     // [events_cap][n/D]
-    bool on() const { return sched_dev.p != nullptr; }
-    int events_done(int steps_done) const { return std::min(cap, steps_done / every); }
-};
-
-// recombination (ppde_chains_set_recombination)
-struct Recombination {
-    int D = 0, every = 0, cap = 0;               // deme size, iterations per event, events_cap
-    std::vector<int32_t> open;                   // the open list: residues of [min_pos, max_pos] the library leaves open, increasing
-    DevBuf<int> open_dev;                        // [n_open]
-    DevBuf<int> partner, lo, hi, differ, child_dist;   // [events_cap][n] each
-    DevBuf<uint8_t> outcome;
-    DevBuf<float> log_ratio, pre, child;
-    bool on() const { return open_dev.p != nullptr; }
-    int events_done(int steps_done) const { return std::min(cap, steps_done / every); }
-    bool event(int it) const { return (it + 1) % every == 0; }   // (it: absolute, or relative to a multiple of every)
-};
-
-// recorder (ppde_chains_set_recorder)
-struct Recorder {
-    ppde_record_config cfg{};
-    int rows_cap = 0, slots = 0;
-    DevBuf<uint8_t> idx;                         // [rows_cap][slots][Ls] (keep_samples)
-    DevBuf<float> e, f;                          // [rows_cap][slots]
-    DevBuf<int> chain;
-    DevBuf<unsigned long long> counts;           // [L][20]
-    bool on() const { return counts.p != nullptr; }
-    int rows_done(int steps_done) const { return steps_done > cfg.burn_in ? (steps_done - cfg.burn_in) / cfg.every : 0; }
-};
-
-// pair counts (ppde_chains_set_pair_counts)
-struct PairCounts {
-    std::vector<int32_t> sites;                  // [S] residues, strictly increasing
-    int nt = 0;                                  // tiles per side (pairs.h)
-    DevBuf<int> sites_dev;                       // [nt * PAIR_TS], padded with -1
-    DevBuf<unsigned long long> counts;           // [nt (nt + 1) / 2][PAIR_TILE]
-    bool on() const { return counts.p != nullptr; }
-    size_t tiles() const { return (size_t)nt * ((size_t)nt + 1) / 2; }
-};
-
-// archive (ppde_chains_set_archive)
-struct Archive {
-    int k = 0;
-    DevBuf<uint8_t> idx;                         // [n][K][Ls]
-    DevBuf<float> e, f;                          // [n][K]
-    DevBuf<int> step, count;                     // [n][K], [n]
-    DevBuf<unsigned int> hash;                   // [n][K] fingerprints (archive.h)
-    bool on() const { return idx.p != nullptr; }
-};
-
-// move statistics (ppde_chains_set_stats)
-struct MoveStats {
-    int n = 0, R = 1, M = 0, L = 0, per_site = 0;   // the shape at the set call: chains, R' = max(n_rungs, 1), path lengths, residues
-    DevBuf<long long> cnt;                       // six [n][R'], two [R'][M], then [R'][L] with per_site (counter)
-    DevBuf<uint8_t> prev;                        // [2][n][Ls] the state the last counted iteration left, read and written in turns (stats.h)
-    DevBuf<int> dist;                            // [n]     its mutation count
-    bool on() const { return cnt.p != nullptr; }
-    // the counters in one allocation: k = 0..5 iters, accepts, moved, jump_sum, dist_sum, wt_returns [n][R'];
-    // 6, 7 len_attempts, len_accepts [R'][M]; 8 site_changes [R'][L]
-    size_t cells(int k) const { return k < 6 ? (size_t)n * R : k < 8 ? (size_t)R * M : per_site ? (size_t)R * L : 0; }
-    size_t cells_before(int k) const {
-        size_t o = 0;
-        for (int j = 0; j < k; ++j) o += cells(j);
-        return o;
-    }
-    long long* counter(int k) const { return cnt + cells_before(k); }
-    size_t cells_total() const { return cells_before(9); }
-};
-
-struct ppde_chains {
-    ppde_model* m = nullptr;
-    int device = 0;                              // (kept here: destroy must not depend on the model still being alive)
-    ppde_chain_config cfg{};
-    hipStream_t stream = nullptr;                // == streams[0]
-    std::vector<hipStream_t> streams;            // one per sub-population
-    std::vector<hipEvent_t> events;              // fork (0) / join (1..) markers
-    std::vector<int> sub_off, sub_n;             // sub-population k covers chains [sub_off[k], sub_off[k] + sub_n[k])
-    int n = 0, T = 0, mu_max = 1, steps_done = 0;
-    bool initialised = false;
-    // device buffers
-    uint32_t *curT = nullptr, *propT = nullptr;  // T4 copies of cur / prop (potts.h), n_pad chains per row
-    int n_pad = 0;
-    uint8_t *cur = nullptr, *prop = nullptr, *fb_state = nullptr, *best_state = nullptr,
-            *rtraj = nullptr, *tmp_acc = nullptr, *tr_acc = nullptr, *tmp_idx = nullptr;
-    unsigned char* rec = nullptr;                // [n] chain records
-    int rec_stride = 0;
-    float wt_e = 0.f, wt_f = 0.f;                // wild type's energy / fitness (mutation-cap reset under gradient reuse)
-    float *grad_cur = nullptr, *grad = nullptr, *epart = nullptr, *gradC = nullptr, *fitC = nullptr,
-          *fb_grad = nullptr, *fb_e = nullptr, *fb_f = nullptr, *e_hist = nullptr,
-          *f_hist = nullptr, *tmp_be = nullptr, *tmp_bf = nullptr, *tr_logacc = nullptr;
-    int* h_err = nullptr;                        // pinned, device-mapped host word behind err_flag: the sync reads it without a copy
-    long long d_it_val = -1;                     // value the device iteration counter holds (-1: unknown)
-    int *tmp_bt = nullptr, *tr_flat = nullptr, *tr_U = nullptr, *err_flag = nullptr,
-        *d_it = nullptr, *tmp_dist = nullptr;
-    unsigned long long* dbg = nullptr;           // stamps of the diagnostic build (64 x (cycles, 100 MHz ticks))
-    // transformer expert: this object's activation workspace, gradient rows [2][n][N] and scores [2][n]
-    TfWork* tfw = nullptr;
-    float *gradT = nullptr, *tfE = nullptr;
-    // chunk scratch of the long-sequence CNN path (this object's own: its graphs hold these pointers)
-    float* cnn_cmax = nullptr;
-    int* cnn_carg = nullptr;
-    uint32_t* cnn_cgate = nullptr;
-    // graph replay: segments of different lengths, longest first, captured once by ppde_chains_init
-    struct GraphSeg { hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr; int len = 0; };
-    std::vector<GraphSeg> graphs;
-    int n_captures = 0, n_captures_in_run = 0;   // graphs captured in all / inside ppde_chains_run (must stay 0)
-    long long n_replayed_steps = 0, n_eager_steps = 0;
-    std::vector<void*> allocs;
-    DevBuf<uint32_t> allowed;                    // design library [L] (ppde_chains_set_library); NULL = none
-    bool reversible = false;                     // ppde_chains_set_reversible: the accept phases run the *_rev kernels
-    Tempering temper;
-    Annealing anneal;
-    Recombination recomb;
-    Recorder recorder;
-    PairCounts pairs;
-    Archive archive;
-    MoveStats stats;
-
-    ppde_chains() = default;
-    ppde_chains(const ppde_chains&) = delete;
-    ppde_chains& operator=(const ppde_chains&) = delete;
-    // everything the object owns; the members (the modes' buffers) go after the body, with this device current
-    ~ppde_chains() {
-        hipSetDevice(device);
-        for (auto& gs : graphs) {
-            if (gs.exec) hipGraphExecDestroy(gs.exec);
-            if (gs.graph) hipGraphDestroy(gs.graph);
-        }
-        for (void* p : allocs) hipFree(p);
-        delete tfw;
-        if (h_err) hipHostFree(h_err);
-        for (hipStream_t st : streams) if (st) hipStreamDestroy(st);
-        for (hipEvent_t ev : events) if (ev) hipEventDestroy(ev);
-    }
-};
-
-static PasArgs chain_args(const ppde_chains* c) {
-    const ppde_model* m = c->m;
-    PasArgs a = base_pas_args(m, c->cfg.which, c->n);
-    a.pas = c->cfg.pas_length;
-    a.thr = c->cfg.nmut_threshold == 0 ? 0x7fffffff : c->cfg.nmut_threshold;
-    a.paper = c->cfg.paper_results; a.min_pos = c->cfg.min_pos; a.max_pos = c->cfg.max_pos;
-    a.rng_mode = c->cfg.rng_mode; a.reuse = c->cfg.reuse_grad; a.rec_after_reset = c->cfg.record_after_reset;
-    a.random_chain = c->cfg.random_chain; a.mu_max = c->mu_max; a.mu_cap = c->mu_max;
-    a.key.k0 = (uint32_t)c->cfg.seed;
-    a.key.k1 = (uint32_t)(c->cfg.seed >> 32) ^ (uint32_t)(c->cfg.chain_offset >> 32);
-    a.key.chain_lo = (uint32_t)c->cfg.chain_offset;
-    a.cur = c->cur; a.prop = c->prop; a.fb_state = c->fb_state;
-    a.curT = (uint8_t*)c->curT; a.propT = (uint8_t*)c->propT; a.n_pad = c->n_pad;
-    a.fb_state_stride = c->cfg.paper_results ? m->g.Ls : 0;
-    a.grad = c->grad; a.epart = c->epart; a.gradC = c->gradC; a.fitC = c->fitC;
-    a.gradT = c->gradT; a.tfE = c->tfE;
-    a.grad_cur = c->grad_cur; a.rec = c->rec; a.rec_stride = c->rec_stride; a.wt_e = c->wt_e; a.wt_f = c->wt_f;
-    a.fb_grad = c->fb_grad; a.fb_grad_stride = c->cfg.paper_results ? (size_t)m->g.N : 0;
-    a.e_hist = c->e_hist; a.f_hist = c->f_hist; a.best_state = c->best_state; a.rtraj = c->rtraj;
-    a.tr_flat = c->tr_flat; a.tr_acc = c->tr_acc; a.tr_logacc = c->tr_logacc; a.tr_U = c->tr_U;
-    a.err_flag = c->err_flag;
-    a.dbg = c->dbg;
-    a.allowed = c->allowed;
-    a.beta = c->anneal.on() ? c->anneal.beta.p : c->temper.beta.p; a.rung = c->temper.rung; a.slot = c->temper.slot; a.swap_attempts = c->temper.swap_attempts; a.swap_accepts = c->temper.swap_accepts;
-    a.rung_hist = c->temper.rung_hist; a.n_rungs = c->temper.n_rungs; a.swap_every = c->temper.swap_every;
-    return a;
-}
-
-// the recorder's kernel for iteration it_base + it_local (record.h): every chain of the object; reads cur, the history rows, slot
-static int launch_record(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
-    const Geom& g = c->m->g;
-    const Recorder& rec = c->recorder;
-    RecArgs r{};
-    r.it_base = it_base; r.it_local = it_local;
-    r.n = c->n; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
-    r.burn_in = rec.cfg.burn_in; r.every = rec.cfg.every; r.rung = rec.cfg.rung; r.n_rungs = c->temper.n_rungs; r.slots = rec.slots;
-    r.cur = c->cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist; r.slot = c->temper.slot;
-    r.idx = rec.idx; r.energy = rec.e; r.fitness = rec.f; r.chain = rec.chain; r.counts = rec.counts;
-    hipLaunchKernelGGL(k_record, dim3(((g.Ls >> 2) + 3) / 4), dim3(REC_BLOCK), 0, s, r);
-    HIPCHK(hipGetLastError());
-    return PPDE_OK;
-}
-
-// the pair counts' kernel for the same iteration (pairs.h), on the recorder's schedule and slots; reads cur and slot only
-static int launch_pairs(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
-    const Geom& g = c->m->g;
-    const Recorder& rec = c->recorder;
-    PairArgs p{};
-    p.it_base = it_base; p.it_local = it_local; p.Ls = g.Ls; p.sh = g.sh;
-    p.burn_in = rec.cfg.burn_in; p.every = rec.cfg.every; p.rung = rec.cfg.rung; p.n_rungs = c->temper.n_rungs; p.slots = rec.slots;
-    p.nt = c->pairs.nt; p.cur = c->cur; p.slot = c->temper.slot; p.sites = c->pairs.sites_dev; p.counts = c->pairs.counts;
-    hipLaunchKernelGGL(k_record_pairs, dim3((unsigned)c->pairs.tiles()), dim3(PAIR_BLOCK), 0, s, p);
-    HIPCHK(hipGetLastError());
-    return PPDE_OK;
-}
-
-// the archive's kernel for the state after it_base + it_local + 1 completed iterations (archive.h): every chain of the object
-static int launch_archive(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
-    const Geom& g = c->m->g;
-    ArchArgs r{};
-    r.it_base = it_base; r.it_local = it_local;
-    r.n = c->n; r.K = c->archive.k; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
-    r.rec = c->rec; r.rec_stride = c->rec_stride; r.cur = c->cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist;
-    r.idx = c->archive.idx; r.energy = c->archive.e; r.fitness = c->archive.f; r.step = c->archive.step; r.count = c->archive.count;
-    r.hash = c->archive.hash;
-    hipLaunchKernelGGL(k_archive, dim3((c->n + ARCH_BLOCK / 64 - 1) / (ARCH_BLOCK / 64)), dim3(ARCH_BLOCK), 0, s, r);
-    HIPCHK(hipGetLastError());
-    return PPDE_OK;
-}
-
-// the statistics' kernel for iteration it_base + it_local (stats.h): every chain of the object. U / mu_cap: the caller-supplied
-// path lengths of that iteration and the sub-steps its noise covers (rng_mode 0)
-static int launch_stats(ppde_chains* c, const int* it_base, int it_local, const int* U, int mu_cap, hipStream_t s) {
-    const Geom& g = c->m->g;
-    StatArgs r{};
-    r.it_base = it_base; r.it_local = it_local;
-    r.n = c->n; r.R = c->stats.R; r.M = c->mu_max; r.L = g.L; r.Ls = g.Ls; r.sh = g.sh;
-    r.rng_mode = c->cfg.rng_mode; r.pas = c->cfg.pas_length; r.mu_cap = mu_cap > 0 ? mu_cap : c->mu_max;
-    r.key = chain_args(c).key;
-    r.rec = c->rec; r.rec_stride = c->rec_stride; r.cur = c->cur; r.rung_hist = c->temper.on() ? c->temper.rung_hist.p : nullptr; r.U_in = U;
-    r.prev = c->stats.prev; r.pdist = c->stats.dist;
-    const MoveStats& st = c->stats;
-    r.iters = st.counter(0); r.accepts = st.counter(1); r.moved = st.counter(2); r.jump_sum = st.counter(3);
-    r.dist_sum = st.counter(4); r.wt_returns = st.counter(5);
-    r.len_attempts = st.counter(6); r.len_accepts = st.counter(7);
-    r.site_changes = st.per_site ? st.counter(8) : nullptr;
-    r.site_blocks = c->stats.per_site ? ((g.Ls >> 2) + 3) / 4 : 0;
-    const size_t lds = std::max(2 * (size_t)r.M, (size_t)16) * r.R * sizeof(unsigned int);   // (at most 64 x 127 x 2 cells: 65 024 bytes)
-    hipLaunchKernelGGL(k_stats, dim3(r.site_blocks + (c->n + STAT_NW - 1) / STAT_NW + 1), dim3(STAT_BLOCK), lds, s, r);
-    HIPCHK(hipGetLastError());
-    return PPDE_OK;
-}
-
-// the two selection kernels behind the accept phase of iteration it_base + it_local (anneal.h): every chain of the object
-static int launch_select(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
-    const PasArgs p = chain_args(c);
-    AnnealArgs r{};
-    r.it_base = it_base; r.it_local = it_local;
-    r.n = c->n; r.D = c->anneal.D; r.every = c->anneal.every; r.S = c->anneal.S;
-    r.g = p.g; r.n_pad = c->n_pad; r.key = p.key;
-    r.rec_stride = c->rec_stride; r.random_chain = c->cfg.random_chain; r.reuse = c->cfg.reuse_grad;
-    r.sched = c->anneal.sched_dev; r.beta = c->anneal.beta; r.rec = c->rec; r.cur = c->cur; r.curT = (uint8_t*)c->curT;
-    r.grad_cur = c->grad_cur; r.e_hist = c->e_hist; r.f_hist = c->f_hist; r.best_state = c->best_state; r.rtraj = c->rtraj;
-    r.parent = c->anneal.parent; r.pre_energy = c->anneal.pre; r.log_mean_w = c->anneal.lmw; r.ess = c->anneal.ess;
-    if (c->anneal.adaptive) {
-        const AnnealStepArgs x{c->anneal.sched[1], c->anneal.rho, c->anneal.min_step, c->anneal.cap, c->anneal.beta_pair};
-        hipLaunchKernelGGL(k_select_plan_adaptive, dim3(c->n / c->anneal.D), dim3(ANNEAL_BLOCK), 0, s, r, x);
-    } else {
-        hipLaunchKernelGGL(k_select_plan, dim3(c->n / c->anneal.D), dim3(ANNEAL_BLOCK), 0, s, r);
-    }
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_select_copy, dim3(c->n), dim3(ANNEAL_BLOCK), 0, s, r);
-    HIPCHK(hipGetLastError());
-    return PPDE_OK;
-}
-
-static States cur_states(const ppde_chains* c) { return States{c->cur, c->curT, c->n_pad}; }
-static States prop_states(const ppde_chains* c) { return States{c->prop, c->propT, c->n_pad}; }
-static EvalTargets chain_targets(const ppde_chains* c, int slot) {
-    EvalTargets t{c->grad, c->epart, c->gradC, c->fitC, slot, c->dbg};
-    t.cmax = c->cnn_cmax; t.carg = c->cnn_carg; t.cgate = c->cnn_cgate; t.cnn_cap = c->n;
-    t.gradT = c->gradT; t.tfE = c->tfE; t.tfw = c->tfw;
-    return t;
-}
-
-// the recombination event behind the accept phase of iteration it_base + it_local (recombine.h): the children of every pair into
-// the proposal slot, the run's expert evaluation of that slot, the decision and the hand-over. Every chain of the object.
-static int launch_cross(ppde_chains* c, const int* it_base, int it_local, hipStream_t s) {
-    const Recombination& rc = c->recomb;
-    CrossArgs r{};
-    r.p = chain_args(c);
-    r.p.it_base = it_base; r.p.it_local = it_local;
-    r.D = rc.D; r.every = rc.every; r.cap = rc.cap; r.n_open = (int)rc.open.size();
-    r.open = rc.open_dev; r.partner = rc.partner; r.lo = rc.lo; r.hi = rc.hi; r.differ = rc.differ; r.child_dist = rc.child_dist;
-    r.outcome = rc.outcome; r.log_ratio = rc.log_ratio; r.pre_energy = rc.pre; r.child_energy = rc.child;
-    hipLaunchKernelGGL(k_cross_propose, dim3(c->n / 2), dim3(CROSS_BLOCK), 0, s, r);
-    HIPCHK(hipGetLastError());
-    int e = eval_experts(c->m, c->cfg.which, prop_states(c), c->n, chain_targets(c, 1), 1, s, 0, c->n);
-    if (e) return e;
-    hipLaunchKernelGGL(k_cross_accept, dim3(c->n / 2), dim3(CROSS_BLOCK), 0, s, r);
-    HIPCHK(hipGetLastError());
-    return PPDE_OK;
-}
-
-enum ChainKernel { KP_PROPOSE, KP_ACCEPT, KP_ACCEPT_PROPOSE };
-
-static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs& a, int n_sub, hipStream_t s) {
-    const ppde_model* m = c->m;
-    // a run with a design library: the forward paths go to the general *_lib kernels with room for the words in LDS; the
-    // accept kernel (no masks on the way back in the default mode) and every run without a library keep their instantiations
-    // and LDS size
-    // (reversible mode: the reverse rows take the library too, so its accept kernel stages the words as well)
-    const bool rev = c->reversible && which != KP_PROPOSE;
-    const bool lib = a.allowed != nullptr && (which != KP_ACCEPT || rev);
-    const size_t lds = pas_lds_bytes(m->g) + (lib ? pas_lib_lds_bytes(m->g) : 0);
-    const int gpt = (m->g.N / 4 + PPDE_BLOCK - 1) / PPDE_BLOCK;
-    // specialised instantiation for the common configurations (pas.h pin_config), the general kernel otherwise
-    static const bool spec_on = env_int("PPDE_CHAIN_SPEC", 1) != 0;   // tuning knob
-    int spec = 0;
-    if (spec_on && a.rng_mode == 1 && !a.paper && !a.rec_after_reset && !a.tr_flat && a.which == a.gwhich &&
-        (a.which == 1 || a.which == 3))
-        spec = (a.which == 1 ? PAS_SPEC_POTTS : PAS_SPEC_POE) | (a.thr == 0x7fffffff ? PAS_SPEC_NOCAP : 0) |
-               (which == KP_ACCEPT_PROPOSE ? 0 : a.reuse ? PAS_SPEC_REUSE : PAS_SPEC_REEVAL);
-    // (every specialisation the host can ask for is instantiated below: experts x cap x policy; the fused kernel has no policy bit)
-    auto with_gpt = [&](auto&& f) {
-        switch (gpt) {
-            case 1: f(std::integral_constant<int, 1>{}); break;
-            case 2: f(std::integral_constant<int, 2>{}); break;
-            default: f(std::integral_constant<int, 3>{}); break;
-        }
-    };
-    auto with_spec = [&](auto&& f) {
-        switch (spec) {
-#define PPDE_SP(v) case (v): f(std::integral_constant<int, (v)>{}); break;
-#define PPDE_SP3(b) PPDE_SP(b) PPDE_SP((b) | PAS_SPEC_REEVAL) PPDE_SP((b) | PAS_SPEC_REUSE)
-            PPDE_SP3(PAS_SPEC_POTTS) PPDE_SP3(PAS_SPEC_POTTS | PAS_SPEC_NOCAP) PPDE_SP3(PAS_SPEC_POE) PPDE_SP3(PAS_SPEC_POE | PAS_SPEC_NOCAP)
-#undef PPDE_SP3
-#undef PPDE_SP
-            default: f(std::integral_constant<int, 0>{}); break;
-        }
-    };
-    hipEvent_t evs = g_potts_events ? g_potts_events->next(false) : nullptr;       // (in-situ timing: this kernel's end = the next Potts launch's start)
-    auto go = [&](auto k) { launch_kernel(k, dim3(n_sub), dim3(PPDE_BLOCK), lds, s, evs, a); };
-    with_gpt([&](auto G) {
-        constexpr int GP = decltype(G)::value;
-        if (c->temper.on() || c->anneal.on()) {          // tempering, annealing (reversible mode): general instantiations, rows and ratio on beta[b] * E
-            if (which == KP_PROPOSE) {
-                if (a.rng_mode == 0) { if (lib) go(k_propose_temp<GP, true, true>); else go(k_propose_temp<GP, true, false>); }
-                else { if (lib) go(k_propose_temp<GP, false, true>); else go(k_propose_temp<GP, false, false>); }
-            } else if (a.rng_mode == 1) { if (lib) go(k_accept_temp<GP, true, true>); else go(k_accept_temp<GP, true, false>); }
-            else { if (lib) go(k_accept_temp<GP, false, true>); else go(k_accept_temp<GP, false, false>); }
-            return;
-        }
-        if (rev) {                                   // general instantiations only; the forward path keeps its kernels
-            if (which == KP_ACCEPT_PROPOSE) { if (lib) go(k_accept_propose_rev<GP, true>); else go(k_accept_propose_rev<GP, false>); }
-            else if (a.rng_mode == 1) { if (lib) go(k_accept_rev<GP, true, true>); else go(k_accept_rev<GP, true, false>); }
-            else { if (lib) go(k_accept_rev<GP, false, true>); else go(k_accept_rev<GP, false, false>); }
-            return;
-        }
-        if (lib) {
-            if (which == KP_ACCEPT_PROPOSE) go(k_accept_propose_lib<GP>);
-            else if (a.rng_mode == 0) go(k_propose_lib<GP, true>);
-            else go(k_propose_lib<GP, false>);
-            return;
-        }
-        if (which == KP_PROPOSE && a.rng_mode == 0) {
-            go(k_propose<GP, true, 0>);
-            return;
-        }
-        with_spec([&](auto S) {
-            constexpr int SP = decltype(S)::value;
-            constexpr bool policy = (SP & (PAS_SPEC_REEVAL | PAS_SPEC_REUSE)) != 0;
-            if (which == KP_ACCEPT_PROPOSE) {
-                if constexpr (!policy) go(k_accept_propose<GP, SP>);
-            } else if constexpr (policy || SP == 0) {
-                if (which == KP_PROPOSE) go(k_propose<GP, false, SP>);
-                else if (SP != 0 || a.rng_mode == 1) go(k_accept<GP, SP, true>);
-                else go(k_accept<GP, 0, false>);   // replay: the reference's bits
-            }
-        });
-    });
-    HIPCHK(hipGetLastError());
-    return PPDE_OK;
-}
-
-// `count` iterations of ppde.py:65-153 for sub-population k, enqueued on that sub-population's stream.
-// Re-evaluating mode: EG(x) P EG(y) A per iteration. Reuse mode: P, then EG(y) + fused [accept | next propose].
-// Tempering: [EG(x)] P EG(y) A S, never fused: the next proposal must see the post-swap beta, the swap the post-accept energy.
-// Annealing: the same flow with the two selection kernels in the swap's place.
-// Recombination: on the host-chosen event iterations the event's three launches follow a plain accept kernel, and the next iteration
-// starts with a plain propose launch (nothing fuses across an event); everywhere else the flow is that of the run without the mode.
-static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int first_local, int count, const int* U,
-                              const float* q, const float* u, int mu_cap = 0) {
-    const ppde_model* m = c->m;
-    hipStream_t s = c->streams[k];
-    const int b_off = c->sub_off[k], n_sub = c->sub_n[k];
-    PasArgs a = chain_args(c);
-    a.b_off = b_off; a.it_base = it_base; a.U_in = U; a.q_in = q; a.u_in = u;
-    if (mu_cap > 0) a.mu_cap = mu_cap;              // caller-supplied noise holds only max_u[i] sub-steps of variates
-    const bool fuse = c->cfg.reuse_grad && c->cfg.rng_mode == 1 && !c->temper.on() && !c->anneal.on();
-    int rc;
-    bool after_event = false;                       // the previous iteration of this call ended with a recombination event
-    for (int i = 0; i < count; ++i) {
-        a.it_local = first_local + i;
-        const bool event = c->recomb.on() && c->recomb.event(a.it_local);
-        if (!c->cfg.reuse_grad) {   // energy and gradient at the current state (ppde.py:79)
-            rc = eval_experts(m, c->cfg.which, cur_states(c), c->n, chain_targets(c, 0), 1, s, b_off, n_sub);
-            if (rc) return rc;
-        }
-        if (!fuse || i == 0 || after_event) {
-            rc = launch_chain_kernel(c, KP_PROPOSE, a, n_sub, s);
-            if (rc) return rc;
-        }
-        // energy and gradient at the proposal (ppde.py:119)
-        rc = eval_experts(m, c->cfg.which, prop_states(c), c->n, chain_targets(c, 1), 1, s, b_off, n_sub);
-        if (rc) return rc;
-        rc = launch_chain_kernel(c, (fuse && i + 1 < count && !event) ? KP_ACCEPT_PROPOSE : KP_ACCEPT, a, n_sub, s);
-        if (rc) return rc;
-        after_event = event;
-        // what follows runs on the object's one stream and covers every chain of it: the swap or the selection, then the observers,
-        // which see the population those left
-        if (c->temper.on()) {
-            hipLaunchKernelGGL(k_swap, dim3((c->n + 255) / 256), dim3(256), 0, s, a);
-            HIPCHK(hipGetLastError());
-        }
-        if (c->anneal.on() && (rc = launch_select(c, it_base, a.it_local, s))) return rc;
-        if (event && (rc = launch_cross(c, it_base, a.it_local, s))) return rc;
-        if (c->recorder.on() && (rc = launch_record(c, it_base, a.it_local, s))) return rc;
-        if (c->pairs.on() && (rc = launch_pairs(c, it_base, a.it_local, s))) return rc;      // (set only next to a recorder)
-        if (c->archive.on() && (rc = launch_archive(c, it_base, a.it_local, s))) return rc;
-        if (c->stats.on() && (rc = launch_stats(c, it_base, a.it_local, U, mu_cap, s))) return rc;
-    }
-    return PPDE_OK;
-}
-
-// `count` iterations starting at (it_base, first_local) for every sub-population: fork from stream 0, run the
-// sub-populations' iteration chains side by side, join back on stream 0.
-static int enqueue_block(ppde_chains* c, const int* it_base, int first_local, int count) {
-    const int K = (int)c->streams.size();
-    if (K > 1) {
-        HIPCHK(hipEventRecord(c->events[0], c->streams[0]));
-        for (int k = 1; k < K; ++k) HIPCHK(hipStreamWaitEvent(c->streams[k], c->events[0], 0));
-    }
-    for (int k = 0; k < K; ++k) {
-        int rc = enqueue_iterations(c, k, it_base, first_local, count, nullptr, nullptr, nullptr);
-        if (rc) return rc;
-    }
-    for (int k = 1; k < K; ++k) {
-        HIPCHK(hipEventRecord(c->events[k], c->streams[k]));
-        HIPCHK(hipStreamWaitEvent(c->streams[0], c->events[k], 0));
-    }
-    return PPDE_OK;
-}
-
-// Capture `len` iterations (iteration index = device counter + node-local offset) into a graph segment.
-static int capture_segment(ppde_chains* c, int len, bool inside_run) {
-    ppde_chains::GraphSeg gs;
-    HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-    int rc = enqueue_block(c, c->d_it, 0, len);
-    if (rc == PPDE_OK) hipLaunchKernelGGL(k_bump, dim3(1), dim3(1), 0, c->stream, c->d_it, len);
-    hipError_t e = hipStreamEndCapture(c->stream, &gs.graph);
-    if (rc == PPDE_OK && e == hipSuccess) e = hipGraphInstantiate(&gs.exec, gs.graph, nullptr, nullptr, 0);
-    if (rc != PPDE_OK || e != hipSuccess) {
-        if (gs.exec) hipGraphExecDestroy(gs.exec);
-        if (gs.graph) hipGraphDestroy(gs.graph);
-        if (rc) return rc;
-        return fail(PPDE_ERR_HIP, std::string("hipGraph capture: ") + hipGetErrorString(e));
-    }
-    hipGraphUpload(gs.exec, c->stream);              // (best effort: the first replay then finds the graph on the device)
-    gs.len = len;
-    c->graphs.push_back(gs);
-    c->n_captures++;
-    if (inside_run) c->n_captures_in_run++;
-    return PPDE_OK;
-}
-
-// Graph segments of a chains object: PPDE_GRAPH_LEN (one length) or {100, 20}, each only if the histories can hold
-// it. Captured and instantiated here, from ppde_chains_init, so that no ppde_chains_run pays for it.
-static int capture_segments(ppde_chains* c) {
-    if (!c->cfg.use_graph || c->cfg.rng_mode != 1 || !c->graphs.empty()) return PPDE_OK;
-    if (c->cfg.which & 4) return PPDE_OK;           // ~900 launches per iteration, tens of milliseconds each way: nothing to gain from replay
-    static const int gl_read = env_int("PPDE_GRAPH_LEN", 0), gl_env = gl_read >= 1 && gl_read <= 1000 ? gl_read : 0;
-    if (c->recomb.on()) {
-        // a segment holds its events at fixed places: its length is a multiple of `every`, and it is replayed from such positions only
-        const int every = c->recomb.every;
-        std::vector<int> lens;
-        if (gl_env) { if (gl_env % every == 0) lens.push_back(gl_env); }
-        else if (every <= 100) { lens.push_back(every * (100 / every)); if (lens[0] != every) lens.push_back(every); }
-        else if (every <= 1000) lens.push_back(every);
-        for (int len : lens) {
-            if (len > c->T) continue;
-            int rc = capture_segment(c, len, false);
-            if (rc) return rc;
-        }
-        return PPDE_OK;
-    }
-    const int lens_default[2] = {100, 20};
-    for (int k = 0; k < (gl_env ? 1 : 2); ++k) {
-        const int len = gl_env ? gl_env : lens_default[k];
-        if (len > c->T) continue;
-        int rc = capture_segment(c, len, false);
-        if (rc) return rc;
-    }
-    return PPDE_OK;
-}
-
-extern "C" {
-
-int ppde_chains_create(ppde_chains** out, ppde_model* m, const ppde_chain_config* cfg) {
-    ARGCHK(out && m && cfg, "null argument");
-    ARGCHK(cfg->n_chains >= 1, "need at least one chain");
-    ARGCHK(cfg->max_steps >= 0, "negative max_steps");
-    ARGCHK(cfg->pas_length >= 1 && cfg->pas_length <= 64, "ppde_pas_length out of range");
-    ARGCHK(cfg->nmut_threshold >= 0, "negative nmut_threshold");
-    ARGCHK(cfg->which >= 1 && cfg->which <= 15 && (cfg->which & 7), "which: bit 0 Potts, bit 1 supervised, bit 2 transformer expert, bit 3 full gradient");
-    ARGCHK(!(cfg->which & 4) || m->tf, "transformer expert not set");
-    ARGCHK(!(cfg->which & 4) || cfg->n_streams <= 1, "the transformer expert runs on one stream");
-    ARGCHK(cfg->min_pos >= 0 && cfg->max_pos < m->L && cfg->min_pos <= cfg->max_pos, "bad [min_pos, max_pos]");
-    ARGCHK(cfg->rng_mode == 0 || cfg->rng_mode == 1, "rng_mode must be 0 or 1");
-    ARGCHK(cfg->random_chain < cfg->n_chains, "random_chain out of range");
-    ARGCHK(!(cfg->which & 1) || m->has_potts, "Potts expert not set");
-    ARGCHK(!(cfg->which & 2) || m->has_cnn, "supervised expert not set");
-    ARGCHK(cfg->chain_offset + (uint64_t)cfg->n_chains <= 0xffffffffull, "chain_offset + n_chains must fit 32 bits");
-    ARGCHK(pas_lds_bytes(m->g) <= 160 * 1024 && m->g.N / 4 <= 3 * PPDE_BLOCK, "sequence too long for the chain kernels (L <= 307)");
-    ARGCHK((m->L + 63) / 64 <= PPDE_NW, "more race waves than waves in a chain workgroup");    // (pas.h propose_body_dev: one residue per lane)
-    HIPCHK(hipSetDevice(m->device));
-    ppde_chains* c = new ppde_chains();
-    c->m = m; c->device = m->device; c->cfg = *cfg; c->n = cfg->n_chains; c->T = cfg->max_steps; c->mu_max = 2 * cfg->pas_length - 1;
-    const Geom& g = m->g;
-    const size_t n = c->n, T1 = (size_t)c->T + 1;
-    const int nets = cnn_parts(m);
-    bool ok = true;
-    auto A = [&](auto** p, size_t count, bool zero) {
-        if (!ok) return;
-        if (dalloc(p, count) != hipSuccess) { ok = false; return; }
-        c->allocs.push_back((void*)*p);
-        if (zero && hipMemset((void*)*p, 0, std::max<size_t>(count, 1) * sizeof(**p)) != hipSuccess) ok = false;
-    };
-    A(&c->cur, n * g.Ls, true); A(&c->prop, n * g.Ls, true);
-    c->n_pad = potts_t4_pad(c->n);
-    A(&c->curT, g.Lp > 0 ? potts_t4_words(g.NC, c->n_pad) : 1, true); A(&c->propT, g.Lp > 0 ? potts_t4_words(g.NC, c->n_pad) : 1, true);
-    A(&c->fb_state, (cfg->paper_results ? n : 1) * g.Ls, true);
-    c->rec_stride = chain_rec_stride(c->mu_max);
-    A(&c->rec, n * c->rec_stride, true);
-    A(&c->grad_cur, cfg->reuse_grad ? n * g.N : 1, true); A(&c->best_state, n * g.L, true); A(&c->rtraj, T1 * g.L, true); A(&c->tmp_acc, n, true);
-    A(&c->tmp_idx, n * g.L, true); A(&c->tmp_dist, n, true);
-    A(&c->grad, 2 * n * g.N, true); A(&c->epart, 2 * n * std::max(g.Lp, 1), true);
-    if (cfg->which & 2) {
-        A(&c->gradC, 2 * nets * n * g.N, true); A(&c->fitC, 2 * nets * n, true);
-        if (!cnn_single_launch(m)) {
-            A(&c->cnn_cmax, cnn_chunk_max_count(m, c->n), true); A(&c->cnn_carg, cnn_chunk_max_count(m, c->n), true);
-            A(&c->cnn_cgate, cnn_chunk_gate_count(m, c->n), true);
-        }
-    }
-    if (cfg->which & 4) {
-        A(&c->gradT, 2 * n * g.N, true); A(&c->tfE, 2 * n, true);
-        if (ok) {
-            c->tfw = new TfWork();
-            if (tf_alloc_work(m->tf, c->tfw, c->n) != PPDE_OK) ok = false;
-        }
-    }
-    A(&c->fb_grad, (cfg->paper_results ? n : 1) * g.N, true);
-    A(&c->fb_e, cfg->paper_results ? n : 1, true); A(&c->fb_f, cfg->paper_results ? n : 1, true);
-    A(&c->e_hist, T1 * n, true); A(&c->f_hist, T1 * n, true);
-    A(&c->tmp_be, n, true); A(&c->tmp_bf, n, true); A(&c->tmp_bt, n, true);
-    A(&c->d_it, 1, true); A(&c->dbg, PPDE_DBG_WORDS, true);
-    // error word in pinned host memory mapped into the device: kernels set it with system-scope atomics (error paths
-    // only), ppde_chains_sync reads it after the stream has drained, without a device-to-host copy
-    if (ok && (hipHostMalloc((void**)&c->h_err, sizeof(int), hipHostMallocMapped) != hipSuccess ||
-               hipHostGetDevicePointer((void**)&c->err_flag, c->h_err, 0) != hipSuccess)) ok = false;
-    if (ok) *c->h_err = 0;
-    if (cfg->trace) {
-        A(&c->tr_flat, (size_t)c->T * c->mu_max * n, true); A(&c->tr_acc, (size_t)c->T * n, true);
-        A(&c->tr_logacc, (size_t)c->T * n, true); A(&c->tr_U, (size_t)c->T * n, true);
-    }
-    int K = (cfg->rng_mode == 1 && cfg->n_streams > 1) ? std::min(cfg->n_streams, std::min(8, c->n)) : 1;
-    c->streams.assign(K, nullptr);
-    c->events.assign(K, nullptr);
-    for (int k = 0; k < K && ok; ++k) {
-        ok = hipStreamCreateWithFlags(&c->streams[k], hipStreamNonBlocking) == hipSuccess &&
-             hipEventCreateWithFlags(&c->events[k], hipEventDisableTiming) == hipSuccess;
-        const int base = c->n / K, extra = c->n % K;
-        c->sub_off.push_back(k * base + std::min(k, extra));
-        c->sub_n.push_back(base + (k < extra ? 1 : 0));
-    }
-    if (!ok) {
-        delete c;
-        return fail(PPDE_ERR_HIP, "device allocation failed while creating chains");
-    }
-    c->stream = c->streams[0];
-    *out = c;
-    return PPDE_OK;
-}
-
-int ppde_chains_destroy(ppde_chains* c) {
-    if (!c) return PPDE_OK;
-    hipSetDevice(c->device);
-    for (hipStream_t st : c->streams) if (st) hipStreamSynchronize(st);
-    delete c;
-    return PPDE_OK;
-}
-
-int ppde_chains_set_library(ppde_chains* c, const uint32_t* allowed_host) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_library: the library must be set before ppde_chains_init (its graphs hold the pointer)");
-    ARGCHK(!c->recomb.on(), "ppde_chains_set_library: recombination is set and holds the open list of the library there was; clear it first "
-                            "(ppde_chains_set_recombination(c, NULL))");
-    const ppde_model* m = c->m;
-    HIPCHK(hipSetDevice(c->device));
-    if (!allowed_host) {                            // clear
-        c->allowed = {};
-        return PPDE_OK;
-    }
-    int open_in_range = 0;
-    for (int l = 0; l < m->L; ++l) {
-        const uint32_t w = allowed_host[l];
-        if (w >> PPDE_A)
-            return fail(PPDE_ERR_INVALID, "design library: residue " + std::to_string(l) + " has a bit >= 20 set (20 letters)");
-        if (w && !((w >> m->h_wt[l]) & 1u))          // (the mutation cap's only move is the revert to the wild type)
-            return fail(PPDE_ERR_INVALID, "design library: open residue " + std::to_string(l) + " lacks its wild-type letter");
-        if (w && l >= c->cfg.min_pos && l <= c->cfg.max_pos) open_in_range++;
-    }
-    if (!open_in_range)
-        return fail(PPDE_ERR_INVALID, "design library: no open residue in [min_pos, max_pos] = [" + std::to_string(c->cfg.min_pos) +
-                                      ", " + std::to_string(c->cfg.max_pos) + "]");
-    DevBuf<uint32_t> d;
-    HIPCHK(d.alloc((size_t)m->L));
-    hipError_t e = hipMemcpy(d, allowed_host, (size_t)m->L * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("design library upload: ") + hipGetErrorString(e));
-    c->allowed = std::move(d);
-    return PPDE_OK;
-}
-
-int ppde_chains_set_reversible(ppde_chains* c, int on) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_reversible: the mode must be set before ppde_chains_init (its graphs hold the kernel choice)");
-    ARGCHK(!(on && c->cfg.paper_results), "ppde_chains_set_reversible: paper_results restarts a rejected chain from its initial state, "
-                                          "which is no Metropolis step; the two cannot be combined");
-    ARGCHK(on || !c->temper.on(), "ppde_chains_set_reversible: tempering is set and needs reversible mode (clear it with "
-                                  "ppde_chains_set_tempering(c, 0, NULL, 0) first)");
-    ARGCHK(on || !c->anneal.on(), "ppde_chains_set_reversible: annealing is set and needs reversible mode (clear it with "
-                                  "ppde_chains_set_annealing(c, NULL) first)");
-    ARGCHK(on || !c->recomb.on(), "ppde_chains_set_reversible: recombination is set and needs reversible mode (clear it with "
-                                  "ppde_chains_set_recombination(c, NULL) first)");
-    c->reversible = on != 0;
-    return PPDE_OK;
-}
-
-int ppde_chains_set_tempering(ppde_chains* c, int n_rungs, const float* beta_host, int swap_every) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_tempering: the ladder must be set before ppde_chains_init (its graphs hold the kernel choice)");
-    ARGCHK(!(c->recorder.on() && c->recorder.cfg.rung >= 0), "ppde_chains_set_tempering: a recorder that follows a rung is set; clear it first "
-                                                             "(ppde_chains_set_recorder(c, NULL))");
-    ARGCHK(!c->stats.on(), "ppde_chains_set_tempering: move statistics are set and were shaped by the ladder there was; clear them first "
-                           "(ppde_chains_set_stats(c, NULL))");
-    ARGCHK(!c->anneal.on(), "ppde_chains_set_tempering: annealing is set (a schedule and a ladder cannot be combined); clear it first "
-                            "(ppde_chains_set_annealing(c, NULL))");
-    ARGCHK(!c->recomb.on(), "ppde_chains_set_tempering: recombination is set (its decision takes no beta per chain); clear it first "
-                            "(ppde_chains_set_recombination(c, NULL))");
-    HIPCHK(hipSetDevice(c->device));
-    if (n_rungs == 0 || !beta_host) {               // clear
-        c->temper = {};
-        return PPDE_OK;
-    }
-    const int R = n_rungs;
-    ARGCHK(c->reversible, "ppde_chains_set_tempering: tempering needs reversible mode (ppde_chains_set_reversible): only there is the "
-                          "law at beta, exp(beta E)/Z, defined");
-    ARGCHK(R >= 1 && R <= 64, "ppde_chains_set_tempering: n_rungs must be in 1..64");
-    for (int r = 0; r < R; ++r) {
-        const float b = beta_host[r];
-        if (!(b > 0.f) || !(b < INFINITY))
-            return fail(PPDE_ERR_INVALID, "ppde_chains_set_tempering: beta[" + std::to_string(r) + "] must be finite and positive");
-        if (r > 0 && !(b < beta_host[r - 1]))
-            return fail(PPDE_ERR_INVALID, "ppde_chains_set_tempering: the ladder must be strictly decreasing (beta[" + std::to_string(r) +
-                                          "] >= beta[" + std::to_string(r - 1) + "])");
-    }
-    ARGCHK(swap_every >= 0, "ppde_chains_set_tempering: negative swap_every");
-    ARGCHK(c->n % R == 0, "ppde_chains_set_tempering: n_chains must be a multiple of n_rungs (ensembles of n_rungs consecutive chains)");
-    ARGCHK(c->cfg.chain_offset % (uint64_t)R == 0, "ppde_chains_set_tempering: chain_offset must be a multiple of n_rungs (an ensemble "
-                                                   "may not straddle two shards)");
-    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_tempering: n_streams > 1 is not supported (the swap couples "
-                                                            "the chains of an ensemble)");
-    // allocate everything first: a failure leaves the object as it was
-    const size_t n = c->n, pairs = (n / R) * (size_t)(R - 1);
-    Tempering t;
-    t.n_rungs = R; t.swap_every = swap_every;
-    t.ladder.assign(beta_host, beta_host + R);
-    hipError_t e = t.beta.alloc(n);
-    if (e == hipSuccess) e = t.rung.alloc(n);
-    if (e == hipSuccess) e = t.slot.alloc(n);
-    if (e == hipSuccess) e = t.swap_attempts.alloc(pairs);
-    if (e == hipSuccess) e = t.swap_accepts.alloc(pairs);
-    if (e == hipSuccess) e = t.rung_hist.alloc(((size_t)c->T + 1) * n);
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_tempering: device allocation: ") + hipGetErrorString(e));
-    c->temper = std::move(t);
-    return PPDE_OK;
-}
-
-int ppde_chains_set_annealing(ppde_chains* c, const ppde_anneal_config* cfg) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_annealing: the schedule must be set before ppde_chains_init (its graphs hold the kernel choice)");
-    ARGCHK(!c->recomb.on(), "ppde_chains_set_annealing: recombination is set (its decision takes no beta per chain); clear it first "
-                            "(ppde_chains_set_recombination(c, NULL))");
-    if (!cfg) {                                     // clear
-        HIPCHK(hipSetDevice(c->device));
-        c->anneal = {};
-        return PPDE_OK;
-    }
-    ARGCHK(c->reversible, "ppde_chains_set_annealing: annealing needs reversible mode (ppde_chains_set_reversible): only there is the "
-                          "law at beta, exp(beta E)/Z, defined");
-    ARGCHK(!c->temper.on(), "ppde_chains_set_annealing: tempering is set (a schedule and a ladder cannot be combined); clear it first "
-                            "(ppde_chains_set_tempering(c, 0, NULL, 0))");
-    ARGCHK(cfg->deme >= 2 && cfg->deme <= ANNEAL_DMAX, "ppde_chains_set_annealing: deme must be in 2..1024");
-    ARGCHK(c->n % cfg->deme == 0, "ppde_chains_set_annealing: n_chains must be a multiple of deme (demes of consecutive chains)");
-    ARGCHK(c->cfg.chain_offset % (uint64_t)cfg->deme == 0, "ppde_chains_set_annealing: chain_offset must be a multiple of deme (a deme "
-                                                           "may not straddle two shards)");
-    ARGCHK(cfg->every >= 1, "ppde_chains_set_annealing: every must be >= 1");
-    ARGCHK(cfg->n_stages >= 1 && cfg->n_stages <= 4096, "ppde_chains_set_annealing: n_stages must be in 1..4096");
-    ARGCHK(cfg->beta, "ppde_chains_set_annealing: no schedule (beta is NULL)");
-    const int S = cfg->n_stages, cap = std::min(S, c->T / cfg->every);
-    ARGCHK(cap >= 1, "ppde_chains_set_annealing: no event would fit (events_cap = min(n_stages, max_steps / every) is 0)");
-    for (int s = 0; s <= S; ++s) {
-        const float b = cfg->beta[s];
-        if (!(b > 0.f) || !(b < INFINITY))
-            return fail(PPDE_ERR_INVALID, "ppde_chains_set_annealing: beta[" + std::to_string(s) + "] must be finite and positive");
-        if (s > 0 && b < cfg->beta[s - 1])
-            return fail(PPDE_ERR_INVALID, "ppde_chains_set_annealing: the schedule must not decrease (beta[" + std::to_string(s) +
-                                          "] < beta[" + std::to_string(s - 1) + "])");
-    }
-    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_annealing: n_streams > 1 is not supported (the selection "
-                                                            "couples the chains of a deme)");
-    HIPCHK(hipSetDevice(c->device));
-    // allocate everything first: a failure leaves the object as it was
-    const size_t n = c->n, demes = n / cfg->deme;
-    Annealing t;
-    t.D = cfg->deme; t.every = cfg->every; t.S = S; t.cap = cap;
-    t.sched.assign(cfg->beta, cfg->beta + S + 1);
-    hipError_t e = t.sched_dev.alloc((size_t)S + 1);
-    if (e == hipSuccess) e = hipMemcpy(t.sched_dev, cfg->beta, ((size_t)S + 1) * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = t.beta.alloc(n);
-    if (e == hipSuccess) e = t.pre.alloc((size_t)cap * n);
-    if (e == hipSuccess) e = t.parent.alloc((size_t)cap * n);
-    if (e == hipSuccess) e = t.lmw.alloc((size_t)cap * demes);
-    if (e == hipSuccess) e = t.ess.alloc((size_t)cap * demes);
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_annealing: device allocation: ") + hipGetErrorString(e));
-    c->anneal = std::move(t);
-    return PPDE_OK;
-}
-
-int ppde_chains_set_annealing_adaptive(ppde_chains* c, const ppde_anneal_adaptive_config* cfg) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_annealing_adaptive: the mode must be set before ppde_chains_init (its graphs hold the kernel choice)");
-    ARGCHK(!c->recomb.on(), "ppde_chains_set_annealing_adaptive: recombination is set (its decision takes no beta per chain); clear it first "
-                            "(ppde_chains_set_recombination(c, NULL))");
-    if (!cfg) {                                     // clear
-        HIPCHK(hipSetDevice(c->device));
-        c->anneal = {};
-        return PPDE_OK;
-    }
-    ARGCHK(c->reversible, "ppde_chains_set_annealing_adaptive: annealing needs reversible mode (ppde_chains_set_reversible): only there is "
-                          "the law at beta, exp(beta E)/Z, defined");
-    ARGCHK(!c->temper.on(), "ppde_chains_set_annealing_adaptive: tempering is set (a schedule and a ladder cannot be combined); clear it "
-                            "first (ppde_chains_set_tempering(c, 0, NULL, 0))");
-    ARGCHK(cfg->deme >= 2 && cfg->deme <= ANNEAL_DMAX, "ppde_chains_set_annealing_adaptive: deme must be in 2..1024");
-    ARGCHK(c->n % cfg->deme == 0, "ppde_chains_set_annealing_adaptive: n_chains must be a multiple of deme (demes of consecutive chains)");
-    ARGCHK(c->cfg.chain_offset % (uint64_t)cfg->deme == 0, "ppde_chains_set_annealing_adaptive: chain_offset must be a multiple of deme (a "
-                                                           "deme may not straddle two shards)");
-    ARGCHK(cfg->every >= 1, "ppde_chains_set_annealing_adaptive: every must be >= 1");
-    ARGCHK(cfg->max_stages >= 1 && cfg->max_stages <= 4096, "ppde_chains_set_annealing_adaptive: max_stages must be in 1..4096");
-    const int cap = std::min(cfg->max_stages, c->T / cfg->every);
-    ARGCHK(cap >= 1, "ppde_chains_set_annealing_adaptive: no event would fit (events_cap = min(max_stages, max_steps / every) is 0)");
-    ARGCHK(cfg->beta_start > 0.f && cfg->beta_start < INFINITY, "ppde_chains_set_annealing_adaptive: beta_start must be finite and positive");
-    ARGCHK(cfg->beta_end > 0.f && cfg->beta_end < INFINITY, "ppde_chains_set_annealing_adaptive: beta_end must be finite and positive");
-    ARGCHK(cfg->beta_start < cfg->beta_end, "ppde_chains_set_annealing_adaptive: beta_start must be below beta_end");
-    ARGCHK(cfg->ess_target > 0.f && cfg->ess_target < 1.f, "ppde_chains_set_annealing_adaptive: ess_target must be inside (0, 1)");
-    ARGCHK(cfg->min_step < INFINITY && cfg->min_step >= cfg->beta_end * 0x1p-20f,
-           "ppde_chains_set_annealing_adaptive: min_step must be finite and >= beta_end * 2^-20 (a step that changes beta in fp32)");
-    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_annealing_adaptive: n_streams > 1 is not supported (the "
-                                                            "selection couples the chains of a deme)");
-    HIPCHK(hipSetDevice(c->device));
-    // allocate everything first: a failure leaves the object as it was
-    const size_t n = c->n, demes = n / cfg->deme;
-    Annealing t;
-    t.D = cfg->deme; t.every = cfg->every; t.S = cfg->max_stages; t.cap = cap;
-    t.adaptive = true; t.rho = cfg->ess_target; t.min_step = cfg->min_step;
-    t.sched = {cfg->beta_start, cfg->beta_end};
-    hipError_t e = t.sched_dev.alloc(2);
-    if (e == hipSuccess) e = hipMemcpy(t.sched_dev, t.sched.data(), 2 * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = t.beta.alloc(n);
-    if (e == hipSuccess) e = t.pre.alloc((size_t)cap * n);
-    if (e == hipSuccess) e = t.parent.alloc((size_t)cap * n);
-    if (e == hipSuccess) e = t.lmw.alloc((size_t)cap * demes);
-    if (e == hipSuccess) e = t.ess.alloc((size_t)cap * demes);
-    if (e == hipSuccess) e = t.beta_pair.alloc(2 * (size_t)cap * demes);
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_annealing_adaptive: device allocation: ") + hipGetErrorString(e));
-    c->anneal = std::move(t);
-    return PPDE_OK;
-}
-
-int ppde_chains_annealing_shape(ppde_chains* c, int32_t* deme, int32_t* events_cap, int32_t* events_done) {
-    ARGCHK(c, "null argument");
-    ARGCHK(c->anneal.on(), "ppde_chains_annealing_shape: no annealing was set (ppde_chains_set_annealing)");
-    if (deme) *deme = c->anneal.D;
-    if (events_cap) *events_cap = c->anneal.cap;
-    if (events_done) *events_done = c->anneal.events_done(c->steps_done);
-    return PPDE_OK;
-}
-
-int ppde_chains_annealing_read(ppde_chains* c, int first_event, int n_events, int32_t* parent, float* pre_energy, double* log_mean_w,
-                               double* ess, float* beta_now) {
-    ARGCHK(c && c->anneal.on(), "ppde_chains_annealing_read: no annealing was set (ppde_chains_set_annealing)");
-    ARGCHK(c->initialised, "chains not initialised");
-    ARGCHK(first_event >= 0 && n_events >= 0 && first_event + n_events <= c->anneal.events_done(c->steps_done),
-           "ppde_chains_annealing_read: events beyond those that have happened (ppde_chains_annealing_shape)");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    const size_t n = c->n, demes = n / c->anneal.D, f = (size_t)first_event, k = (size_t)n_events;
-    if (parent && k) HIPCHK(hipMemcpy(parent, c->anneal.parent + f * n, k * n * sizeof(int), hipMemcpyDeviceToHost));
-    if (pre_energy && k) HIPCHK(hipMemcpy(pre_energy, c->anneal.pre + f * n, k * n * sizeof(float), hipMemcpyDeviceToHost));
-    if (log_mean_w && k) HIPCHK(hipMemcpy(log_mean_w, c->anneal.lmw + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
-    if (ess && k) HIPCHK(hipMemcpy(ess, c->anneal.ess + f * demes, k * demes * sizeof(double), hipMemcpyDeviceToHost));
-    if (beta_now) HIPCHK(hipMemcpy(beta_now, c->anneal.beta, n * sizeof(float), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-
-int ppde_chains_annealing_read_betas(ppde_chains* c, int first_event, int n_events, float* beta_before, float* beta_after) {
-    ARGCHK(c && c->anneal.on(), "ppde_chains_annealing_read_betas: no annealing was set (ppde_chains_set_annealing)");
-    ARGCHK(c->initialised, "chains not initialised");
-    ARGCHK(first_event >= 0 && n_events >= 0 && first_event + n_events <= c->anneal.events_done(c->steps_done),
-           "ppde_chains_annealing_read_betas: events beyond those that have happened (ppde_chains_annealing_shape)");
-    const Annealing& an = c->anneal;
-    const size_t demes = (size_t)c->n / an.D, f = (size_t)first_event, k = (size_t)n_events;
-    if (!an.adaptive) {                             // a fixed schedule: every deme walks it
-        for (size_t ev = 0; ev < k; ++ev)
-            for (size_t d = 0; d < demes; ++d) {
-                if (beta_before) beta_before[ev * demes + d] = an.sched[f + ev];
-                if (beta_after) beta_after[ev * demes + d] = an.sched[f + ev + 1];
-            }
-        return PPDE_OK;
-    }
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    if (beta_before && k) HIPCHK(hipMemcpy(beta_before, an.beta_pair + f * demes, k * demes * sizeof(float), hipMemcpyDeviceToHost));
-    if (beta_after && k)
-        HIPCHK(hipMemcpy(beta_after, an.beta_pair + ((size_t)an.cap + f) * demes, k * demes * sizeof(float), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-
-int ppde_chains_set_recombination(ppde_chains* c, const ppde_recombine_config* cfg) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_recombination: the mode must be set before ppde_chains_init (its graphs hold the events)");
-    if (!cfg) {                                     // clear
-        HIPCHK(hipSetDevice(c->device));
-        c->recomb = {};
-        return PPDE_OK;
-    }
-    ARGCHK(c->reversible, "ppde_chains_set_recombination: recombination needs reversible mode (ppde_chains_set_reversible): only there "
-                          "do the chains have the law exp(E)/Z whose product the exchange keeps");
-    ARGCHK(!c->temper.on(), "ppde_chains_set_recombination: tempering is set (the decision takes no beta per chain); clear it first "
-                            "(ppde_chains_set_tempering(c, 0, NULL, 0))");
-    ARGCHK(!c->anneal.on(), "ppde_chains_set_recombination: annealing is set (the decision takes no beta per chain); clear it first "
-                            "(ppde_chains_set_annealing(c, NULL))");
-    ARGCHK(!c->cfg.paper_results, "ppde_chains_set_recombination: paper_results is not supported");
-    ARGCHK(cfg->deme >= 2 && cfg->deme % 2 == 0, "ppde_chains_set_recombination: deme must be even and >= 2 (the chains of a deme are paired)");
-    ARGCHK(c->n % cfg->deme == 0, "ppde_chains_set_recombination: n_chains must be a multiple of deme (demes of consecutive chains)");
-    ARGCHK(c->cfg.chain_offset % (uint64_t)cfg->deme == 0, "ppde_chains_set_recombination: chain_offset must be a multiple of deme (a deme "
-                                                           "may not straddle two shards)");
-    ARGCHK(cfg->every >= 1, "ppde_chains_set_recombination: every must be >= 1");
-    const int cap = c->T / cfg->every;
-    ARGCHK(cap >= 1, "ppde_chains_set_recombination: no event would fit (events_cap = max_steps / every is 0)");
-    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_recombination: n_streams > 1 is not supported (the exchange "
-                                                            "couples the chains of a deme)");
-    HIPCHK(hipSetDevice(c->device));
-    // allocate everything first: a failure leaves the object as it was
-    const int L = c->m->L;
-    std::vector<uint32_t> words;
-    if (c->allowed) {
-        words.resize((size_t)L);
-        HIPCHK(hipMemcpy(words.data(), c->allowed, (size_t)L * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    }
-    Recombination t;
-    t.D = cfg->deme; t.every = cfg->every; t.cap = cap;
-    for (int l = c->cfg.min_pos; l <= c->cfg.max_pos; ++l)
-        if (words.empty() || words[(size_t)l]) t.open.push_back(l);
-    ARGCHK(!t.open.empty(), "ppde_chains_set_recombination: no open residue in [min_pos, max_pos]");
-    const size_t cells = (size_t)cap * c->n;
-    hipError_t e = t.open_dev.alloc(t.open.size());
-    if (e == hipSuccess) e = hipMemcpy(t.open_dev, t.open.data(), t.open.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = t.partner.alloc(cells);
-    if (e == hipSuccess) e = t.lo.alloc(cells);
-    if (e == hipSuccess) e = t.hi.alloc(cells);
-    if (e == hipSuccess) e = t.differ.alloc(cells);
-    if (e == hipSuccess) e = t.child_dist.alloc(cells);
-    if (e == hipSuccess) e = t.outcome.alloc(cells);
-    if (e == hipSuccess) e = t.log_ratio.alloc(cells);
-    if (e == hipSuccess) e = t.pre.alloc(cells);
-    if (e == hipSuccess) e = t.child.alloc(cells);
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_recombination: device allocation: ") + hipGetErrorString(e));
-    c->recomb = std::move(t);
-    return PPDE_OK;
-}
-
-int ppde_chains_recombination_shape(ppde_chains* c, int32_t* deme, int32_t* n_open, int32_t* open_sites, int32_t* events_cap,
-                                    int32_t* events_done) {
-    ARGCHK(c, "null argument");
-    ARGCHK(c->recomb.on(), "ppde_chains_recombination_shape: no recombination was set (ppde_chains_set_recombination)");
-    ARGCHK(c->initialised, "chains not initialised");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    if (deme) *deme = c->recomb.D;
-    if (n_open) *n_open = (int32_t)c->recomb.open.size();
-    if (open_sites) std::copy(c->recomb.open.begin(), c->recomb.open.end(), open_sites);
-    if (events_cap) *events_cap = c->recomb.cap;
-    if (events_done) *events_done = c->recomb.events_done(c->steps_done);
-    return PPDE_OK;
-}
-
-int ppde_chains_recombination_read(ppde_chains* c, int first_event, int n_events, int32_t* partner, int32_t* lo, int32_t* hi,
-                                   int32_t* differ, int32_t* child_dist, uint8_t* outcome, float* log_ratio, float* pre_energy,
-                                   float* child_energy) {
-    ARGCHK(c && c->recomb.on(), "ppde_chains_recombination_read: no recombination was set (ppde_chains_set_recombination)");
-    ARGCHK(c->initialised, "chains not initialised");
-    ARGCHK(first_event >= 0 && n_events >= 0 && first_event + n_events <= c->recomb.events_done(c->steps_done),
-           "ppde_chains_recombination_read: events beyond those that have happened (ppde_chains_recombination_shape)");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    const Recombination& r = c->recomb;
-    const size_t o = (size_t)first_event * c->n, k = (size_t)n_events * c->n;
-    if (!k) return PPDE_OK;
-    if (partner) HIPCHK(hipMemcpy(partner, r.partner + o, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (lo) HIPCHK(hipMemcpy(lo, r.lo + o, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (hi) HIPCHK(hipMemcpy(hi, r.hi + o, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (differ) HIPCHK(hipMemcpy(differ, r.differ + o, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (child_dist) HIPCHK(hipMemcpy(child_dist, r.child_dist + o, k * sizeof(int), hipMemcpyDeviceToHost));
-    if (outcome) HIPCHK(hipMemcpy(outcome, r.outcome + o, k, hipMemcpyDeviceToHost));
-    if (log_ratio) HIPCHK(hipMemcpy(log_ratio, r.log_ratio + o, k * sizeof(float), hipMemcpyDeviceToHost));
-    if (pre_energy) HIPCHK(hipMemcpy(pre_energy, r.pre + o, k * sizeof(float), hipMemcpyDeviceToHost));
-    if (child_energy) HIPCHK(hipMemcpy(child_energy, r.child + o, k * sizeof(float), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-
-// rungs, temperatures, slots and counters of a fresh start: chain g = chain_offset + b starts on rung g % R (chain_offset % R == 0)
-static int init_tempering(ppde_chains* c) {
-    const int R = c->temper.n_rungs;
-    const size_t n = c->n, pairs = (n / R) * (size_t)(R - 1);
-    std::vector<float> hb(n);
-    std::vector<int> hr(n), hs(n);
-    std::vector<uint8_t> h8(n);
-    for (size_t b = 0; b < n; ++b) { hr[b] = (int)(b % R); hb[b] = c->temper.ladder[hr[b]]; hs[b] = (int)b; h8[b] = (uint8_t)hr[b]; }
-    HIPCHK(hipMemcpy(c->temper.beta, hb.data(), n * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->temper.rung, hr.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->temper.slot, hs.data(), n * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->temper.rung_hist, h8.data(), n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(c->temper.swap_attempts, 0, std::max<size_t>(pairs, 1) * sizeof(long long)));
-    HIPCHK(hipMemset(c->temper.swap_accepts, 0, std::max<size_t>(pairs, 1) * sizeof(long long)));
-    return PPDE_OK;
-}
-
-int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
-    ARGCHK(c && idx0_dev, "null argument");
-    ppde_model* m = c->m;
-    HIPCHK(hipSetDevice(m->device));
-    const Geom& g = m->g;
-    hipStream_t s = c->stream;
-    const int n = c->n;
-    hipLaunchKernelGGL(k_pack_state, dim3((n * g.Ls + 255) / 256), dim3(256), 0, s, idx0_dev, c->cur, n, g.L, g.Ls, g.sh);
-    HIPCHK(hipGetLastError());
-    int rc = state_rows_to_t4(m, c->cur, c->curT, n, c->n_pad, s);
-    if (rc) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    *c->h_err = 0;
-    HIPCHK(hipMemsetAsync(c->d_it, 0, sizeof(int), s));
-    c->d_it_val = 0;
-    PasArgs a = chain_args(c);
-    if (c->cfg.reuse_grad || c->cfg.paper_results) {
-        // fallback rows: the wild type (mutation-cap reset) or the initial population (paper_results)
-        const int nf = c->cfg.paper_results ? n : 1;
-        const States fstates = c->cfg.paper_results ? cur_states(c) : States{m->d_wt, m->d_wtT, potts_t4_pad(1)};
-        if (c->cfg.paper_results) HIPCHK(hipMemcpyAsync(c->fb_state, c->cur, (size_t)n * g.Ls, hipMemcpyDeviceToDevice, s));
-        else HIPCHK(hipMemcpyAsync(c->fb_state, m->d_wt, (size_t)g.Ls, hipMemcpyDeviceToDevice, s));
-        if (c->cfg.reuse_grad) {
-            // evaluate into slot 0 viewed with n = nf (layout [slot][nf][...] only matters within this call)
-            EvalTargets t = chain_targets(c, 0);
-            rc = eval_experts(m, c->cfg.which, fstates, nf, t, 1, s);
-            if (rc) return rc;
-            PasArgs f = a;
-            f.n = nf;
-            hipLaunchKernelGGL(k_combine_rows, dim3(nf), dim3(256), 0, s, f, c->fb_grad);
-            HIPCHK(hipGetLastError());
-            hipLaunchKernelGGL(k_slot_energy, dim3((nf + 3) / 4), dim3(256), 0, s, f, c->fb_e, c->fb_f);
-            HIPCHK(hipGetLastError());
-        }
-    } else {
-        HIPCHK(hipMemcpyAsync(c->fb_state, m->d_wt, (size_t)g.Ls, hipMemcpyDeviceToDevice, s));
-    }
-    if (c->cfg.reuse_grad && !c->cfg.paper_results) {   // what a mutation-cap reset continues from
-        HIPCHK(hipMemcpyAsync(&c->wt_e, c->fb_e, sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(&c->wt_f, c->fb_f, sizeof(float), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        a.wt_e = c->wt_e; a.wt_f = c->wt_f;
-    }
-    // energies (and, when gradients are reused, the gradient) of the initial population -> slot 0
-    rc = eval_experts(m, c->cfg.which, cur_states(c), n, chain_targets(c, 0), 1, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_init_chain, dim3((n + 3) / 4), dim3(256), 0, s, a);
-    HIPCHK(hipGetLastError());
-    if (c->cfg.reuse_grad) {   // the current state's combined gradient row travels with the chain from here on
-        hipLaunchKernelGGL(k_combine_rows, dim3(n), dim3(256), 0, s, a, c->grad_cur);
-        HIPCHK(hipGetLastError());
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    if (c->temper.on()) {
-        rc = init_tempering(c);
-        if (rc) return rc;
-    }
-    if (c->anneal.on()) {                                 // (a fresh start: every chain at beta[0])
-        const std::vector<float> hb((size_t)n, c->anneal.sched[0]);
-        HIPCHK(hipMemcpy(c->anneal.beta, hb.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (c->recorder.on()) HIPCHK(hipMemset(c->recorder.counts, 0, (size_t)g.L * PPDE_A * sizeof(unsigned long long)));   // (a fresh start counts from zero)
-    if (c->pairs.on()) HIPCHK(hipMemset(c->pairs.counts, 0, c->pairs.tiles() * PAIR_TILE * sizeof(unsigned long long)));
-    if (c->archive.on()) {                              // (a fresh start: an empty archive, then the initial population as t = 0)
-        HIPCHK(hipMemsetAsync(c->archive.count, 0, (size_t)n * sizeof(int), s));
-        rc = launch_archive(c, nullptr, -1, s);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    if (c->stats.on()) {                               // (a fresh start: zero counters, the initial population as the state before iteration 0)
-        HIPCHK(hipMemsetAsync(c->stats.cnt, 0, c->stats.cells_total() * sizeof(long long), s));
-        HIPCHK(hipMemcpyAsync(c->stats.prev, c->cur, (size_t)n * g.Ls, hipMemcpyDeviceToDevice, s));   // (buffer 0: iteration 0 reads it)
-        hipLaunchKernelGGL(k_stats_init, dim3((n + 255) / 256), dim3(256), 0, s, c->rec, c->rec_stride, c->stats.dist, n);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    c->steps_done = 0;
-    c->initialised = true;
-    rc = capture_segments(c);                       // (replayed by every later run; never captured inside one)
-    if (rc) return rc;
-    return PPDE_OK;
-}
-
-int ppde_chains_run(ppde_chains* c, int steps, const int32_t* U_dev, const float* q_dev, const float* u_dev,
-                    const int32_t* max_u) {
-    ARGCHK(c && c->initialised, "chains not initialised");
-    ARGCHK(steps >= 0 && c->steps_done + steps <= c->T, "run would exceed max_steps");
-    ppde_model* m = c->m;
-    HIPCHK(hipSetDevice(m->device));
-    const Geom& g = m->g;
-    if (c->cfg.rng_mode == 0) {
-        ARGCHK(steps == 0 || (U_dev && q_dev && u_dev && max_u), "rng_mode 0 needs U, q, u and max_u");
-        size_t qoff = 0;
-        for (int i = 0; i < steps; ++i) {
-            ARGCHK(max_u[i] >= 1 && max_u[i] <= c->mu_max, "max_u out of range");
-            int rc = enqueue_iterations(c, 0, nullptr, c->steps_done + i, 1, U_dev + (size_t)i * c->n,
-                                        q_dev + qoff * c->n * g.N, u_dev + (size_t)i * c->n, max_u[i]);
-            if (rc) return rc;
-            qoff += max_u[i];
-        }
-        c->steps_done += steps;
-        return PPDE_OK;
-    }
-    int done = 0;
-    if (c->recomb.on() && !c->graphs.empty()) {
-        // segments start at multiples of `every` only: eager iterations up to the next such position, then the longest segment that
-        // fits, and the rest eagerly
-        const int every = c->recomb.every;
-        while (done < steps) {
-            const int pos = c->steps_done + done, left = steps - done;
-            const ppde_chains::GraphSeg* seg = nullptr;
-            if (pos % every == 0)
-                for (const auto& gs : c->graphs) if (gs.len <= left) { seg = &gs; break; }       // longest first
-            if (seg) {
-                if (c->d_it_val != (long long)pos) {
-                    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->d_it, pos, 1, c->stream));
-                    c->d_it_val = (long long)pos;
-                }
-                HIPCHK(hipGraphLaunch(seg->exec, c->stream));
-                done += seg->len;
-                c->d_it_val += seg->len;
-                c->n_replayed_steps += seg->len;
-                continue;
-            }
-            const int k = pos % every == 0 ? left : std::min(left, every - pos % every);
-            int rc = enqueue_block(c, nullptr, pos, k);
-            if (rc) return rc;
-            c->n_eager_steps += k;
-            done += k;
-        }
-        c->steps_done += steps;
-        return PPDE_OK;
-    }
-    if (!c->graphs.empty()) {
-        for (const auto& gs : c->graphs) {          // longest segment first
-            while (steps - done >= gs.len) {
-                // every segment ends by adding its length to the device counter: it only needs setting after eager
-                // iterations (which take their index from the launch arguments and leave the counter behind)
-                if (c->d_it_val != (long long)c->steps_done + done) {
-                    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)c->d_it, c->steps_done + done, 1, c->stream));
-                    c->d_it_val = (long long)c->steps_done + done;
-                }
-                HIPCHK(hipGraphLaunch(gs.exec, c->stream));
-                done += gs.len;
-                c->d_it_val += gs.len;
-            }
-        }
-        c->n_replayed_steps += done;
-    }
-    if (done < steps) {
-        int rc = enqueue_block(c, nullptr, c->steps_done + done, steps - done);
-        if (rc) return rc;
-        c->n_eager_steps += steps - done;
-    }
-    c->steps_done += steps;
-    return PPDE_OK;
-}
-
-int ppde_chains_graph_stats(ppde_chains* c, int32_t* captures, int32_t* captures_in_run, int64_t* replayed_steps,
-                            int64_t* eager_steps) {
-    ARGCHK(c, "null chains");
-    if (captures) *captures = c->n_captures;
-    if (captures_in_run) *captures_in_run = c->n_captures_in_run;
-    if (replayed_steps) *replayed_steps = c->n_replayed_steps;
-    if (eager_steps) *eager_steps = c->n_eager_steps;
-    return PPDE_OK;
-}
-
-int ppde_chains_sync(ppde_chains* c) {
-    ARGCHK(c, "null chains");
-    HIPCHK(hipSetDevice(c->m->device));
-    // short runs are latency-bound on the host side too: poll the stream for a while before blocking in the driver
-    // (a blocking wait wakes up tens of microseconds after the last kernel; a 20-iteration block is 500 us)
-    hipError_t q = hipErrorNotReady;
-    for (int spin = 0; spin < 20000 && (q = hipStreamQuery(c->stream)) == hipErrorNotReady; ++spin) { }
-    if (q == hipErrorNotReady) q = hipStreamSynchronize(c->stream);
-    HIPCHK(q);
-    const int err = *(volatile int*)c->h_err;
-    if (err & 2) return fail(PPDE_ERR_INVALID, "a supplied path length U exceeds the max_u of its iteration (the noise block holds only max_u sub-steps)");
-    if (err) return fail(PPDE_ERR_NUMERIC, "a proposal row had no usable mass (every move masked out, or every admissible logit 86.6 or more below / one 88.7 above the softmax reference): the categorical is undefined");
-    return PPDE_OK;
-}
-
-int ppde_chains_steps_done(ppde_chains* c) { return c ? c->steps_done : PPDE_ERR_INVALID; }
-
-// `units` x `per_unit` state rows [Ls] at the device address `src` -> plain rows [L] at the host address `dst`, through a device
-// buffer, a block of whole units at a time (32-bit thread indices: at most 2^30 per launch)
-static int read_state_rows(ppde_chains* c, const uint8_t* src, size_t units, size_t per_unit, uint8_t* dst) {
-    const Geom& g = c->m->g;
-    const size_t L = g.L, per = per_unit * (size_t)std::max(g.L, g.Ls);
-    const size_t block = std::max<size_t>(1, std::min<size_t>(units, ((size_t)1 << 30) / per));
-    DevBuf<uint8_t> tmp;
-    HIPCHK(tmp.alloc(block * per_unit * L));
-    for (size_t u = 0; u < units; u += block) {
-        const int rows_n = (int)(std::min(block, units - u) * per_unit);
-        hipLaunchKernelGGL(k_unpack_state, dim3((rows_n * g.L + 255) / 256), dim3(256), 0, c->stream,
-                           src + u * per_unit * g.Ls, tmp.p, rows_n, g.L, g.Ls, g.sh);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipMemcpy(dst + u * per_unit * L, tmp.p, (size_t)rows_n * L, hipMemcpyDeviceToHost));
-    }
-    return PPDE_OK;
-}
-
-int ppde_chains_peek(ppde_chains* c, uint8_t* idx, float* energy, float* fitness, uint8_t* accepted, int32_t* dist) {
-    ARGCHK(c && c->initialised, "chains not initialised");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    const Geom& g = c->m->g;
-    const int n = c->n;
-    hipStream_t s = c->stream;
-    if (idx) {
-        hipLaunchKernelGGL(k_unpack_state, dim3((n * g.L + 255) / 256), dim3(256), 0, s, c->cur, c->tmp_idx, n, g.L, g.Ls, g.sh);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(idx, c->tmp_idx, (size_t)n * g.L, hipMemcpyDeviceToHost, s));
-    }
-    if (dist) {
-        hipLaunchKernelGGL(k_mut_distance, dim3((n + 3) / 4), dim3(256), 0, s, c->cur, c->m->d_wt, n, g.L, g.Ls, g.sh, c->tmp_dist);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(dist, c->tmp_dist, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    if (energy) HIPCHK(hipMemcpyAsync(energy, c->e_hist + (size_t)c->steps_done * n, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (fitness) HIPCHK(hipMemcpyAsync(fitness, c->f_hist + (size_t)c->steps_done * n, n * sizeof(float), hipMemcpyDeviceToHost, s));
-    if (accepted) {
-        hipLaunchKernelGGL(k_rec_gather, dim3((n + 255) / 256), dim3(256), 0, s, chain_args(c), (float*)nullptr, (float*)nullptr,
-                           (int*)nullptr, c->tmp_acc);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(accepted, c->tmp_acc, n, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    return PPDE_OK;
-}
-
-int ppde_chains_collect(ppde_chains* c, uint8_t* best_idx, float* best_energy, float* best_fitness, int32_t* best_step,
-                        float* energy_history, float* fitness_history, uint8_t* random_traj) {
-    ARGCHK(c && c->initialised, "chains not initialised");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    const Geom& g = c->m->g;
-    const size_t n = c->n, rows = (size_t)c->steps_done + 1;
-    if (best_idx) HIPCHK(hipMemcpy(best_idx, c->best_state, n * g.L, hipMemcpyDeviceToHost));
-    hipLaunchKernelGGL(k_rec_gather, dim3(((int)n + 255) / 256), dim3(256), 0, c->stream, chain_args(c), c->tmp_be, c->tmp_bf,
-                       c->tmp_bt, (uint8_t*)nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (best_energy) HIPCHK(hipMemcpy(best_energy, c->tmp_be, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (best_fitness) HIPCHK(hipMemcpy(best_fitness, c->tmp_bf, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (best_step) HIPCHK(hipMemcpy(best_step, c->tmp_bt, n * sizeof(int), hipMemcpyDeviceToHost));
-    if (energy_history) HIPCHK(hipMemcpy(energy_history, c->e_hist, rows * n * sizeof(float), hipMemcpyDeviceToHost));
-    if (fitness_history) HIPCHK(hipMemcpy(fitness_history, c->f_hist, rows * n * sizeof(float), hipMemcpyDeviceToHost));
-    if (random_traj) {
-        ARGCHK(c->cfg.random_chain >= 0, "no random trajectory was recorded (random_chain = -1)");
-        HIPCHK(hipMemcpy(random_traj, c->rtraj, rows * g.L, hipMemcpyDeviceToHost));
-    }
-    return PPDE_OK;
-}
-
-int ppde_chains_tempering_state(ppde_chains* c, int32_t* rung, float* beta, int64_t* swap_attempts, int64_t* swap_accepts) {
-    ARGCHK(c && c->initialised, "chains not initialised");
-    ARGCHK(c->temper.on(), "ppde_chains_tempering_state: no tempering was set (ppde_chains_set_tempering)");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    const size_t n = c->n, pairs = (n / c->temper.n_rungs) * (size_t)(c->temper.n_rungs - 1);
-    if (rung) HIPCHK(hipMemcpy(rung, c->temper.rung, n * sizeof(int), hipMemcpyDeviceToHost));
-    if (beta) HIPCHK(hipMemcpy(beta, c->temper.beta, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (swap_attempts && pairs) HIPCHK(hipMemcpy(swap_attempts, c->temper.swap_attempts, pairs * sizeof(long long), hipMemcpyDeviceToHost));
-    if (swap_accepts && pairs) HIPCHK(hipMemcpy(swap_accepts, c->temper.swap_accepts, pairs * sizeof(long long), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-
-int ppde_chains_tempering_history(ppde_chains* c, uint8_t* rung_history) {
-    ARGCHK(c && c->initialised && rung_history, "chains not initialised, or null argument");
-    ARGCHK(c->temper.on(), "ppde_chains_tempering_history: no tempering was set (ppde_chains_set_tempering)");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    HIPCHK(hipMemcpy(rung_history, c->temper.rung_hist, ((size_t)c->steps_done + 1) * c->n, hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-
-int ppde_chains_set_recorder(ppde_chains* c, const ppde_record_config* cfg) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_recorder: the recorder must be set before ppde_chains_init (its graphs hold the pointers)");
-    ARGCHK(!c->pairs.on(), "ppde_chains_set_recorder: pair counts are set and follow this recorder's schedule; clear the pair counts first "
-                           "(ppde_chains_set_pair_counts(c, NULL))");
-    if (!cfg) {                                     // clear
-        HIPCHK(hipSetDevice(c->device));
-        c->recorder = {};
-        return PPDE_OK;
-    }
-    ARGCHK(cfg->every >= 1, "ppde_chains_set_recorder: every must be >= 1");
-    ARGCHK(cfg->burn_in >= 0, "ppde_chains_set_recorder: negative burn_in");
-    ARGCHK(cfg->rung >= -1, "ppde_chains_set_recorder: rung must be -1 (every chain) or a rung of the ladder");
-    ARGCHK(cfg->keep_samples == 0 || cfg->keep_samples == 1, "ppde_chains_set_recorder: keep_samples must be 0 or 1");
-    ARGCHK(cfg->rung < 0 || c->temper.on(), "ppde_chains_set_recorder: following a rung needs tempering (ppde_chains_set_tempering first)");
-    ARGCHK(cfg->rung < c->temper.n_rungs || cfg->rung < 0, "ppde_chains_set_recorder: rung beyond the ladder");
-    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_recorder: n_streams > 1 is not supported (the counters have one "
-                                                            "owner per launch)");
-    const int rows_cap = c->T > cfg->burn_in ? (c->T - cfg->burn_in) / cfg->every : 0;
-    ARGCHK(rows_cap >= 1, "ppde_chains_set_recorder: no iteration of max_steps would be recorded (burn_in + every > max_steps)");
-    HIPCHK(hipSetDevice(c->device));
-    // allocate everything first: a failure leaves the object as it was
-    const Geom& g = c->m->g;
-    const size_t slots = cfg->rung >= 0 ? (size_t)c->n / c->temper.n_rungs : (size_t)c->n, cells = (size_t)rows_cap * slots;
-    const size_t n_counts = (size_t)g.L * PPDE_A;
-    Recorder t;
-    t.cfg = *cfg; t.rows_cap = rows_cap; t.slots = (int)slots;
-    hipError_t e = t.counts.alloc_zero(n_counts);
-    if (cfg->keep_samples) {
-        if (e == hipSuccess) e = t.idx.alloc_zero(cells * (size_t)g.Ls);
-        if (e == hipSuccess) e = t.e.alloc(cells);
-        if (e == hipSuccess) e = t.f.alloc(cells);
-        if (e == hipSuccess) e = t.chain.alloc(cells);
-    }
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_recorder: device allocation: ") + hipGetErrorString(e));
-    c->recorder = std::move(t);
-    return PPDE_OK;
-}
-
-int ppde_chains_recorder_shape(ppde_chains* c, int32_t* rows_done, int32_t* rows_cap, int32_t* slots) {
-    ARGCHK(c, "null argument");
-    ARGCHK(c->recorder.on(), "ppde_chains_recorder_shape: no recorder was set (ppde_chains_set_recorder)");
-    if (rows_done) *rows_done = c->initialised ? c->recorder.rows_done(c->steps_done) : 0;
-    if (rows_cap) *rows_cap = c->recorder.rows_cap;
-    if (slots) *slots = c->recorder.slots;
-    return PPDE_OK;
-}
-
-int ppde_chains_recorder_read(ppde_chains* c, int first_row, int n_rows, uint8_t* idx, float* energy, float* fitness,
-                              int32_t* chain, uint64_t* site_counts) {
-    ARGCHK(c && c->initialised, "chains not initialised");
-    ARGCHK(c->recorder.on(), "ppde_chains_recorder_read: no recorder was set (ppde_chains_set_recorder)");
-    ARGCHK(first_row >= 0 && n_rows >= 0 && (long long)first_row + n_rows <= c->recorder.rows_done(c->steps_done),
-           "ppde_chains_recorder_read: rows beyond those recorded so far (ppde_chains_recorder_shape: rows_done)");
-    ARGCHK(c->recorder.cfg.keep_samples || !(idx || energy || fitness || chain),
-           "ppde_chains_recorder_read: the recorder keeps site counts only (keep_samples = 0): pass NULL for the samples");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    const Geom& g = c->m->g;
-    const size_t slots = c->recorder.slots, cells = (size_t)n_rows * slots, o = (size_t)first_row * slots;
-    if (idx && cells && (rc = read_state_rows(c, c->recorder.idx + o * g.Ls, (size_t)n_rows, slots, idx))) return rc;   // [rows][slots][Ls] -> [L]
-    if (energy && cells) HIPCHK(hipMemcpy(energy, c->recorder.e + o, cells * sizeof(float), hipMemcpyDeviceToHost));
-    if (fitness && cells) HIPCHK(hipMemcpy(fitness, c->recorder.f + o, cells * sizeof(float), hipMemcpyDeviceToHost));
-    if (chain && cells) HIPCHK(hipMemcpy(chain, c->recorder.chain + o, cells * sizeof(int), hipMemcpyDeviceToHost));
-    if (site_counts) HIPCHK(hipMemcpy(site_counts, c->recorder.counts, (size_t)g.L * PPDE_A * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-
-int ppde_chains_set_archive(ppde_chains* c, const ppde_archive_config* cfg) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_archive: the archive must be set before ppde_chains_init (its graphs hold the pointers)");
-    if (!cfg) {                                     // clear
-        HIPCHK(hipSetDevice(c->device));
-        c->archive = {};
-        return PPDE_OK;
-    }
-    ARGCHK(cfg->k >= 1 && cfg->k <= ARCH_KMAX, "ppde_chains_set_archive: k must be in 1..32");
-    ARGCHK(!c->cfg.paper_results, "ppde_chains_set_archive: paper_results is not supported (after a rejection its history row holds the "
-                                  "energy of the state that was left while the chain continues from its initial state: a mismatched pair)");
-    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_archive: n_streams > 1 is not supported (one launch archives "
-                                                            "every chain of the object)");
-    HIPCHK(hipSetDevice(c->device));
-    // allocate everything first: a failure leaves the object as it was
-    const Geom& g = c->m->g;
-    const size_t n = c->n, cells = n * (size_t)cfg->k;
-    Archive t;
-    t.k = cfg->k;
-    hipError_t e = t.idx.alloc_zero(cells * (size_t)g.Ls);
-    if (e == hipSuccess) e = t.e.alloc(cells);
-    if (e == hipSuccess) e = t.f.alloc(cells);
-    if (e == hipSuccess) e = t.step.alloc(cells);
-    if (e == hipSuccess) e = t.hash.alloc(cells);
-    if (e == hipSuccess) e = t.count.alloc_zero(n);
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_archive: device allocation: ") + hipGetErrorString(e));
-    c->archive = std::move(t);
-    return PPDE_OK;
-}
-
-int ppde_chains_archive_shape(ppde_chains* c, int32_t* k) {
-    ARGCHK(c, "null argument");
-    ARGCHK(c->archive.on(), "ppde_chains_archive_shape: no archive was set (ppde_chains_set_archive)");
-    if (k) *k = c->archive.k;
-    return PPDE_OK;
-}
-
-int ppde_chains_archive_read(ppde_chains* c, uint8_t* idx, float* energy, float* fitness, int32_t* step, int32_t* count) {
-    ARGCHK(c && c->archive.on(), "ppde_chains_archive_read: no archive was set (ppde_chains_set_archive)");
-    ARGCHK(c->initialised, "chains not initialised");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    const Geom& g = c->m->g;
-    const size_t n = c->n, K = c->archive.k, cells = n * K, L = g.L;
-    std::vector<float> he(cells), hf(cells);
-    std::vector<int> hs(cells), hc(n);
-    HIPCHK(hipMemcpy(he.data(), c->archive.e, cells * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hf.data(), c->archive.f, cells * sizeof(float), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hs.data(), c->archive.step, cells * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(hc.data(), c->archive.count, n * sizeof(int), hipMemcpyDeviceToHost));
-    std::vector<uint8_t> hi;
-    if (idx) {
-        hi.resize(cells * L);
-        if ((rc = read_state_rows(c, c->archive.idx, n, K, hi.data()))) return rc;   // [n][K][Ls] -> [n][K][L]
-    }
-    // each chain's entries by (energy descending, step ascending); the slots beyond count filled
-    std::vector<int> order(K);
-    for (size_t b = 0; b < n; ++b) {
-        const int cnt = std::max(0, std::min(hc[b], (int)K));
-        const size_t o = b * K;
-        for (int j = 0; j < cnt; ++j) order[j] = j;
-        std::sort(order.begin(), order.begin() + cnt, [&](int x, int y) {
-            return he[o + x] > he[o + y] || (he[o + x] == he[o + y] && hs[o + x] < hs[o + y]);
-        });
-        for (size_t j = 0; j < K; ++j) {
-            const bool live = (int)j < cnt;
-            const size_t src = o + (live ? order[j] : 0);
-            if (energy) energy[o + j] = live ? he[src] : -INFINITY;
-            if (fitness) fitness[o + j] = live ? hf[src] : 0.f;
-            if (step) step[o + j] = live ? hs[src] : -1;
-            if (idx) {
-                if (live) memcpy(idx + (o + j) * L, hi.data() + src * L, L);
-                else memset(idx + (o + j) * L, 255, L);
-            }
-        }
-        if (count) count[b] = cnt;
-    }
-    return PPDE_OK;
-}
-
-int ppde_chains_set_stats(ppde_chains* c, const ppde_stats_config* cfg) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_stats: the statistics must be set before ppde_chains_init (its graphs hold the pointers)");
-    if (!cfg) {                                     // clear
-        HIPCHK(hipSetDevice(c->device));
-        c->stats = {};
-        return PPDE_OK;
-    }
-    ARGCHK(cfg->per_site == 0 || cfg->per_site == 1, "ppde_chains_set_stats: per_site must be 0 or 1");
-    ARGCHK(c->streams.size() <= 1 && c->cfg.n_streams <= 1, "ppde_chains_set_stats: n_streams > 1 is not supported (the counters have one "
-                                                            "owner per launch)");
-    HIPCHK(hipSetDevice(c->device));
-    // allocate everything first: a failure leaves the object as it was
-    const Geom& g = c->m->g;
-    MoveStats t;
-    t.n = c->n; t.R = std::max(c->temper.n_rungs, 1); t.M = c->mu_max; t.L = g.L; t.per_site = cfg->per_site;
-    hipError_t e = t.cnt.alloc_zero(t.cells_total());
-    if (e == hipSuccess) e = t.prev.alloc_zero(2 * (size_t)t.n * g.Ls);
-    if (e == hipSuccess) e = t.dist.alloc_zero((size_t)t.n);
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_stats: device allocation: ") + hipGetErrorString(e));
-    c->stats = std::move(t);
-    return PPDE_OK;
-}
-
-int ppde_chains_stats_shape(ppde_chains* c, int32_t* n_rungs, int32_t* n_lengths, int32_t* per_site) {
-    ARGCHK(c, "null argument");
-    ARGCHK(c->stats.on(), "ppde_chains_stats_shape: no statistics were set (ppde_chains_set_stats)");
-    if (n_rungs) *n_rungs = c->stats.R;
-    if (n_lengths) *n_lengths = c->mu_max;
-    if (per_site) *per_site = c->stats.per_site;
-    return PPDE_OK;
-}
-
-int ppde_chains_stats_read(ppde_chains* c, int64_t* iters, int64_t* accepts, int64_t* moved, int64_t* jump_sum, int64_t* dist_sum,
-                           int64_t* wt_returns, int64_t* len_attempts, int64_t* len_accepts, int64_t* site_changes) {
-    ARGCHK(c && c->stats.on(), "ppde_chains_stats_read: no statistics were set (ppde_chains_set_stats)");
-    ARGCHK(c->initialised, "chains not initialised");
-    ARGCHK(c->stats.per_site || !site_changes, "ppde_chains_stats_read: the statistics keep no per-site counts (per_site = 0): pass NULL "
-                                               "for site_changes");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    int64_t* out[9] = {iters, accepts, moved, jump_sum, dist_sum, wt_returns, len_attempts, len_accepts, site_changes};
-    for (int k = 0; k < 9; ++k)
-        if (out[k] && c->stats.cells(k))
-            HIPCHK(hipMemcpy(out[k], c->stats.counter(k), c->stats.cells(k) * sizeof(long long), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-
-int ppde_chains_set_pair_counts(ppde_chains* c, const ppde_pair_config* cfg) {
-    ARGCHK(c, "null argument");
-    ARGCHK(!c->initialised, "ppde_chains_set_pair_counts: pair counts must be set before ppde_chains_init (its graphs hold the pointers)");
-    if (!cfg) {                                     // clear
-        HIPCHK(hipSetDevice(c->device));
-        c->pairs = {};
-        return PPDE_OK;
-    }
-    ARGCHK(c->recorder.on(), "ppde_chains_set_pair_counts: no recorder was set (pair counts follow its schedule and slots: "
-                             "ppde_chains_set_recorder first)");
-    const int L = c->m->g.L;
-    ARGCHK(cfg->n_sites >= 0 && cfg->n_sites <= L, "ppde_chains_set_pair_counts: n_sites must be in 0..L (0: every residue)");
-    ARGCHK(cfg->n_sites == 0 || cfg->sites, "ppde_chains_set_pair_counts: n_sites > 0 needs a site list");
-    ARGCHK(cfg->n_sites > 0 || !cfg->sites, "ppde_chains_set_pair_counts: a site list with n_sites = 0 (0 with NULL selects every residue)");
-    const int S = cfg->n_sites ? cfg->n_sites : L;
-    for (int i = 0; i < cfg->n_sites; ++i) {
-        if (cfg->sites[i] < 0 || cfg->sites[i] >= L)
-            return fail(PPDE_ERR_INVALID, "ppde_chains_set_pair_counts: sites[" + std::to_string(i) + "] = " + std::to_string(cfg->sites[i]) +
-                                          " lies outside the sequence 0.." + std::to_string(L - 1));
-        if (i > 0 && cfg->sites[i] <= cfg->sites[i - 1])
-            return fail(PPDE_ERR_INVALID, "ppde_chains_set_pair_counts: the sites must be strictly increasing (sites[" + std::to_string(i) +
-                                          "] <= sites[" + std::to_string(i - 1) + "])");
-    }
-    HIPCHK(hipSetDevice(c->device));
-    // allocate everything first: a failure leaves the object as it was
-    PairCounts t;
-    t.nt = (S + PAIR_TS - 1) / PAIR_TS;
-    std::vector<int32_t> padded((size_t)t.nt * PAIR_TS, -1);
-    for (int i = 0; i < S; ++i) padded[i] = cfg->n_sites ? cfg->sites[i] : i;
-    t.sites.assign(padded.begin(), padded.begin() + S);
-    hipError_t e = t.sites_dev.alloc(padded.size());
-    if (e == hipSuccess) e = hipMemcpy(t.sites_dev, padded.data(), padded.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = t.counts.alloc_zero(t.tiles() * PAIR_TILE);
-    if (e != hipSuccess) return fail(PPDE_ERR_HIP, std::string("ppde_chains_set_pair_counts: device allocation: ") + hipGetErrorString(e));
-    c->pairs = std::move(t);
-    return PPDE_OK;
-}
-
-int ppde_chains_pair_counts_shape(ppde_chains* c, int32_t* n_sites, int32_t* sites) {
-    ARGCHK(c, "null argument");
-    ARGCHK(c->pairs.on(), "ppde_chains_pair_counts_shape: no pair counts were set (ppde_chains_set_pair_counts)");
-    if (n_sites) *n_sites = (int32_t)c->pairs.sites.size();
-    if (sites) std::copy(c->pairs.sites.begin(), c->pairs.sites.end(), sites);
-    return PPDE_OK;
-}
-
-int ppde_chains_pair_counts_read(ppde_chains* c, uint64_t* pair_counts) {
-    ARGCHK(c && c->initialised, "chains not initialised");
-    ARGCHK(c->pairs.on(), "ppde_chains_pair_counts_read: no pair counts were set (ppde_chains_set_pair_counts)");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    if (!pair_counts) return PPDE_OK;
-    // the device keeps the upper block triangle, tile by tile (pairs.h): one row of tiles at a time to the host, mirrored here
-    const size_t S = c->pairs.sites.size(), W = S * PPDE_A;
-    const int nt = c->pairs.nt;
-    std::vector<unsigned long long> rowbuf((size_t)nt * PAIR_TILE);
-    size_t first = 0;
-    for (int ti = 0; ti < nt; ++ti) {
-        const size_t tiles = (size_t)(nt - ti);
-        HIPCHK(hipMemcpy(rowbuf.data(), c->pairs.counts + first * PAIR_TILE, tiles * PAIR_TILE * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost));
-        first += tiles;
-        for (int tj = ti; tj < nt; ++tj)
-            for (int p = 0; p < PAIR_TS; ++p)
-                for (int q = 0; q < PAIR_TS; ++q) {
-                    const size_t i = (size_t)ti * PAIR_TS + p, j = (size_t)tj * PAIR_TS + q;
-                    if (i >= S || j >= S) continue;
-                    const unsigned long long* bins = rowbuf.data() + ((size_t)(tj - ti) * PAIR_TS * PAIR_TS + p * PAIR_TS + q) * PAIR_BINS;
-                    for (int x = 0; x < PPDE_A; ++x)
-                        for (int y = 0; y < PPDE_A; ++y) {
-                            const uint64_t v = bins[x * PPDE_A + y];
-                            pair_counts[(i * PPDE_A + x) * W + j * PPDE_A + y] = v;
-                            if (tj != ti) pair_counts[(j * PPDE_A + y) * W + i * PPDE_A + x] = v;
-                        }
-                }
-    }
-    return PPDE_OK;
-}
-
-int ppde_chains_trace(ppde_chains* c, int32_t* flat, uint8_t* accepted, float* log_acc, int32_t* U) {
-    ARGCHK(c && c->cfg.trace, "chains were created without trace");
-    int rc = ppde_chains_sync(c);
-    if (rc) return rc;
-    const size_t n = c->n, t = c->steps_done;
-    if (flat) HIPCHK(hipMemcpy(flat, c->tr_flat, t * c->mu_max * n * sizeof(int), hipMemcpyDeviceToHost));
-    if (accepted) HIPCHK(hipMemcpy(accepted, c->tr_acc, t * n, hipMemcpyDeviceToHost));
-    if (log_acc) HIPCHK(hipMemcpy(log_acc, c->tr_logacc, t * n * sizeof(float), hipMemcpyDeviceToHost));
-    if (U) HIPCHK(hipMemcpy(U, c->tr_U, t * n * sizeof(int), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-
-int ppde_chains_philox_dump(ppde_chains* c, int it, int s, float* q_dev, float* u_dev, int32_t* U_dev) {
-    ARGCHK(c && q_dev && u_dev && U_dev, "null argument");
-    ARGCHK(s >= 0 && s < c->mu_max, "sub-step out of range");
-    HIPCHK(hipSetDevice(c->m->device));
-    PasArgs a = chain_args(c);
-    hipLaunchKernelGGL(k_philox_dump, dim3(c->n), dim3(256), 0, c->stream, a.key, it, s, c->cfg.pas_length, c->n,
-                       c->m->g.N, q_dev, u_dev, U_dev);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return PPDE_OK;
-}
-
-#ifdef PPDE_STAMPS
-int ppde_debug_read_stamps(ppde_chains* c, unsigned long long* out128) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out128, c->dbg, 128 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-// per-workgroup records of the last k_cnn launch: [wg][4] = 100 MHz ticks at entry, route start, route end, exit
-int ppde_debug_read_wg_stamps(ppde_chains* c, unsigned long long* out, int words) {
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipMemcpy(out, c->dbg + 128, (size_t)std::min(words, PPDE_DBG_WORDS - 128) * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return PPDE_OK;
-}
-#endif
-
-int ppde_chains_time_potts_in_situ(ppde_chains* c, int iters, float* avg_us, int* launches, float* avg_dispatch_us) {
-    ARGCHK(c && c->initialised && avg_us && launches && iters >= 1, "bad argument");
-    // only launch_potts and launch_chain_kernel bind events: with another expert in the energy the event in front of a Potts
-    // launch would not be its immediate predecessor's
-    ARGCHK((c->cfg.which & 7) == 1, "in-situ timing is defined for the Potts-only energy (which = 1)");
-    ARGCHK(c->cfg.rng_mode == 1, "in-situ timing needs the device RNG");
-    ARGCHK(c->steps_done + iters <= c->T, "run would exceed max_steps");
-    ARGCHK(c->streams.size() == 1, "in-situ timing takes consecutive dispatches of ONE stream");
-    HIPCHK(hipSetDevice(c->m->device));
-    EventPool pool;
-    pool.ev.assign((size_t)iters * 4 * c->streams.size() + 4, nullptr);     // every kernel of an iteration: <= 2 expert + 2 chain launches
-    pool.is_potts.assign(pool.ev.size(), 0);
-    for (auto& e : pool.ev) HIPCHK(hipEventCreate(&e));
-    g_potts_events = &pool;
-    int rc = enqueue_block(c, nullptr, c->steps_done, iters);
-    g_potts_events = nullptr;
-    if (rc == PPDE_OK) {
-        c->steps_done += iters;
-        rc = ppde_chains_sync(c);
-    }
-    if (rc) return rc;
-    ARGCHK(!pool.exhausted, "event pool exhausted: a launch went out untimed");
-    double tot = 0.0, tot_d = 0.0;
-    int cnt = 0, cnt_d = 0;
-    for (size_t i = 1; i < pool.used; ++i) {                             // predecessor's end -> this Potts launch's end
-        float ms = 0.f;
-        if (!pool.is_potts[i]) continue;
-        if (hipEventElapsedTime(&ms, pool.ev[i - 1], pool.ev[i]) == hipSuccess) { tot += ms; ++cnt; }
-        // the dispatch's own interval: an event bound to a kernel against itself yields that command's start -> end as the
-        // command processor stamped them (the pair rocprofv3's kernel trace reads)
-        if (hipEventElapsedTime(&ms, pool.ev[i], pool.ev[i]) == hipSuccess) { tot_d += ms; ++cnt_d; }
-    }
-    (void)hipGetLastError();
-    ARGCHK(cnt > 0, "no Potts launch was timed");
-    *avg_us = (float)(tot * 1000.0 / cnt);
-    *launches = cnt;
-    if (avg_dispatch_us) *avg_dispatch_us = cnt_d ? (float)(tot_d * 1000.0 / cnt_d) : 0.f;
-    return PPDE_OK;
-}
-
-int ppde_chains_time_experts(ppde_chains* c, int reps, float* avg_us) {
-    ARGCHK(c && c->initialised && avg_us && reps >= 1, "bad argument");
-    HIPCHK(hipSetDevice(c->m->device));
-    EventPair ev;
-    HIPCHK(hipEventCreate(&ev.a));
-    HIPCHK(hipEventCreate(&ev.b));
-    // current states into the proposal slot, exactly as the evaluation inside an iteration launches it
-    int rc = eval_experts(c->m, c->cfg.which, cur_states(c), c->n, chain_targets(c, 1), 1, c->stream);   // warm
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(ev.a, c->stream));
-    for (int i = 0; i < reps; ++i)
-        if ((rc = eval_experts(c->m, c->cfg.which, cur_states(c), c->n, chain_targets(c, 1), 1, c->stream))) return rc;
-    HIPCHK(hipEventRecord(ev.b, c->stream));
-    HIPCHK(hipEventSynchronize(ev.b));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, ev.a, ev.b));
-    *avg_us = ms * 1000.f / reps;
-    return PPDE_OK;
-}
-
-int ppde_chains_time_potts_kernel(ppde_chains* c, int reps, float* avg_us) {
-    ARGCHK(c && c->initialised && avg_us && reps >= 1, "bad argument");
-    ARGCHK(c->cfg.which & 1, "no Potts expert in this energy");
-    HIPCHK(hipSetDevice(c->m->device));
-    EventPair ev;
-    HIPCHK(hipEventCreate(&ev.a));
-    HIPCHK(hipEventCreate(&ev.b));
-    hipEvent_t e0 = ev.a, e1 = ev.b;
-    // writes the proposal slot, exactly as the launch inside an iteration does
-    EvalTargets t = chain_targets(c, 1);
-    int rc = launch_potts(c->m, cur_states(c), c->n, t, c->stream);   // warm
-    if (rc) return rc;
-    HIPCHK(hipEventRecord(e0, c->stream));
-    for (int i = 0; i < reps; ++i) {
-        rc = launch_potts(c->m, cur_states(c), c->n, t, c->stream);
-        if (rc) return rc;
-    }
-    HIPCHK(hipEventRecord(e1, c->stream));
-    HIPCHK(hipEventSynchronize(e1));
-    float ms = 0.f;
-    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
-    *avg_us = ms * 1000.f / reps;
-    return PPDE_OK;
-}
-
-}  // extern "C"
+#include "chains.h"

@@ -1,8 +1,8 @@
 #!/bin/bash
 # Builds the host side of ppde_api.hip (no device code) + the mock runtime + one driver of this directory with AddressSanitizer
 # and runs it: bash tests/hostcheck/build_and_run.sh NAME [sweep], NAME one of abi, reversible, tempering, recorder, pairs,
-# archive, stats, anneal. Output: tests/hostcheck/_build/NAME/ (git-ignored; one directory per driver, so two drivers can be
-# built at the same time).
+# archive, stats, anneal, anneal_adaptive, recombine. Output: tests/hostcheck/_build/NAME/ (git-ignored; one directory per driver,
+# so two drivers can be built at the same time). HIPMOCK_TRACE=FILE in the environment: the mock's call trace (hipmock.cpp).
 set -e
 NAME=${1:?usage: build_and_run.sh NAME [sweep]}; shift
 HERE=$(cd "$(dirname "$0")" && pwd); ROOT=$(cd "$HERE/../.." && pwd); B=$HERE/_build/$NAME

@@ -4,6 +4,7 @@
 // recombination_shape / read -> collect -> destroy on both RNG modes and both gradient policies, an event-aligned and a misaligned
 // run sequence over captured graphs, and -- with `driver sweep` -- the same walk once per fallible runtime call with that call
 // failing, so every clean-up path runs. Kernels do not run here: numbers mean nothing, memory errors and leaks are the point.
+// Besides the walks: the replay plan of ppde_chains_run (replay_plan below), with and without the mode.
 #include "walk.h"
 
 namespace {
@@ -193,8 +194,59 @@ done:
     if (m) ppde_model_destroy(m);
     return status;
 }
+
+// The replay plan: which iterations of a run are replayed from the graph segments captured at init and which are enqueued eagerly.
+// Device RNG, use_graph, max_steps 130, runs of 7, 100 and 23 iterations; ppde_chains_graph_stats after each. Segments are taken
+// longest first and, with recombination, start at multiples of `every` only:
+//   no recombination (segments 100, 20): eager 7 | 100 | 20 + eager 3
+//   every = 3 (segments 99, 3):          3 3 + eager 1 | eager 2, 32 x 3, eager 2 | eager 1, 7 x 3, eager 1
+//   every = 7 (segments 98, 7):          7 | 98 + eager 2 | eager 5, 7 7, eager 4
+// Nothing is captured inside a run.
+int replay_plan(bool verbose) {
+    int status = PPDE_OK;
+    ppde_model* m = nullptr;
+    ppde_chains* c = nullptr;
+    const int L = 48, Lp = 40, win = 4, n = 8;
+    const int runs[3] = {7, 100, 23};
+    struct Case { int every, captures; long long replayed[3], eager[3]; };
+    const Case cases[3] = {{0, 2, {0, 100, 120}, {7, 7, 10}}, {3, 2, {6, 102, 123}, {1, 5, 7}}, {7, 2, {7, 105, 119}, {0, 2, 11}}};
+    std::vector<uint8_t> wt(L, 3), idx((size_t)n * L, 3);
+    auto J = rnd((size_t)Lp * Lp * 400, 0.05f), h = rnd((size_t)Lp * 20, 0.5f);
+    TRY(ppde_model_create(&m, 0, L, wt.data()));
+    TRY(ppde_model_set_potts(m, J.data(), h.data(), Lp, win));
+    for (const Case& k : cases) {
+        ppde_chain_config cfg{};
+        cfg.n_chains = n; cfg.max_steps = 130; cfg.pas_length = 2; cfg.min_pos = win; cfg.max_pos = win + Lp - 1;
+        cfg.which = 1; cfg.rng_mode = 1; cfg.random_chain = -1; cfg.use_graph = 1; cfg.n_streams = 1; cfg.seed = 3;
+        TRY(ppde_chains_create(&c, m, &cfg));
+        if (k.every) {
+            ppde_recombine_config r = rcfg(2, k.every);
+            TRY(ppde_chains_set_reversible(c, 1));
+            TRY(ppde_chains_set_recombination(c, &r));
+        }
+        TRY(ppde_chains_init(c, idx.data()));
+        for (int i = 0; i < 3; ++i) {
+            TRY(ppde_chains_run(c, runs[i], nullptr, nullptr, nullptr, nullptr));
+            int32_t cap = 0, cap_run = 0; int64_t rep = 0, eag = 0;
+            TRY(ppde_chains_graph_stats(c, &cap, &cap_run, &rep, &eag));
+            if (verbose) fprintf(stderr, "replay plan, every = %d, after run %d: %d captures (%d in a run), %lld replayed, %lld eager\n", k.every, i,
+                                 cap, cap_run, (long long)rep, (long long)eag);
+            if (cap != k.captures || cap_run != 0 || rep != k.replayed[i] || eag != k.eager[i]) {
+                fprintf(stderr, "replay plan, every = %d, run %d: expected %d captures (0 in a run), %lld replayed, %lld eager\n", k.every, i,
+                        k.captures, k.replayed[i], k.eager[i]);
+                status = 90; goto done;
+            }
+        }
+        TRY(ppde_chains_sync(c));
+        ppde_chains_destroy(c); c = nullptr;
+    }
+done:
+    if (c) ppde_chains_destroy(c);
+    if (m) ppde_model_destroy(m);
+    return status;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
-    return run_walks(argc, argv, "hostcheck recombine ok: %ld fallible runtime calls per walk, %ld injected failures handled\n", walk);
+    return run_walks(argc, argv, "hostcheck recombine ok: %ld fallible runtime calls per walk, %ld injected failures handled\n", walk, replay_plan);
 }

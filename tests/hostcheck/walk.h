@@ -16,6 +16,7 @@ extern "C" void hipmock_rearm(long fail_at);
 extern "C" long hipmock_launches();
 extern "C" long hipmock_allocs();
 extern "C" long hipmock_writes();
+extern "C" void hipmock_note(const char* text);   // a line of the driver's own in the mock's call trace (HIPMOCK_TRACE)
 
 namespace {
 std::mt19937 rng(7);
@@ -33,9 +34,10 @@ Ptrs many(int count, size_t n) { Ptrs r; for (int i = 0; i < count; ++i) r.store
 #define WALK_FAIL(code) do { status = (code); goto done; } while (0)
 #define TRY(x) do { int rc_ = (x); if (rc_ != PPDE_OK) { if (verbose) fprintf(stderr, "  %s -> %d (%s)\n", #x, rc_, ppde_last_error()); status = rc_; goto done; } } while (0)
 // a refusal: PPDE_ERR_INVALID with a message (naming `word`, where one is given), and the runtime sees no launch, allocation, copy
-// or fill across the call
+// or fill across the call. The message goes into the call trace.
 inline const char* walk_word(const char* word = "") { return word; }
 #define EXPECT_INVALID(x, ...) do { const long l_ = hipmock_launches(), a_ = hipmock_allocs(), w_ = hipmock_writes(); int rc_ = (x); \
+    hipmock_note(ppde_last_error()); \
     if (rc_ != PPDE_ERR_INVALID || !ppde_last_error()[0] || !strstr(ppde_last_error(), walk_word(__VA_ARGS__))) { \
         fprintf(stderr, "expected PPDE_ERR_INVALID with a message naming '%s' from %s, got %d (%s)\n", walk_word(__VA_ARGS__), #x, rc_, ppde_last_error()); \
         WALK_FAIL(99); } \
