@@ -84,12 +84,13 @@ def plan(e, dbeta, u, fault=None):
 
 
 def annealed_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_length, nmut_threshold, betas, every, deme,
-                 seed=0, chain_offset=0, allowed=None, trace=False, select_u=None, fault=None):
+                 seed=0, chain_offset=0, allowed=None, trace=False, select_u=None, fault=None, keep_probs=False):
     """The whole mode on explicit noise: what hr.reversible_run returns (histories and best states on the UNTEMPERED energy;
     history row it + 1 and states[it + 1] describe the population AFTER selection), plus parent int32 [events, n] (local
     indices), pre_energy fp32 [events, n], log_mean_w / ess fp64 [events, n / D], beta fp32 [n] at the end, accepted
     [T, n] (the slots' own Metropolis results), post_accept (states, energies) per iteration, and select_margin, the smallest
-    |tau_j - C_i| / W over all offspring. `select_u`: callable it -> u [n / D] replacing Philox."""
+    |tau_j - C_i| / W over all offspring. `select_u`: callable it -> u [n / D] replacing Philox. `keep_probs`: the traces keep the
+    forward proposal rows (helpers_reversible.replay_margins reads them)."""
     betas = np.asarray(betas, dtype=np.float32)
     S, D = int(betas.size) - 1, int(deme)
     thr = hr._threshold(nmut_threshold)
@@ -110,7 +111,7 @@ def annealed_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_l
     for it in range(num_steps):
         U, q, u = noise(it)
         sc = ht.ScaledEnergy(energy, beta)
-        out = hr.reversible_iteration(sc, cur, cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed)
+        out = hr.reversible_iteration(sc, cur, cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
         (ex, fx), (ey, fy) = sc.raw
         a = out["accepted"]
         cur = out["idx"].clone()

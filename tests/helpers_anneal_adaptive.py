@@ -93,37 +93,38 @@ def ulp32(b):
 
 
 def adaptive_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_length, nmut_threshold, beta_start, beta_end, rho,
-                 min_step, every, deme, max_stages=4096, seed=0, chain_offset=0, allowed=None, fault=None):
+                 min_step, every, deme, max_stages=4096, seed=0, chain_offset=0, allowed=None, fault=None, trace=False, keep_probs=False):
     """The adaptive run of ONE deme (idx0 [D, L]; `noise` as helpers_anneal.annealed_run takes it) by the rule itself: the schedule
     is grown one event at a time -- annealed_run on the path so far (padded with an equal beta, whose event is the identity)
     shows the energies event s sees, `step` turns them into beta_after[s] -- and the run on the finished path is returned with
     beta_path fp32 [events + 1]. `fault`: one of FAULTS ('delta_w' resamples event s by helpers_anneal.plan's weights at d
-    instead of at the rounded pair; the others change beta_next)."""
+    instead of at the rounded pair; the others change beta_next). `trace`, `keep_probs`: as annealed_run takes them, for the
+    returned run."""
     D = int(deme)
     assert idx0.shape[0] == D
     cap = min(int(max_stages), num_steps // every)
     path = [np.float32(beta_start)]
     db_over = {}
 
-    def run(sched, T):
+    def run(sched, T, **kw):
         if fault != "delta_w":
             return ha.annealed_run(energy, idx0, wt_idx, noise, T, min_pos, max_pos, pas_length, nmut_threshold, sched, every, D, seed=seed,
-                                   chain_offset=chain_offset, allowed=allowed)
+                                   chain_offset=chain_offset, allowed=allowed, **kw)
         return _run_with_db(energy, idx0, wt_idx, noise, T, min_pos, max_pos, pas_length, nmut_threshold, sched, every, D, seed,
-                            chain_offset, allowed, db_over)
+                            chain_offset, allowed, db_over, **kw)
 
     for s in range(cap):
         r = run(np.array(path + [path[-1]], np.float32), (s + 1) * every)
         st = step(r["pre_energy"][s], path[-1], beta_end, rho, min_step, fault=fault)
         db_over[s] = st["db"]
         path.append(st["beta_next"])
-    res = run(np.array(path, np.float32), num_steps)
+    res = run(np.array(path, np.float32), num_steps, trace=trace, keep_probs=keep_probs)
     res["beta_path"] = np.array(path, np.float32)
     return res
 
 
 def _run_with_db(energy, idx0, wt_idx, noise, T, min_pos, max_pos, pas_length, nmut_threshold, sched, every, D, seed, chain_offset,
-                 allowed, db_over):
+                 allowed, db_over, **kw):
     """annealed_run whose plan of event s takes dbeta = db_over[s] where given (the 'delta_w' fault): helpers_anneal.plan is
     wrapped for the duration of the call."""
     real, calls = ha.plan, [0]
@@ -136,7 +137,7 @@ def _run_with_db(energy, idx0, wt_idx, noise, T, min_pos, max_pos, pas_length, n
     ha.plan = plan
     try:
         return ha.annealed_run(energy, idx0, wt_idx, noise, T, min_pos, max_pos, pas_length, nmut_threshold, sched, every, D, seed=seed,
-                               chain_offset=chain_offset, allowed=allowed)
+                               chain_offset=chain_offset, allowed=allowed, **kw)
     finally:
         ha.plan = real
 

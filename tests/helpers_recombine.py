@@ -81,11 +81,13 @@ def event(X, wt, sites, s, it, D, seed, chain_offset=0, fault=None):
 
 
 def recombined_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_length, nmut_threshold, every, D, seed, allowed,
-                   chain_offset=0, fault=None):
+                   chain_offset=0, fault=None, trace=False, keep_probs=False):
     """The CPU iteration of reversible mode (helpers_reversible.reversible_iteration) on explicit noise with the events of the
     rule: dict of states [T + 1, n, L], energy_history / fitness_history [T + 1, n] (row it + 1 after the event), accepted
     [T, n] (the slots' own Metropolis results) and the event records partner, lo, hi, differ, child_dist, outcome, log_ratio,
-    pre_energy, child_energy [events, n]."""
+    pre_energy, child_energy [events, n]. `trace`: also traces (the iterations' dicts; `keep_probs`: with their forward rows),
+    post_accept (states, energies per iteration, in front of the event) and the running best by the accept phase's strict rule
+    (best_idx, best_energy, best_fitness, best_step), as helpers_anneal.annealed_run keeps them."""
     import torch
     import helpers_reversible as hr
     from ppde_amd import library as dl
@@ -98,12 +100,23 @@ def recombined_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas
     e0, f0 = energy.energy(cur)
     e_hist, f_hist, states, accs = [e0.numpy()], [f0.numpy()], [cur.numpy().copy()], []
     rec = {k: [] for k in ("partner", "lo", "hi", "differ", "child_dist", "outcome", "log_ratio", "pre_energy", "child_energy")}
+    traces, post = [], []
+    best_e, best_f, best_t, best_x = e0.numpy().copy(), f0.numpy().copy(), np.zeros(n, np.int64), cur.numpy().copy()
+
+    def take_best(e_row, f_row, x_rows, t):
+        better = e_row > best_e                                              # strict: the accept phase's rule
+        best_e[better], best_f[better], best_t[better], best_x[better] = e_row[better], f_row[better], t, x_rows[better]
+
     for it in range(num_steps):
         U, q, u = noise(it)
-        out = hr.reversible_iteration(energy, cur, cur, wt, U, q, u, min_pos, max_pos, thr, allowed)
+        out = hr.reversible_iteration(energy, cur, cur, wt, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
         cur = out["idx"].clone()
         e, f = out["energy"].numpy().copy(), out["fitness"].numpy().copy()
         accs.append(out["accepted"].numpy())
+        if trace:
+            traces.append(out)
+            post.append((cur.numpy().copy(), e.copy()))
+            take_best(e, f, cur.numpy(), it + 1)
         if (it + 1) % every == 0:
             ev = event(cur.numpy(), wt.numpy(), sites, (it + 1) // every - 1, it, D, seed, chain_offset, fault)
             ce, cf = (t.numpy() for t in energy.energy(torch.as_tensor(ev["children"]).long()))
@@ -121,12 +134,16 @@ def recombined_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas
             acc = outcome == 1
             cur = torch.as_tensor(np.where(acc[:, None], ev["children"], cur.numpy())).long()
             e, f = np.where(acc, ce, e), np.where(acc, cf, f)
+            if trace:
+                take_best(e, f, cur.numpy(), it + 1)
         e_hist.append(e)
         f_hist.append(f)
         states.append(cur.numpy().copy())
     res = dict(states=np.stack(states), energy_history=np.stack(e_hist), fitness_history=np.stack(f_hist),
                accepted=np.stack(accs) if accs else np.zeros((0, n), bool))
     res.update({k: np.stack(v) if v else np.zeros((0, n)) for k, v in rec.items()})
+    if trace:
+        res.update(traces=traces, post_accept=post, best_idx=best_x, best_energy=best_e, best_fitness=best_f, best_step=best_t)
     return res
 
 
