@@ -2,7 +2,14 @@
 
 Only `tests/`, `__graft_entry__.smoke()` and `bench.py`'s `cpu_baseline` leg may import this file.
 
-PARITY UNPINNED (the ESM-2 arithmetic below; the reference's glue around it IS pinned, see the end of this header).
+WHAT PINS THE ESM-2 ARITHMETIC BELOW. The published architecture as the `transformers` package's ESM-2 port
+(`EsmForMaskedLM`, built from a bare config and filled with this project's seeded weights) implements it: forward pass,
+score and input gradient at seven geometries, among them the 150M model at full depth, frozen as
+tests/golden/esm_port_*.npz. This file with half_points=True lies within the device tests' bound (4 x the fp16 yardstick) of
+those fixtures, in fp32 it is as close to the fp64 port as the port's own fp32 run, and the fp64 reference of the device
+tests lies within 1/100 of a yardstick (tests/test_esm_port_cpu.py; the device itself: tests/test_esm_port_gpu.py).
+WHAT REMAINS OPEN: the `esm_one_hot` fork itself, and the values of the real checkpoints. (The reference's glue around the
+model is pinned to the reference, see the end of this header.)
 The reference's transformer expert (ppde/nets.py:172-240 `Transformer`, :302-312 `PottsTransformer`,
 ppde/energy.py:110-130) calls `esm_one_hot.pretrained.esm2_t30_150M_UR50D()`: a third-party dependency
 (`git+https://github.com/pemami4911/esm_one_hot.git`, unpinned, environment.yml:22) that is not in the mount, whose

@@ -2,7 +2,7 @@
 // sequences, forward AND input gradient, for a batch of chains.
 //
 // Replaces Transformer.local_score / forward (reference ppde/nets.py:219-240; the model itself is the third-party
-// `esm_one_hot` ESM-2, see oracle/esm_oracle.py for what is restated and why parity is unpinned) and the autograd
+// `esm_one_hot` ESM-2, see oracle/esm_oracle.py for what is restated and what pins it) and the autograd
 // of it in ProteinProductOfExperts.get_energy_and_grads (ppde/energy.py:110-130; minibatches of 64 there, the whole
 // population at once here: 288 GB of HBM hold every activation of a 256-chain evaluation, ~9 GB).
 //

@@ -18,6 +18,9 @@ What it does
     exponential_ -> rand reproduces those draws bit for bit — that is what lets a noise-explicit
     implementation replay the reference's trajectories.
 
+`python tests/golden/make_golden.py esm_port` is the one target that does not need the reference: it needs the
+`transformers` package (its ESM-2 port, evaluated on seeded synthetic weights; see esm_port_cases).
+
 The fixtures hold data only (inputs, seeds, expected outputs) — no reference code.
 """
 import argparse
@@ -71,7 +74,7 @@ def install_stubs():
 #   model(x_onehot [n, L, 33])['logits'],  alphabet.tok_to_idx,  alphabet.get_batch_converter()(pairs) -> (labels, strs,
 #   one-hot tokens [1, L + 2, 33] incl. <cls>/<eos>, which nets.py:186 strips).
 # The stand-in serves the BUILD'S OWN ESM-2 restatement (oracle/esm_oracle.py, fp32: on the CPU `torch.cuda.amp.autocast`
-# is disabled) on seeded synthetic weights, so the ESM arithmetic stays unpinned; what the fixtures pin is the reference's
+# is disabled) on seeded synthetic weights, so these fixtures do not pin the ESM arithmetic (esm_port_cases below does); what they pin is the reference's
 # glue around it: nets.py:193-240 (permutation, local_score, Delta against the wild type), :302-312 (PottsTransformer),
 # energy.py:110-130 (minibatch loop, gradient w.r.t. the slice) and PPDE_PAS.run on top.
 STUB_ESM = dict(layers=2, dim=128, heads=4, ffn=256, seed=5)
@@ -479,7 +482,37 @@ def script_case(root, protein, n_chains, n_iters, seed, out):
     print("wrote", out, f"({os.path.getsize(out) / 1e3:.0f} kB); reference log head:", log[:2])
 
 
+def esm_port_cases(only_check=False):
+    """The `transformers` package's ESM-2 port (tests/helpers_esm_port.py: built from a bare config, filled with the seeded
+    synthetic weights, fp64, matrices at their fp16 values) on the inputs of tests/test_transformer_stages_gpu.py: logits,
+    score and the gradient on the Potts one-hot, one file per geometry. Needs neither the reference nor any download."""
+    sys.path.insert(0, os.path.join(REPO, "oracle"))
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import helpers_esm_port as hp
+    import helpers_transformer as ht
+    tv, pv = hp.versions()
+    for geom in hp.GEOMETRIES:
+        L, layers, dim, heads, ffn, n = geom
+        st = synthetic.make_esm2_state(layers, dim, heads, ffn, seed=hp.WEIGHT_SEED)
+        wt, idx = ht.chains_like_the_parity_test(L, n)
+        port = hp.Port(st, layers, dim, heads, ffn, hp.F64, fp16_matrices=True)
+        assert port.unfilled == sorted(hp.UNFILLED), port.unfilled
+        o = port.from_onehot(idx)
+        assert torch.equal(o["logits"], port.from_ids(idx)["logits"]), "ids path differs from the embeds path"
+        out = os.path.join(HERE, f"esm_port_{hp.tag(*geom)}.npz")
+        np.savez_compressed(out, idx=idx.astype(np.uint8), wt_idx=wt, geometry=np.array(geom, np.int64), weight_seed=hp.WEIGHT_SEED,
+                            fp16_matrices=True, logits=o["logits"].numpy(), score=o["score"].numpy(), grad=o["grad"].numpy(),
+                            transformers_version=tv, torch_version=pv)
+        kb = os.path.getsize(out) / 1e3
+        assert kb < 300, (out, kb)
+        print("wrote", out, f"({kb:.0f} kB)")
+
+
 def main():
+    if "esm_port" in sys.argv[1:]:
+        torch.set_num_threads(1)
+        esm_port_cases()
+        return
     if not os.path.isdir("/root/reference/ppde"):
         sys.exit("the reference is not mounted here; fixtures can only be regenerated in the build container")
     sys.path.insert(0, "/root/reference")

@@ -3,6 +3,11 @@ oracle/esm_oracle.py, written so that every stage can be evaluated from GIVEN in
 in fp64 (the reference) or in fp32 with the fp16 rounding points of `EsmOracle(half_points=True)` (`half=True`: used ONLY
 as the yardstick -- how far an evaluation that rounds where the device rounds lies from fp64 -- never as the reference).
 
+What pins this file: its fp64 evaluation lies within 1/100 of the fp16 yardstick of an independent ESM-2, the `transformers`
+package's port on the same seeded weights (logits, score and input gradient at seven geometries, frozen as
+tests/golden/esm_port_*.npz; per layer against the live package: tests/test_esm_port_cpu.py, which also shows the faults that
+comparison rejects and the device tests could not). Open: the reference's `esm_one_hot` fork and the real checkpoints' values.
+
 The matrices enter every evaluation at their fp16 values (that quantisation is the specification: the device multiplies
 fp16 copies); biases, layer-norm gains and the rotary tables are not quantised. Stages, with the buffer ids of
 ppde_debug_transformer_read:
@@ -355,6 +360,23 @@ def score_rel(got, ref, scale=None):
     """|delta| / |s| (scale: the raw scores, where got / ref are energies against the wild type)."""
     got, ref = _t(got), _t(ref)
     return float(((got - ref).abs() / (_t(scale) if scale is not None else ref).abs()).max())
+
+
+# ---- the independent pin: tests/golden/esm_port_<tag>.npz hold what the `transformers` package's ESM-2 port computes (fp64, matrices
+# at their fp16 values) on make_esm2_state(seed=ESM_PORT_WEIGHT_SEED) and chains_like_the_parity_test(L, n); see tests/helpers_esm_port.py
+#                     (L, layers, dim, heads, ffn, chains)
+ESM_PORT_GEOMETRIES = [(17, 2, 128, 4, 256, 3),          # short sequence
+                       (129, 2, 128, 4, 256, 3),         # one row past 128
+                       (237, 2, 96, 4, 256, 2),          # head width 24, pad keys
+                       (129, 2, 256, 4, 512, 2),         # head width 64
+                       (104, 2, 480, 20, 1920, 2),       # 35M widths
+                       (256, 2, 128, 2, 256, 2),         # the longest sequence, rotary to position 255
+                       (104, 30, 640, 20, 2560, 2)]      # the 150M model at its full depth
+ESM_PORT_WEIGHT_SEED = 3
+
+
+def esm_port_tag(L, layers, dim, heads, ffn=None, n=None):
+    return f"{L}x{layers}x{dim}x{heads}"
 
 
 def chains_like_the_parity_test(L, n, seed=3):

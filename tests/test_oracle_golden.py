@@ -110,8 +110,8 @@ def test_real_shipped_weights(name, protein, tmp_path):
 def test_transformer_product_of_experts_glue():
     """energy.py:110-130 / nets.py:193-240, :302-312 as the REFERENCE ran them over the stand-in ESM-2 (ops_tfpoe_toy.npz):
     the energy holds + lamda * fit, grad_x does NOT hold lamda * d fit/dx (gradient w.r.t. the minibatch slice, :125), the
-    Potts -> ESM permutation, the wild type's score. The ESM arithmetic itself stays unpinned (the stand-in IS this
-    repository's restatement); the glue around it is what this pins."""
+    Potts -> ESM permutation, the wild type's score. The ESM arithmetic itself is not pinned HERE (the stand-in IS this
+    repository's restatement; tests/test_esm_port_cpu.py pins it to an independent port); the glue around it is what this pins."""
     import esm_oracle as eo
     fx = load("ops_tfpoe_toy.npz")
     idx = torch.as_tensor(fx["idx"].astype(np.int64))

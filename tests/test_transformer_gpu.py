@@ -1,7 +1,8 @@
 """GPU parity of the transformer unsupervised expert (BASELINE config 5) against oracle/esm_oracle.py.
 
-PARITY UNPINNED: the reference's model is the third-party esm_one_hot ESM-2 with hub weights, neither of which is in
-the mount; the oracle restates the published architecture on self-generated seeded weights (see its header).
+The reference's model is the third-party esm_one_hot ESM-2 with hub weights, neither of which is in the mount; the oracle
+restates the published architecture on self-generated seeded weights, and is pinned to an independent ESM-2 port on those
+weights (see its header; tests/test_esm_port_cpu.py). The fork itself and the real checkpoints' values stay open.
 Tolerances (fp16 matmuls with fp32 accumulation on both sides, fp16 tensors at the same places): scores
 2e-3 * (1 + |s|) ... the observed ratios are appended to gpurun_out/parity_observed.json."""
 import os
@@ -139,7 +140,7 @@ def test_product_of_experts_with_transformer_and_sampler(L, win):
 # ---- the reference's transformer branches (energy.py:110-130) ---------------------------------------------------
 # Fixtures: the REFERENCE's ProteinProductOfExperts / PPDE_PAS.run over a stand-in for the absent esm_one_hot that serves
 # this repository's own ESM-2 restatement in fp32 (tests/golden/make_golden.py). They pin the glue (what is summed into
-# the energy, what the gradient is taken of, minibatching, the sampler on top); the ESM arithmetic stays unpinned, and
+# the energy, what the gradient is taken of, minibatching, the sampler on top); the ESM arithmetic is pinned elsewhere (tests/test_esm_port_*.py), and
 # the HIP path computes it in fp16 where the CPU reference had fp32, hence the tolerances: scores 2e-3 * (1 + |s|),
 # gradients 3e-2 * max|g|; draws / accept bits equal except on flagged near-ties of the oracle's own decision.
 def _tfpoe_model(fx, unsup):
