@@ -66,7 +66,8 @@ typedef enum {
                                 * logit 86.6 or more below mref (the normaliser falls below 2^-125: a chain at the mutation cap or
                                 * a state outside the library whose best admissible move lies ~23 or more below the current
                                 * letters once the gradient's spread reaches 128) or a logit more than 88.7 above it (a spread
-                                * beyond 2 * (64 + 88)); the reference, which reduces a maximum per row, carries on there */
+                                * beyond 2 * (64 + 88)); the reference, which reduces a maximum per row, carries on there.
+                                * ppde_model_set_transformer: the wild type's score is not finite on the weights given */
 } ppde_status;
 
 typedef struct ppde_model ppde_model;
@@ -107,7 +108,21 @@ int ppde_model_set_cnn(ppde_model* m, int n_nets, int C, int K, int F,
  * facebookresearch/esm's ESM2: per-layer arrays have n_layers entries. Written for head widths 24, 32 and 64
  * (esm2_t12_35M: dim 480, 20 heads, ffn 1920; esm2_t30_150M: 640, 20, 2560; esm2_t33_650M: 1280, 20, 5120), ffn a multiple
  * of 128, L <= 256. Also evaluates the wild
- * type's score. */
+ * type's score.
+ * Range. Every activation and activation gradient is an fp16 tensor (normal range 6.1e-5 .. 65504, subnormals kept). What that
+ * supports, measured by rescaling seeded weights against fp64 (tests/test_transformer_range_{cpu,gpu}.py), in
+ * terms one can read off a checkpoint's activations: the residual stream (entries of order 1 at unit scale) times 2^-12 .. 2^12,
+ * and no entry of it beyond 65504 (at 2^14 it is lost); q against k (entries of order 0.1 and 1) times 2^-12 .. 2^13 in either
+ * direction; v against out_proj times 2^-14 .. 2^13; layer-norm outputs (gains) times 2^-14 .. 2^11 with the matrices behind them
+ * scaled back: within these the distance from fp64 stays within twice what it is at unit scale (gradient 9e-4 of its largest row,
+ * d embedding 1.6e-3). Logits up to 80 in magnitude and one stream channel 8 times the others are held at 5e-3 and 2.5e-3 of the
+ * gradient; attention rows with one dominant key (scores of order 16) at 8e-2 .. 1.3e-1, which is fp16's rounding of such scores
+ * and not the kernels': there the gradient has one digit.
+ * Refusals, both leaving the expert that was there answering bit for bit (the new one is built completely, the wild type's score
+ * included, before the old one is let go): PPDE_ERR_INVALID naming tensor and layer when a parameter is not finite in fp32 or a
+ * matrix entry is not finite once rounded to fp16 (|w| >= 65520), before the device is touched; PPDE_ERR_NUMERIC when the wild
+ * type's score comes out non-finite (an fp16 activation overflowed on these weights: every energy would be NaN). A chain whose own
+ * activations overflow returns a non-finite energy and gradient and leaves the other chains of its batch bit for bit as they are. */
 typedef struct {
     const float* embed;                 /* embed_tokens.weight [33][dim] (also the tied LM-head projection) */
     const float* const* q_w; const float* const* q_b;       /* layers.i.self_attn.{q,k,v,out}_proj.{weight [dim][dim], bias} */

@@ -658,22 +658,64 @@ int ppde_model_set_transformer(ppde_model* m, int n_layers, int dim, int heads, 
            "the attention kernels are written for head widths 24, 32 and 64 (ESM-2 35M: 480 / 20, 150M: 640 / 20, 650M: 1280 / 20)");
     ARGCHK(dim % 8 == 0 && ffn % 128 == 0 && dim <= TF_LN_MAXD, "dim must be a multiple of 8 (<= 1536), ffn a multiple of 128");
     ARGCHK(m->L <= TF_TP_MAX, "the transformer expert handles sequences of up to 256 residues");
+    // every parameter finite in fp32, every matrix entry finite at the fp16 value the device multiplies (|w| < 65520):
+    // checked before anything is touched, so that a refusal leaves the expert that was there
+    {
+        int rc = PPDE_OK;
+        auto finite = [&](const char* name, int layer, const float* v, size_t count, bool matrix) {
+            if (rc != PPDE_OK) return;
+            if (!v) { rc = fail(PPDE_ERR_INVALID, std::string("null transformer parameter ") + name); return; }
+            for (size_t i = 0; i < count; ++i) {
+                const bool ok = matrix ? std::isfinite((float)(half_t)v[i]) : std::isfinite(v[i]);
+                if (ok) continue;
+                rc = fail(PPDE_ERR_INVALID, std::string("transformer parameter ") + name + (layer >= 0 ? " of layer " + std::to_string(layer) : std::string())
+                                                + ": entry " + std::to_string(i) + (std::isfinite(v[i]) ? " is beyond fp16's largest value 65504, the format the matrices are multiplied in"
+                                                                                                        : " is not finite"));
+                return;
+            }
+        };
+        const size_t D = (size_t)dim, F = (size_t)ffn;
+        finite("embed_tokens.weight", -1, w->embed, (size_t)TF_VOCAB * D, true);
+        const float* const* per_layer[] = {w->q_w, w->q_b, w->k_w, w->k_b, w->v_w, w->v_b, w->o_w, w->o_b, w->ln1_w, w->ln1_b, w->ln2_w, w->ln2_b,
+                                           w->fc1_w, w->fc1_b, w->fc2_w, w->fc2_b};
+        for (auto p : per_layer) ARGCHK(p, "null per-layer transformer parameter array");
+        for (int l = 0; l < n_layers; ++l) {
+            finite("self_attn.q_proj.weight", l, w->q_w[l], D * D, true);   finite("self_attn.q_proj.bias", l, w->q_b[l], D, false);
+            finite("self_attn.k_proj.weight", l, w->k_w[l], D * D, true);   finite("self_attn.k_proj.bias", l, w->k_b[l], D, false);
+            finite("self_attn.v_proj.weight", l, w->v_w[l], D * D, true);   finite("self_attn.v_proj.bias", l, w->v_b[l], D, false);
+            finite("self_attn.out_proj.weight", l, w->o_w[l], D * D, true); finite("self_attn.out_proj.bias", l, w->o_b[l], D, false);
+            finite("self_attn_layer_norm.weight", l, w->ln1_w[l], D, false); finite("self_attn_layer_norm.bias", l, w->ln1_b[l], D, false);
+            finite("final_layer_norm.weight", l, w->ln2_w[l], D, false);     finite("final_layer_norm.bias", l, w->ln2_b[l], D, false);
+            finite("fc1.weight", l, w->fc1_w[l], F * D, true);               finite("fc1.bias", l, w->fc1_b[l], F, false);
+            finite("fc2.weight", l, w->fc2_w[l], D * F, true);               finite("fc2.bias", l, w->fc2_b[l], D, false);
+        }
+        finite("emb_layer_norm_after.weight", -1, w->final_ln_w, D, false);  finite("emb_layer_norm_after.bias", -1, w->final_ln_b, D, false);
+        finite("lm_head.dense.weight", -1, w->head_dense_w, D * D, true);    finite("lm_head.dense.bias", -1, w->head_dense_b, D, false);
+        finite("lm_head.layer_norm.weight", -1, w->head_ln_w, D, false);     finite("lm_head.layer_norm.bias", -1, w->head_ln_b, D, false);
+        finite("lm_head.bias", -1, w->head_bias, (size_t)TF_VOCAB, false);
+        if (rc) return rc;
+    }
     HIPCHK(hipSetDevice(m->device));
-    delete m->tf; m->tf = nullptr;
-    delete m->s_tfw; m->s_tfw = nullptr;
-    hipFree(m->s_gradT); hipFree(m->s_tfE); m->s_gradT = m->s_tfE = nullptr; m->s_tf_n = 0;
+    // the new expert is built completely, the wild type's score included, before the old one is let go
     TfModel* t = new TfModel();
     t->layers = n_layers; t->Dr = dim; t->D = (dim + 127) & ~127; t->H = heads; t->F = ffn; t->HD = dim / heads;
     int rc = tf_build_model(t, m->L, w);
     if (rc) { delete t; return rc; }
     // wild type's local score (nets.py:188) with the kernels that evaluate every other state
-    TfWork wk;
-    DevBuf<float> sc;
-    if ((rc = tf_alloc_work(t, &wk, 1)) == PPDE_OK && sc.alloc(1) != hipSuccess) rc = fail(PPDE_ERR_HIP, "allocation failed");
-    if (rc == PPDE_OK) rc = tf_eval(t, &wk, m->d_wt, m->g.Ls, m->g.sh, 1, sc.p, nullptr, 0);
-    if (rc == PPDE_OK && hipMemcpy(&t->wt_score, sc.p, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PPDE_ERR_HIP, "copy failed");
+    {
+        TfWork wk;
+        DevBuf<float> sc;
+        if ((rc = tf_alloc_work(t, &wk, 1)) == PPDE_OK && sc.alloc(1) != hipSuccess) rc = fail(PPDE_ERR_HIP, "allocation failed");
+        if (rc == PPDE_OK) rc = tf_eval(t, &wk, m->d_wt, m->g.Ls, m->g.sh, 1, sc.p, nullptr, 0);
+        if (rc == PPDE_OK && hipMemcpy(&t->wt_score, sc.p, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = fail(PPDE_ERR_HIP, "copy failed");
+    }
+    if (rc == PPDE_OK && !std::isfinite(t->wt_score))
+        rc = fail(PPDE_ERR_NUMERIC, "the wild type's transformer score is not finite: an fp16 activation overflowed 65504 on these weights "
+                                    "(see the supported range of the transformer expert in ppde_hip.h); every energy would be NaN");
     if (rc) { delete t; return rc; }
-    m->tf = t;
+    delete m->tf; m->tf = t;
+    delete m->s_tfw; m->s_tfw = nullptr;
+    hipFree(m->s_gradT); hipFree(m->s_tfE); m->s_gradT = m->s_tfE = nullptr; m->s_tf_n = 0;
     return PPDE_OK;
 }
 

@@ -1926,12 +1926,14 @@ __global__ __launch_bounds__(256) void tf_score(const half_t* __restrict__ logit
         float s = 0.f;
 #pragma unroll
         for (int k = 0; k < TF_VOCAB; ++k) s += expf(v[k] - mx);
-        const float lse = logf(s) + mx;
+        // log_softmax as (v - mx) - log s, never v - (log s + mx): the sum log s + mx is rounded at the logits' magnitude (2^-18 at
+        // 60), and where a row is peaked -- softmax 1 - 1e-5 at the token -- that is half of 1 - softmax, the whole of d logits there
+        const float ls = logf(s);
         const int tok = perm[min((int)idx[(size_t)b * Ls + sh + l], 19)];
         half_t* dl = dlogits ? dlogits + m * TF_VOCAB_PAD : nullptr;
 #pragma unroll
         for (int k = 0; k < TF_VOCAB; ++k) {
-            const float lp = v[k] - lse;
+            const float lp = (v[k] - mx) - ls;
             if (k == tok) part += lp;
             if (dl) dl[k] = (half_t)((k == tok ? 1.0f : 0.0f) - expf(lp));
             const int aa = pinv[k];                            // Potts letter of token k, or -1 (static index into v: no scratch)

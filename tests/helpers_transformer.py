@@ -32,7 +32,9 @@ Rounding points of the half evaluation beyond EsmOracle's, each one the device's
   * the energy is the score minus the wild type's, subtracted in fp32 (stage E's `wt_score`).
 
 `mut` (a `Mut`) plants ONE fault of the kind a kernel could have into an evaluation; tests/test_transformer_stages_cpu.py
-shows that each lands far outside the bound the GPU tests apply.
+shows that each lands far outside the bound the GPU tests apply. Four of them (attn_ftz, lse_no_max, lse_plus_max,
+online_no_rescale) are invisible on make_esm2_state's magnitudes and seen only on rescaled weights:
+tests/test_transformer_range_cpu.py.
 
 The last section restates the persistent GEMMs' tile walk (which output tile a workgroup computes as its first, second, ...)
 from the kernels' integer formulas, the GEMM shapes of one evaluation and the row padding: what
@@ -135,6 +137,28 @@ class _SoftmaxRowsumCut(torch.autograd.Function):
         return p * (dp - (dp * p)[..., : ctx.keep].sum(-1, keepdim=True)), None
 
 
+FP16_MIN_NORMAL = 2.0 ** -14
+
+
+def _ftz(t):
+    """fp16 flush-to-zero: magnitudes below the smallest normal become 0 (and pass no gradient)."""
+    return torch.where(t.abs() >= FP16_MIN_NORMAL, t, torch.zeros_like(t))
+
+
+def _softmax_online_no_rescale(s, rise=11.0, tile=16):
+    """softmax over key tiles of 16 with a running maximum, whose accumulated weights are NOT rescaled at a tile where the
+    maximum rises by more than `rise` (they are at every smaller rise: at such rows it is softmax up to rounding)."""
+    m = torch.full_like(s[..., :1], -math.inf)
+    total, parts = torch.zeros_like(m), []
+    for j in range(0, s.shape[-1], tile):
+        sj = s[..., j:j + tile]
+        mj = torch.maximum(m, sj.detach().amax(-1, keepdim=True))
+        f = torch.where(mj - m > rise, torch.ones_like(m), torch.exp(m - mj))
+        parts = [pp * f for pp in parts] + [torch.exp(sj - mj)]
+        total, m = total * f + parts[-1].sum(-1, keepdim=True), mj
+    return torch.cat(parts, -1) / total
+
+
 class _GeluStoredGrad(torch.autograd.Function):
     """GELU of an fp16-valued pre-activation, rounded to fp16; the backward multiplies the fp16 gradient by GELU' ROUNDED TO
     fp16, which is what the forward GEMM stores and the backward GEMM's epilogue reads (tf_gelu_both, TF_EPI_GELU_BWD)."""
@@ -198,6 +222,9 @@ def attention(P, qkv, dtype=F64, half=False, mut=None):
         qr, kr = _pick(mut, _rotary(q, dtype, half, TAIL), qr), _pick(mut, _rotary(k, dtype, half, TAIL), kr)
     if name == "drot_sign_dk":
         kr = _pick(mut, _rotary(k, dtype, half, wrong_grad_sign=True), kr)
+    if name == "attn_ftz":                                         # fp16 subnormals of the MFMA operands read as zero: q, k, v here
+        st = lambda t: t + (_ftz(t) - t).detach()                  # (values only: their gradients are products of other operands)
+        qr, kr, v = _pick(mut, st(qr), qr), _pick(mut, st(kr), kr), _pick(mut, st(v), v)
     s = qr @ kr.transpose(-1, -2)
     if name == "dk_no_tail":                                       # dK lacks the last query tile's contribution
         s = _pick(mut, torch.cat((s[..., :TAIL, :], qr[..., TAIL:, :] @ kr.detach().transpose(-1, -2)), -2), s)
@@ -211,9 +238,13 @@ def attention(P, qkv, dtype=F64, half=False, mut=None):
         p = _pick(mut, pm, torch.softmax(s, -1))
     elif name == "softmax_bwd_rowsum_no_pad_tile":
         p = _pick(mut, _SoftmaxRowsumCut.apply(s, L // 16 * 16), torch.softmax(s, -1))
+    elif name == "online_no_rescale":                              # running maximum over key tiles, no rescaling at a rise > 11
+        p = _pick(mut, _softmax_online_no_rescale(s), torch.softmax(s, -1))
     else:
         p = torch.softmax(s, -1)
     p = _h(p, half)
+    if name == "attn_ftz":                                         # probabilities below 2^-14 are zero in P V and in the backward
+        p = _pick(mut, _ftz(p), p)
     ctx = p @ v
     if name == "dv_no_tail":
         ctx = _pick(mut, torch.cat((ctx[..., :TAIL, :], p[..., TAIL:, :] @ v.detach()), -2), ctx)
@@ -260,7 +291,7 @@ def stage_d(P, xlast, dtype=F64, half=False, mut=None, gelu_grad_fp16=True):
     return _h(_h(y, half) @ P.mat("embed_tokens.weight", dtype).t() + P.vec("lm_head.bias", dtype), half)
 
 
-def stage_e(P, logits, idx, dtype=F64, half=False, wt_score=None):
+def stage_e(P, logits, idx, dtype=F64, half=False, wt_score=None, mut=None):
     """logits [n, L, 33], idx [n, L] Potts letters -> (score [n], d score / d logits [n, L, 33]). With wt_score (the
     device's own wild-type score, an input like the tokens) the first is the energy score - wt_score, which the half
     evaluation subtracts in fp32 as the device does. The score is ONE number per chain, and in fp32 its distance from fp64
@@ -268,6 +299,13 @@ def stage_e(P, logits, idx, dtype=F64, half=False, wt_score=None):
     order and one that does not depend on the host's reduction kernels (the device's fixed tree is another order of the
     same sum)."""
     lp = torch.log_softmax(logits.to(dtype), -1)
+    if mut is not None and mut.name == "lse_no_max":               # log-sum-exp without the row maximum subtracted
+        lg = logits.to(dtype)
+        lp = lg - lg.exp().sum(-1, keepdim=True).log()
+    if mut is not None and mut.name == "lse_plus_max":             # v - (log s + max): the sum rounded at the logits' magnitude
+        lg = logits.to(dtype)                                      # (what tf_score did until the range tests ran it at logits of 60)
+        mx = lg.amax(-1, keepdim=True)
+        lp = lg - ((lg - mx).exp().sum(-1, keepdim=True).log() + mx)
     onehot = torch.nn.functional.one_hot(P.perm[torch.as_tensor(np.asarray(idx)).long()], 33).to(dtype)
     rows = (onehot * lp).sum(-1)                                   # [n, L]: one non-zero term each
     if half:

@@ -49,6 +49,24 @@ int sequence(int L, int Lp, int win, bool with_tf, bool verbose, int tf_dim = 12
         TRY(ppde_model_set_transformer(m, layers, dim, heads, ffn, &w));
         float s = 0.f;
         TRY(ppde_model_get_transformer_wt_score(m, &s));
+        // a matrix entry that is inf once rounded to fp16, a NaN bias, an inf gain: each refused naming the tensor, before the runtime
+        // is touched, and the expert that is there stays (the evaluations below use it)
+        float& big = f2w.store[1][7];
+        const float keep = big;
+        big = 65520.f;
+        EXPECT_INVALID(ppde_model_set_transformer(m, layers, dim, heads, ffn, &w), "fc2.weight of layer 1");
+        big = -65519.f;                                                              // rounds to -65504: accepted
+        TRY(ppde_model_set_transformer(m, layers, dim, heads, ffn, &w));
+        big = keep;
+        const float keep_b = qb.store[0][3];
+        qb.store[0][3] = NAN;
+        EXPECT_INVALID(ppde_model_set_transformer(m, layers, dim, heads, ffn, &w), "q_proj.bias of layer 0");
+        qb.store[0][3] = keep_b;
+        const float keep_g = hlw[0];
+        hlw[0] = INFINITY;
+        EXPECT_INVALID(ppde_model_set_transformer(m, layers, dim, heads, ffn, &w), "lm_head.layer_norm.weight");
+        hlw[0] = keep_g;
+        TRY(ppde_model_get_transformer_wt_score(m, &s));
     }
     TRY(ppde_idx_to_onehot(m, idx.data(), n, onehot.data(), nullptr));
     TRY(ppde_onehot_to_idx(m, onehot.data(), n, back.data(), nullptr));

@@ -20,11 +20,12 @@ from ppde_amd.encoding import seqs_to_idx
 from test_hip_parity import observed
 
 
-def _model(L, layers, dim, heads, ffn, seed=3, with_cnn=False, potts=None):
+def _model(L, layers, dim, heads, ffn, seed=3, with_cnn=False, potts=None, state=None):
+    """`state`: the transformer's weights, where they are not make_esm2_state's of `seed` (the rescaled ones of the range tests)."""
     from ppde_amd.energy import HipModel
     rng = np.random.default_rng(seed)
     wt = rng.integers(0, 20, L).astype(np.uint8)
-    st = synthetic.make_esm2_state(layers, dim, heads, ffn, seed=seed)
+    st = synthetic.make_esm2_state(layers, dim, heads, ffn, seed=seed) if state is None else state
     m = HipModel(wt, "cuda:0")
     if potts:
         J, h = synthetic.make_potts(potts[1], seed=seed)

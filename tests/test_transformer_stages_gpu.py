@@ -56,10 +56,11 @@ def read_buffers(m, L, layers, dim, ffn, n):
     return b
 
 
-def device_buffers(L, layers, dim, heads, ffn, n):
-    """One evaluation with the gradient on the device; every buffer the checks read, pad columns included."""
+def device_buffers(L, layers, dim, heads, ffn, n, state=None):
+    """One evaluation with the gradient on the device; every buffer the checks read, pad columns included. `state`: the weights,
+    where they are not make_esm2_state(seed=3)."""
     from test_transformer_gpu import _model
-    m, wt, _, _ = _model(L, layers, dim, heads, ffn)
+    m, wt, _, _ = _model(L, layers, dim, heads, ffn, state=state)
     wt2, idx = ht.chains_like_the_parity_test(L, n)
     assert np.array_equal(wt, wt2)
     e, _, g = m.energy_grad(torch.as_tensor(idx).cuda(), 4)
@@ -84,11 +85,12 @@ def _strip_pads(b, dim, layers):
     return {k: (torch.as_tensor(v) if k not in ("idx", "wt_score") else v) for k, v in out.items()}
 
 
-def check_stages(tag, L, layers, dim, heads, ffn, raw, stages=True, chains=None, family="tfstage"):
+def check_stages(tag, L, layers, dim, heads, ffn, raw, stages=True, chains=None, family="tfstage", state=None):
     """Apply every check to one device evaluation; the assertion comes last so that a failure reports all of its ratios.
     `chains`: check these chains of the evaluation only (every buffer, idx, e and grad sliced on the chain axis; the first
-    one must be the wild type); within them no row, head or stage is exempt."""
-    P = ht.Params(synthetic.make_esm2_state(layers, dim, heads, ffn, seed=3), layers, dim, heads)
+    one must be the wild type); within them no row, head or stage is exempt. `state`: the weights the device was given, where
+    they are not make_esm2_state(seed=3); reference and yardstick are evaluated on them."""
+    P = ht.Params(synthetic.make_esm2_state(layers, dim, heads, ffn, seed=3) if state is None else state, layers, dim, heads)
     if chains is not None:
         raw = {k: (v if k == "wt_score" else np.ascontiguousarray(np.asarray(v)[list(chains)])) for k, v in raw.items()}
     b = _strip_pads(raw, dim, layers)
