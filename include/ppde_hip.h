@@ -423,7 +423,8 @@ int ppde_chains_annealing_read_betas(ppde_chains* c, int first_event, int n_even
  *     `which`); E', f' = the proposal slot's energy and fitness;
  *   decision, in fp32 and in this order, E_a, E_b = the post-accept energies (history row it + 1): d = (E'_a - E_a) + (E'_b - E_b);
  *     outcome 3: an E' is not finite (rejected); 2: a mutation cap is set and a child_dist >= nmut_threshold (rejected, never through
- *     u); 1: expf(d) >= u (accepted); 0: rejected by u. A pair with differ = 0 takes the same path (d = 0: accepted);
+ *     u); 4: forbidden patterns are set and a child is not free (rejected, never through u; ppde_chains_set_forbidden_patterns);
+ *     1: expf(d) >= u (accepted); 0: rejected by u. A pair with differ = 0 takes the same path (d = 0: accepted);
  *   on acceptance each of the two slots takes from its child everything the next iteration and the observers read for a chain: the
  *     state (and its transposed copy), the energy, fitness and mutation count it continues from, its gradient row under gradient
  *     reuse, row it + 1 of both histories and of the random trajectory for the recorded chain, the running best by the accept
@@ -456,6 +457,55 @@ int ppde_chains_recombination_shape(ppde_chains* c, int32_t* deme, int32_t* n_op
 int ppde_chains_recombination_read(ppde_chains* c, int first_event, int n_events,
                                    int32_t* partner, int32_t* lo, int32_t* hi, int32_t* differ, int32_t* child_dist,
                                    uint8_t* outcome, float* log_ratio, float* pre_energy, float* child_energy);
+
+/* Forbidden sequence patterns (off by default; needs reversible mode): "never produce this short pattern anywhere" as one more
+ * indicator in the target. The reversible chains' stationary law becomes exp(beta E(x)) 1[dist(x) < thr] 1[x free] / Z (beta under
+ * tempering or annealing). The proof is the mutation cap's: a Metropolis step that explicitly rejects every proposal outside a
+ * set, from a state inside it, is reversible with respect to the law restricted to that set.
+ *   patterns: M of them, 1 <= M <= 32; pattern m is length[m] elements, 1 <= length[m] <= 8, element j = element[m][j], a non-empty
+ *     set of letters as a 20-bit word (bit k = letter k of ACDEFGHIKLMNPQRSTVWY, the design library's convention). A state x
+ *     matches pattern m at start p when 0 <= p <= L - length[m] and x[p + j] is in element j for every j. Windows run over the
+ *     WHOLE sequence [0, L): frozen residues and residues outside [min_pos, max_pos] are context;
+ *   native sites: allow_native != 0 exempts every (m, p) at which the WILD TYPE matches, whatever the chain puts there later;
+ *     allow_native = 0 exempts nothing. active[p] bit m = pattern m is checked at start p: p + length[m] <= L and (m, p) not exempt.
+ *     x is FREE when no active (m, p) matches;
+ *   accept phase: a proposal y that is not free is rejected explicitly, next to the cap's dist(y) < thr, never through the test
+ *     against u. It records what a cap rejection records: accept bit 0, the current energy in row it + 1; the trace's log_acc stays
+ *     the computed value. The forward path, the Philox counters and the variates consumed do not change. Only y is checked, not
+ *     the intermediate states of its path;
+ *   initial states: every one must be free: ppde_chains_init with one that is not is PPDE_ERR_INVALID and names the chain, the
+ *     pattern and the position. With allow_native = 0 and a wild type that matches, the setter succeeds and leaves a note that
+ *     names the pattern and the position in ppde_last_error (the run is legal from other free states);
+ *   recombination: a pair with a child that is not free is rejected with outcome 4, checked after the non-finite energy (3) and
+ *     the cap (2) and before u. A run without patterns never writes 4;
+ *   tempering's swap and annealing's selection move free states only and do not change. Both rng_modes, every `which` and
+ *     n_streams > 1 work (one veto launch per sub-population on its stream);
+ *   vetoes int64 [n][M]: vetoes[b][m] = the iteration proposals of chain b that were not free and whose lowest matching active
+ *     pattern was m, counted whether or not the proposal would otherwise have been accepted. Recombination's children are not
+ *     counted (their record is outcome 4). ppde_chains_init zeroes them.
+ * One more kernel per iteration (ppde_amd/csrc/motif.h: k_motif_veto, one wave per chain, on the proposal slot behind its expert
+ * evaluation and in front of the accept or fused launch) and one inside a recombination event (between the children and their
+ * evaluation). A run without the mode enqueues nothing new and computes the bits it computed before. Valid between
+ * ppde_chains_create and ppde_chains_init, before or after ppde_chains_set_library; NULL clears it. PPDE_ERR_INVALID with a message,
+ * the object unchanged: after init; reversible mode not on (hence with paper_results); n_patterns outside 1..32; a length outside
+ * 1..8 or above L; an element inside its pattern's length that is 0 or has a bit >= 20 set; no active (m, p) at all. While it is
+ * set, ppde_chains_set_reversible(c, 0) is PPDE_ERR_INVALID. A failed allocation is PPDE_ERR_HIP and leaves nothing half-set. */
+typedef struct {
+    int32_t n_patterns;         /* M, 1..32 */
+    const int32_t* length;      /* [M] 1..8 */
+    const uint32_t* element;    /* [M][8]; words behind a pattern's length are ignored */
+    int32_t allow_native;
+} ppde_motif_config;
+int ppde_chains_set_forbidden_patterns(ppde_chains* c, const ppde_motif_config* cfg /* NULL clears */);
+/* M, allow_native and the active words. Any pointer may be NULL. PPDE_ERR_INVALID without the mode. */
+int ppde_chains_forbidden_shape(ppde_chains* c, int32_t* n_patterns, int32_t* allow_native, uint32_t* active /* [L] */);
+/* The counters so far. Synchronises. PPDE_ERR_INVALID without the mode or before init. */
+int ppde_chains_forbidden_read(ppde_chains* c, int64_t* vetoes /* [n][M] */);
+/* The scan on its own (stateless): the same device function over n rows of residue indices [n][L] on the device, against the
+ * model's wild type. first_pattern[i] = the lowest active pattern row i matches and first_pos[i] its lowest start position; -1 / -1
+ * for a free row. Synchronises the stream. The config is checked as by the setter. */
+int ppde_motif_scan(ppde_model* m, const ppde_motif_config* cfg, const uint8_t* idx_dev, int n, int32_t* first_pattern_dev,
+                    int32_t* first_pos_dev, void* stream);
 
 /* Recorder (off by default): thinned samples of the population and per-site letter counts, written on the device inside the
  * iteration loop (one more kernel behind the accept phase -- behind the swap, with tempering -- of every iteration of a recording

@@ -60,6 +60,12 @@ class RecombineConfig(C.Structure):
     _fields_ = [("deme", C.c_int32), ("every", C.c_int32)]
 
 
+class MotifConfig(C.Structure):
+    """ppde_motif_config (include/ppde_hip.h)."""
+    _fields_ = [("n_patterns", C.c_int32), ("length", C.POINTER(C.c_int32)), ("element", C.POINTER(C.c_uint32)),
+                ("allow_native", C.c_int32)]
+
+
 class TfWeights(C.Structure):
     """ppde_tf_weights (include/ppde_hip.h): host pointers to ESM-2's fp32 parameters."""
     _PER_LAYER = ("q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "o_w", "o_b", "ln1_w", "ln1_b", "ln2_w", "ln2_b",
@@ -105,6 +111,10 @@ SIGNATURES = {
     "ppde_chains_set_recombination": (_i, [_p, C.POINTER(RecombineConfig)]),
     "ppde_chains_recombination_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ppde_chains_recombination_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "ppde_chains_set_forbidden_patterns": (_i, [_p, C.POINTER(MotifConfig)]),
+    "ppde_chains_forbidden_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _p]),
+    "ppde_chains_forbidden_read": (_i, [_p, _p]),
+    "ppde_motif_scan": (_i, [_p, C.POINTER(MotifConfig), _p, _i, _p, _p, _p]),
     "ppde_chains_set_recorder": (_i, [_p, C.POINTER(RecordConfig)]),
     "ppde_chains_recorder_shape": (_i, [_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "ppde_chains_recorder_read": (_i, [_p, _i, _i, _p, _p, _p, _p, _p]),

@@ -46,6 +46,16 @@ struct Recombination {
     bool event(int it) const { return (it + 1) % every == 0; }   // (it: absolute, or relative to a multiple of every)
 };
 
+// forbidden patterns (ppde_chains_set_forbidden_patterns)
+struct Forbidden {
+    int M = 0, allow_native = 1;                 // patterns; the wild type's own matches are exempt
+    std::vector<uint32_t> active, pattern;       // [L] bit m: pattern m is checked at that start; [32][8] element words (motif.h)
+    DevBuf<uint32_t> active_dev, pattern_dev;
+    DevBuf<uint8_t> veto;                        // [n] the pending proposal (or child) is not free
+    DevBuf<long long> vetoes;                    // [n][M] iteration proposals vetoed, by lowest matching pattern
+    bool on() const { return veto.p != nullptr; }
+};
+
 // recorder (ppde_chains_set_recorder)
 struct Recorder {
     ppde_record_config cfg{};
@@ -141,6 +151,7 @@ struct ppde_chains {
     Tempering temper;
     Annealing anneal;
     Recombination recomb;
+    Forbidden forbid;
     Recorder recorder;
     PairCounts pairs;
     Archive archive;
@@ -187,6 +198,7 @@ static PasArgs chain_args(const ppde_chains* c) {
     a.err_flag = c->err_flag;
     a.dbg = c->dbg;
     a.allowed = c->allowed;
+    a.veto = c->forbid.veto;
     a.beta = c->anneal.on() ? c->anneal.beta.p : c->temper.beta.p; a.rung = c->temper.rung; a.slot = c->temper.slot; a.swap_attempts = c->temper.swap_attempts; a.swap_accepts = c->temper.swap_accepts;
     a.rung_hist = c->temper.rung_hist; a.n_rungs = c->temper.n_rungs; a.swap_every = c->temper.swap_every;
     return a;
@@ -308,6 +320,7 @@ static int read_state_rows(ppde_chains* c, const uint8_t* src, size_t units, siz
 // fresh starts).
 #include "tempering_host.h"
 #include "anneal_host.h"
+#include "motif_host.h"
 #include "recombine_host.h"
 #include "record_host.h"
 #include "pairs_host.h"
@@ -400,6 +413,7 @@ static int launch_chain_kernel(ppde_chains* c, ChainKernel which, const PasArgs&
 // Re-evaluating mode: EG(x) P EG(y) A per iteration. Reuse mode: P, then EG(y) + fused [accept | next propose].
 // Tempering: [EG(x)] P EG(y) A S, never fused: the next proposal must see the post-swap beta, the swap the post-accept energy.
 // Annealing: the same flow with the two selection kernels in the swap's place.
+// Forbidden patterns: one veto launch on the proposal slot in front of every accept or fused launch, under both policies.
 // Recombination: on the host-chosen event iterations the event's three launches follow a plain accept kernel, and the next iteration
 // starts with a plain propose launch (nothing fuses across an event); everywhere else the flow is that of the run without the mode.
 static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int first_local, int count, const int* U,
@@ -423,6 +437,7 @@ static int enqueue_iterations(ppde_chains* c, int k, const int* it_base, int fir
         }
         // energy and gradient at the proposal (ppde.py:119)
         CHK(eval_experts(m, c->cfg.which, prop_states(c), c->n, chain_targets(c, 1), 1, s, b_off, n_sub));
+        if (c->forbid.on()) CHK(launch_veto(c, b_off, n_sub, true, s));   // the proposal is not free: veto[b] for the accept phase
         CHK(launch_chain_kernel(c, (fuse && i + 1 < count && !event) ? KP_ACCEPT_PROPOSE : KP_ACCEPT, a, n_sub, s));
         after_event = event;
         // what follows runs on the object's one stream and covers every chain of it: the swap or the selection, then the observers,
@@ -660,6 +675,7 @@ int ppde_chains_set_reversible(ppde_chains* c, int on) {
     CHK(free_of(c->temper.on(), "tempering", "ppde_chains_set_tempering(c, 0, NULL, 0)"));
     CHK(free_of(c->anneal.on(), "annealing", "ppde_chains_set_annealing(c, NULL)"));
     CHK(free_of(c->recomb.on(), "recombination", "ppde_chains_set_recombination(c, NULL)"));
+    CHK(free_of(c->forbid.on(), "a pattern constraint", "ppde_chains_set_forbidden_patterns(c, NULL)"));
     c->reversible = on != 0;
     return PPDE_OK;
 }
@@ -671,6 +687,7 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
     const Geom& g = m->g;
     hipStream_t s = c->stream;
     const int n = c->n;
+    if (c->forbid.on()) CHK(forbidden_check_init(c, idx0_dev));    // every initial state must be free
     hipLaunchKernelGGL(k_pack_state, dim3((n * g.Ls + 255) / 256), dim3(256), 0, s, idx0_dev, c->cur, n, g.L, g.Ls, g.sh);
     HIPCHK(hipGetLastError());
     CHK(state_rows_to_t4(m, c->cur, c->curT, n, c->n_pad, s));
@@ -717,6 +734,7 @@ int ppde_chains_init(ppde_chains* c, const uint8_t* idx0_dev) {
     // a fresh start of every mode that is on (each in its header), then the graph segments
     if (c->temper.on()) CHK(tempering_fresh_start(c));
     if (c->anneal.on()) CHK(anneal_fresh_start(c));
+    if (c->forbid.on()) CHK(forbidden_fresh_start(c));
     if (c->recorder.on()) CHK(recorder_fresh_start(c));
     if (c->pairs.on()) CHK(pairs_fresh_start(c));
     if (c->archive.on()) CHK(archive_fresh_start(c));

@@ -87,6 +87,9 @@ struct PasArgs {
     long long* swap_accepts;
     uint8_t* rung_hist;         // [T+1][n]
     int n_rungs, swap_every;
+    // forbidden patterns (ppde_chains_set_forbidden_patterns): veto[b] != 0 = the pending proposal is not free (motif.h); NULL = none.
+    // Read by the REV accept phases only.
+    const uint8_t* veto;        // [n]
 };
 
 // LDS of a chain workgroup: the gradient row (float4[N/4]), the letters of the start state and of the wild
@@ -1412,8 +1415,8 @@ __device__ __forceinline__ void accept_stage_path(const PasArgs& a, const RowLds
 // Reverse path, accept/reject, records (ppde.py:122-153). Expects lds.G = gradient at the proposal, lds.St = x,
 // R.cur = x's letters, lds.mv / lpf filled by accept_prefetch. On return R.cur holds the proposal's letters.
 // REV (reversible mode): the reverse rows are the forward row function read at the undoing moves (reverse_rows above); a path
-// with a forbidden reverse move and a proposal at or over the mutation cap are rejected explicitly (never through the test
-// against u, which can be 0); nothing is reset to the wild type: the cap is a constraint of the target, not a reset.
+// with a forbidden reverse move, a proposal at or over the mutation cap and one that is not free (a.veto) are rejected explicitly
+// (never through the test against u, which can be 0); nothing is reset to the wild type: the cap is a constraint of the target, not a reset.
 // TEMP (tempering, REV only): the chain targets exp(beta E): reverse rows of beta * g, log_acc = beta * (e_y - e_x) + the path's
 // log-ratio; everything recorded (histories, best, cur_e) stays the untempered energy and fitness.
 template <int GPT, bool DEV = false, bool REV = false, bool LIB = false, bool TEMP = false>
@@ -1433,6 +1436,8 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
     float log_ratio = 0.f;
     RevPath rp;
     rp.dist = d_cur; rp.forbid = false; rp.s1max = 0.f;
+    bool vetoed = false;                            // the proposal matches a forbidden pattern: rejected like one at the cap
+    if constexpr (REV) { if (a.veto) vetoed = a.veto[b] != 0; }
     if constexpr (REV) rev_annotate_path(lds, Ub);
     // The reverse rows of a path are independent of each other (gradient at y, states along the recorded path), so
     // up to PAS_SB of them are evaluated per pass: two barriers per pass instead of two per sub-step.
@@ -1461,7 +1466,7 @@ __device__ __forceinline__ AcceptOut accept_body(const PasArgs& a, const RowLds&
     float de = e_y - e_x;
     if constexpr (TEMP) de = beta * de;
     const float log_acc = de + log_ratio;
-    const bool acc = REV ? (!rp.forbid & (d_prop < a.thr) & (expf(log_acc) >= u)) : (expf(log_acc) >= u);
+    const bool acc = REV ? (!rp.forbid & (d_prop < a.thr) & !vetoed & (expf(log_acc) >= u)) : (expf(log_acc) >= u);
     const float e_new = acc ? e_y : e_x, f_new = acc ? f_y : f_x;
 
     PPDE_STAMP(a.dbg, 27, stamp);

@@ -23,6 +23,7 @@
 #include "stats.h"
 #include "anneal.h"
 #include "recombine.h"
+#include "motif.h"
 
 static thread_local std::string g_err;
 

@@ -15,7 +15,8 @@
 //   proposal), counts differ and the two child_dist (wave reductions, one LDS exchange) and writes the record row's
 //   partner / lo / hi / differ / child_dist / pre_energy.
 // k_cross_accept: one workgroup per pair. Decision in fp32: d = (E'_a - E_a) + (E'_b - E_b); outcome 3 a non-finite child energy,
-//   2 a child at or over the mutation cap (neither goes through u), 1 expf(d) >= u, 0 otherwise. An accepted pair's two slots take
+//   2 a child at or over the mutation cap, 4 a child that matches a forbidden pattern (none goes through u), 1 expf(d) >= u, 0
+//   otherwise. An accepted pair's two slots take
 //   from the proposal slot what k_select_copy gives a replaced slot: state row + T4 bytes, cur_e / cur_f / dist_cur, the grad_cur
 //   row under gradient reuse (the combined row of slot 1), row it + 1 of both histories (and of rtraj), the running best by the
 //   accept phase's strict rule. The last accept bit and the traces stay the slot's own Metropolis result.
@@ -193,6 +194,7 @@ __global__ __launch_bounds__(CROSS_BLOCK) void k_cross_accept(CrossArgs a) {
     int outcome;
     if (!finite) outcome = 3;
     else if (da >= p.thr || db >= p.thr) outcome = 2;                    // (thr = INT_MAX without a cap)
+    else if (p.veto && (p.veto[la] | p.veto[lb])) outcome = 4;           // a child is not free (motif.h)
     else outcome = expf(d) >= dr.u ? 1 : 0;
     if (tid == 0) {
         a.outcome[row + la] = (uint8_t)outcome; a.outcome[row + lb] = (uint8_t)outcome;

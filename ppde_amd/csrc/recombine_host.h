@@ -15,6 +15,7 @@ static int launch_cross(ppde_chains* c, const int* it_base, int it_local, hipStr
     r.outcome = rc.outcome; r.log_ratio = rc.log_ratio; r.pre_energy = rc.pre; r.child_energy = rc.child;
     launch_kernel(k_cross_propose, dim3(c->n / 2), dim3(CROSS_BLOCK), 0, s, nullptr, r);
     HIPCHK(hipGetLastError());
+    if (c->forbid.on()) CHK(launch_veto(c, 0, c->n, false, s));     // the children's bytes for outcome 4; not counted
     CHK(eval_experts(c->m, c->cfg.which, prop_states(c), c->n, chain_targets(c, 1), 1, s, 0, c->n));
     launch_kernel(k_cross_accept, dim3(c->n / 2), dim3(CROSS_BLOCK), 0, s, nullptr, r);
     HIPCHK(hipGetLastError());

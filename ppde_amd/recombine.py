@@ -2,11 +2,11 @@
 
 The raw arrays, as `Chains.recombination_state()` holds them, [events, n] each: partner (index of the other chain of the pair), lo, hi
 (the cut, as indices into the open list), differ (segment residues at which the two parents differ), child_dist, outcome
-(0 rejected by the test against u, 1 accepted, 2 a child at the mutation cap, 3 a non-finite child energy), log_ratio, pre_energy,
-child_energy."""
+(0 rejected by the test against u, 1 accepted, 2 a child at the mutation cap, 3 a non-finite child energy, 4 a child that matches
+a forbidden pattern: only with ppde_chains_set_forbidden_patterns), log_ratio, pre_energy, child_energy."""
 import numpy as np
 
-REJECTED, ACCEPTED, CAPPED, NOT_FINITE = 0, 1, 2, 3
+REJECTED, ACCEPTED, CAPPED, NOT_FINITE, FORBIDDEN = 0, 1, 2, 3, 4
 
 
 def _pairs(records):
@@ -23,13 +23,13 @@ def _rate(acc, sel):
 def summarise(records):
     """Acceptance of the recorded pairs. Pairs whose parents agree on the whole segment (differ = 0) are always accepted and
     change nothing: they are counted apart, and every acceptance rate is over the pairs with differ > 0.
-    Returns pairs, identical_share, acceptance, capped_share, not_finite_share (shares of all pairs), by_length {hi - lo + 1:
+    Returns pairs, identical_share, acceptance, capped_share, not_finite_share, forbidden_share (shares of all pairs), by_length {hi - lo + 1:
     (pairs, acceptance)} and by_differ {differ: (pairs, acceptance)}."""
     p = _pairs(records)
     n = int(p["outcome"].size)
     if n == 0:
         return dict(pairs=0, identical_share=float("nan"), acceptance=float("nan"), capped_share=float("nan"),
-                    not_finite_share=float("nan"), by_length={}, by_differ={})
+                    not_finite_share=float("nan"), forbidden_share=float("nan"), by_length={}, by_differ={})
     acc = p["outcome"] == ACCEPTED
     real = p["differ"] > 0
     length = p["hi"] - p["lo"] + 1
@@ -37,7 +37,7 @@ def summarise(records):
     by_differ = {int(v): (int((p["differ"] == v).sum()), _rate(acc, p["differ"] == v)) for v in np.unique(p["differ"][real])}
     return dict(pairs=n, identical_share=float((~real).mean()), acceptance=_rate(acc, real),
                 capped_share=float((p["outcome"] == CAPPED).mean()), not_finite_share=float((p["outcome"] == NOT_FINITE).mean()),
-                by_length=by_length, by_differ=by_differ)
+                forbidden_share=float((p["outcome"] == FORBIDDEN).mean()), by_length=by_length, by_differ=by_differ)
 
 
 def lineage(records, open_sites, n, L):

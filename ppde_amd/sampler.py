@@ -77,6 +77,15 @@ Extra, optional attributes on `args` (absent in the reference, defaults keep its
                         (without one: min_pos..max_pos); a site list in library.parse_sites syntax ('8-20,33') or a strictly
                         increasing sequence of 0-based residues. After run(), `sampler.samples` also holds pair_counts uint64
                         [S, 20, S, 20] and pair_sites int32 [S] (both None when off); a sharded run sums the counts.
+    ppde_forbid         None (default): off. Forbidden sequence patterns, as text 'N{P}[ST], NG, K(4)' (ppde_amd/motifs.py: a letter, x
+                        = any, [..] a set, {..} a complement, (n) a repetition; a name of motifs.PRESETS stands for its pattern), a
+                        list of such strings or a motifs.Patterns: at most 32 patterns of 1..8 elements. A proposal that matches one
+                        anywhere in the sequence (frozen residues are context) is rejected on the device, so the chains sample
+                        exp(E) 1[free] / Z (include/ppde_hip.h, ppde_chains_set_forbidden_patterns). Needs ppde_reversible. Sites at
+                        which the wild type matches are exempt unless ppde_forbid_strict is set. Every initial state must be free.
+                        After run(), `sampler.forbidden` holds text, allow_native, active uint32 [L], vetoes int64 [n, M] (global
+                        chain order) and `summary` (motifs.summarise: the share of proposals vetoed, overall and per pattern).
+    ppde_forbid_strict  False (default). True: the wild type's own matches are checked too (allow_native = 0).
     ppde_archive        None or 0 (default): off. K in 1..32: every chain keeps, on the device, the K best distinct sequences it
                         visited, each with its own energy (include/ppde_hip.h, ppde_chains_set_archive): n K L bytes whatever the
                         run length, no host round trip, nothing else of the run changes. The wild type is never archived. After
@@ -103,7 +112,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import _hip, anneal as chain_anneal, recombine as chain_recombine, archive as chain_archive, library as design_library, stats as chain_stats
+from . import _hip, motifs as chain_motifs, anneal as chain_anneal, recombine as chain_recombine, archive as chain_archive, library as design_library, stats as chain_stats
 from .base_sampler import BaseSampler
 from .encoding import idx_to_onehot
 from .noise import draw_chunk
@@ -167,6 +176,35 @@ def pair_sites_of(spec, L, min_pos, max_pos, lib_words=None):
     if spec[-1] >= L:
         raise ValueError(f"ppde_sample_pairs: residue {spec[-1]} lies outside the sequence 0..{L - 1}")
     return np.asarray(spec, np.int32)
+
+
+def check_forbid(spec, strict=False, reversible=False, paper_results=False):
+    """(Patterns or None, allow_native) of the ppde_forbid* arguments; ValueError for what the ABI would refuse and can be seen
+    without the sequence (the text form, the number of patterns and their lengths, the modes)."""
+    strict = bool(strict)
+    if spec is None or (isinstance(spec, (str, list, tuple)) and len(spec) == 0):
+        if strict:
+            raise ValueError("ppde_forbid_strict needs ppde_forbid")
+        return None, True
+    if not reversible:
+        raise ValueError("ppde_forbid: a pattern constraint needs ppde_reversible (only there is the target exp(E) 1[free] / Z that "
+                         "the explicit rejection keeps)" + ("; paper_results excludes it" if paper_results else ""))
+    return chain_motifs.parse(spec), not strict
+
+
+def check_forbid_population(pt, allow_native, wt_idx, population_idx):
+    """What needs the sequence: the setter's checks against L, at least one active (pattern, position), and every initial state
+    free; ValueError names the chain, the pattern and the position."""
+    L = int(np.asarray(wt_idx).size)
+    chain_motifs.check_patterns(pt, L)
+    if not chain_motifs.active_mask(pt, L, wt_idx, allow_native).any():
+        raise ValueError("ppde_forbid: no active (pattern, position): the wild type matches every pattern at every start")
+    fp, pos = chain_motifs.find(population_idx, pt, wt_idx, allow_native)
+    bad = np.flatnonzero(fp >= 0)
+    if bad.size:
+        b = int(bad[0])
+        raise ValueError(f"ppde_forbid: the initial state of chain {b} is not free: forbidden pattern {int(fp[b])} ({pt.text[int(fp[b])]}) "
+                         f"matches at position {int(pos[b])}" + ("" if allow_native else " (ppde_forbid_strict checks the wild type's own sites)"))
 
 
 def check_archive(k, paper_results=False, n_streams=1):
@@ -536,7 +574,8 @@ class Chains:
     def recombination_state(self, first=0, count=None):
         """Events [first, first + count) (default: all so far), [count, n] each: partner (LOCAL index), lo, hi (indices into
         open_sites), differ, child_dist int32, outcome uint8 (0 rejected by u, 1 accepted, 2 a child at the mutation cap, 3 a
-        non-finite child energy), log_ratio, pre_energy, child_energy fp32; deme, every, open_sites, events."""
+        non-finite child energy, 4 a child that matches a forbidden pattern), log_ratio, pre_energy, child_energy fp32; deme,
+        every, open_sites, events."""
         D, sites, _, done = self.recombination_shape()
         first = int(first)
         count = done - first if count is None else int(count)
@@ -544,6 +583,34 @@ class Chains:
         self._call("recombination_read", first, count, *[_hip.ptr(out[k_]) for k_, _ in self.RECOMBINATION_FIELDS])
         out.update(deme=D, every=self.recombination["every"], open_sites=sites, events=done)
         return out
+
+    def set_forbidden(self, patterns, allow_native=True):
+        """Forbidden patterns (include/ppde_hip.h, ppde_chains_set_forbidden_patterns): `patterns` as ppde_amd/motifs.py parses
+        them ('N{P}[ST], NG', a list, or Patterns); a proposal that matches one at an active start is rejected, so the chains
+        sample the target restricted to free states. allow_native exempts the sites at which the wild type matches. None clears
+        it. Needs reversible mode; only before init(). `self.forbidden["note"]` holds what the setter had to say (a wild type
+        that is not free under allow_native False)."""
+        if patterns is None:
+            self._call("set_forbidden_patterns", None)
+            self.forbidden = None
+            return
+        cfg, pt = chain_motifs.config(patterns, allow_native)
+        self._call("set_forbidden_patterns", C.byref(cfg))
+        note = self.lib.ppde_last_error().decode()
+        self.forbidden = dict(patterns=pt, allow_native=bool(allow_native),
+                              note=note if note.startswith("ppde_chains_set_forbidden_patterns: note:") else None)
+
+    def forbidden_state(self):
+        """dict(n_patterns, allow_native, active uint32 [L], text, vetoes int64 [n, M] -- None before init())."""
+        M, an = C.c_int32(), C.c_int32()
+        active = np.empty(self.model.L, np.uint32)
+        self._call("forbidden_shape", C.byref(M), C.byref(an), _hip.ptr(active))
+        vetoes = None
+        if getattr(self, "_initialised", False):
+            vetoes = np.zeros((self.n, M.value), np.int64)
+            self._call("forbidden_read", _hip.ptr(vetoes))
+        return dict(n_patterns=M.value, allow_native=bool(an.value), active=active, text=list(self.forbidden["patterns"].text),
+                    vetoes=vetoes)
 
     def set_recorder(self, every, burn_in=0, rung=None, keep_samples=True):
         """Recorder (include/ppde_hip.h, ppde_chains_set_recorder): the state after t completed iterations is recorded on the
@@ -648,6 +715,7 @@ class Chains:
             raise ValueError("residue indices must be in 0..19")
         torch.cuda.current_stream(self.model.device).synchronize()
         self._call("init", _hip.ptr(idx0))
+        self._initialised = True
 
     def run(self, steps, noise=None):
         """noise = (U int32 [steps,n], q fp32 [sum max_u, n, N], u fp32 [steps,n], max_u list) for rng_mode 0."""
@@ -784,6 +852,9 @@ class PPDE_PAS(BaseSampler):
             getattr(args, "ppde_sample_every", 0), getattr(args, "ppde_sample_burn_in", 0), getattr(args, "ppde_sample_rung", None),
             getattr(args, "ppde_sample_counts_only", False), getattr(args, "ppde_sample_pairs", None), self.betas, self.n_streams)
         self.archive_k = check_archive(getattr(args, "ppde_archive", None), self.paper_results, self.n_streams)
+        self.forbid, self.forbid_allow_native = check_forbid(getattr(args, "ppde_forbid", None), getattr(args, "ppde_forbid_strict", False),
+                                                             self.reversible, self.paper_results)
+        self.forbidden = None
         self.stats_spec = check_stats(getattr(args, "ppde_stats", None), self.n_streams)
         self.tempering = self.annealing = self.samples = self.archive = self.stats = None     # what the last run() collected
         self.noise_bytes = getattr(args, "ppde_noise_bytes", 96 << 20)   # host->device noise is uploaded in chunks of about this size
@@ -805,6 +876,9 @@ class PPDE_PAS(BaseSampler):
             lib = design_library.full_library(L) if self.library is None else design_library.as_words(self.library, L)
             lib_words = design_library.fold_range(lib, min_pos, max_pos)
             design_library.check_population(lib_words, initial_population.detach().argmax(-1).cpu().numpy())
+        if self.forbid is not None:
+            check_forbid_population(self.forbid, self.forbid_allow_native, self._wt_idx,
+                                    initial_population.detach().argmax(-1).cpu().numpy())
         R = 0 if self.betas is None else int(self.betas.size)
         if R and n_global % R:
             raise ValueError(f"ppde_betas: the population of {n_global} chains is no multiple of the {R} rungs of the ladder")
@@ -853,6 +927,8 @@ class PPDE_PAS(BaseSampler):
             chains.set_library(lib_words)
         if self.reversible:
             chains.set_reversible(True)
+        if self.forbid is not None:
+            chains.set_forbidden(self.forbid, self.forbid_allow_native)
         if plan.R:
             chains.set_tempering(self.betas, self.swap_every)
         if plan.D and self.anneal_adaptive is not None:
@@ -915,6 +991,9 @@ class PPDE_PAS(BaseSampler):
             self._log_annealing(chains, shard, D)
         if plan.X:
             self._log_recombination(chains, shard)
+        if self.forbid is not None:
+            v = shard.gather(chains.forbidden_state()["vetoes"])
+            print("   " + chain_motifs.log_line(chain_motifs.summarise(v, chains.steps_done, self.forbid.text)))
         if self.stats_spec is not None:
             print(chain_stats.log_line(gather_stats(shard, chains.stats())))
 
@@ -1019,6 +1098,14 @@ class PPDE_PAS(BaseSampler):
         arc["candidates"] = chain_archive.merge(arc["idx"], arc["energy"], arc["fitness"], arc["step"], arc["count"])
         return arc
 
+    def _collect_forbidden(self, chains, shard):
+        if self.forbid is None:
+            return None
+        st = chains.forbidden_state()
+        v = shard.gather(st["vetoes"])
+        return dict(text=st["text"], allow_native=st["allow_native"], active=st["active"], vetoes=v,
+                    summary=chain_motifs.summarise(v, chains.steps_done, st["text"]))
+
     def _collect_stats(self, chains, shard):
         if self.stats_spec is None:
             return None
@@ -1036,6 +1123,7 @@ class PPDE_PAS(BaseSampler):
                             "there is no generic torch fallback")
         min_pos, max_pos = int(min_pos), int(max_pos)
         # ---- host-only plan: every refusal that needs no device comes from here
+        self._wt_idx = np.asarray(model.wt_idx) if self.forbid is not None else None
         plan = self._plan(initial_population, num_steps, min_pos, max_pos)
         shard, R, D, L, random_idx = plan.shard, plan.R, plan.D, plan.L, plan.random_idx
         idx0 = model.onehot_to_idx(initial_population)
@@ -1094,6 +1182,7 @@ class PPDE_PAS(BaseSampler):
         self.samples = self._collect_samples(chains, shard, R)
         self.archive = self._collect_archive(chains, shard)
         self.stats = self._collect_stats(chains, shard)
+        self.forbidden = self._collect_forbidden(chains, shard)
         if shard.n_global == 1:
             # the reference's single-chain shapes (ppde.py:178-183; the ensemble's `.squeeze()`, nets.py:442, makes one chain's
             # fitness a scalar): fitness_history (T+1,) next to energy_history (T+1, 1); with ProteinSupervised the energy IS

@@ -15,7 +15,9 @@ Extra flags: --ppde_rng {torch,philox}, --ppde_seed, --ppde_reuse_grad {0,1}, --
 a run: a ladder of inverse temperatures with replica exchange); --ppde_sample_every, --ppde_sample_burn_in, --ppde_sample_rung,
 --ppde_sample_counts_only, --ppde_sample_pairs (thinned samples of the population and per-site letter counts, recorded on the device: samples.npy
 [rows, slots, L] uint8, sample_energy.npy, sample_fitness.npy, sample_chain.npy [rows, slots], site_counts.npy [L, 20]). A run with
-a ladder also writes rung_history.npy [T+1, n], swap_attempts.npy and swap_accepts.npy [n / R, R - 1].
+a ladder also writes rung_history.npy [T+1, n], swap_attempts.npy and swap_accepts.npy [n / R, R - 1]. --ppde_forbid,
+--ppde_forbid_file, --ppde_forbid_strict (forbidden sequence patterns of a reversible run: motif_vetoes.npy [n, M] int64 and
+motif_patterns.txt).
 """
 import argparse
 import datetime
@@ -44,9 +46,26 @@ def get_sampler(args, library=None):
         # (a copy: the namespace itself is what config.txt records, and a mask is no JSON)
         # (--ppde_stats_no_sites alone switches the statistics on, without their per-residue counts)
         stats = "no-sites" if getattr(args, "ppde_stats_no_sites", False) else bool(getattr(args, "ppde_stats", False))
-        return PPDE_PAS(argparse.Namespace(**{**vars(args), "ppde_library": library, "ppde_stats": stats}))
+        return PPDE_PAS(argparse.Namespace(**{**vars(args), "ppde_library": library, "ppde_stats": stats,
+                                              "ppde_forbid": forbidden_patterns_from_flags(args)}))
     raise NotImplementedError(f"--sampler {args.sampler}: only PPDE is implemented on the MI355X path "
                               "(simulated_annealing / MALA-approx / CMAES / Random are the paper's baselines)")
+
+
+def forbidden_patterns_from_flags(args):
+    """--ppde_forbid / --ppde_forbid_file -> the list of pattern texts, or None. The file holds one pattern (or a comma-separated
+    list) per line; '#' starts a comment."""
+    items = []
+    text, path = getattr(args, "ppde_forbid", None), getattr(args, "ppde_forbid_file", None)
+    if text:
+        items += [t.strip() for t in text.split(",")]
+    if path is not None:
+        with open(path) as f:
+            for raw in f:
+                line = raw.split("#", 1)[0].strip()
+                if line:
+                    items += [t.strip() for t in line.split(",")]
+    return items or None
 
 
 def design_library_from_flags(args, wt_idx, min_pos, max_pos):
@@ -166,6 +185,11 @@ def main(args):
             np.save(results_path / "candidates.npy", cand["idx"])
             for name, key in (("energy", "energy"), ("fitness", "fitness"), ("chain", "chain"), ("step", "step"), ("nchains", "n_chains")):
                 np.save(results_path / f"candidates_{name}.npy", cand[key])
+        forbidden = getattr(sampler, "forbidden", None)
+        if forbidden is not None:
+            np.save(results_path / "motif_vetoes.npy", forbidden["vetoes"])
+            with open(results_path / "motif_patterns.txt", "w") as f:
+                f.write("".join(t + "\n" for t in forbidden["text"]))
         stats = getattr(sampler, "stats", None)
         if stats is not None:
             for name in ("iters", "accepts", "moved", "jump_sum", "dist_sum", "wt_returns", "len_attempts", "len_accepts", "site_changes"):
@@ -302,6 +326,17 @@ def build_parser():
                          "population's distinct candidates merged from them: candidates.npy uint8 [M, L] with candidates_energy, "
                          "_fitness, _chain, _step and _nchains [M], best first. Works with either --ppde_rng; not with "
                          "--paper_results")
+    pp.add_argument("--ppde_forbid", metavar="PATTERNS", type=str, default=None,
+                    help="forbidden sequence patterns (needs --ppde_reversible), e.g. 'N{P}[ST],NG,K(4)': a letter, x = any, [..] a "
+                         "set, {..} a complement, (n) a repetition, or a preset name (n_glycosylation, deamidation, isomerisation); "
+                         "at most 32 patterns of 1..8 elements. A proposal that matches one anywhere in the sequence is rejected, so "
+                         "no chain, sample or archive entry ever holds one. Sites at which the wild type matches are exempt. Writes "
+                         "motif_vetoes.npy int64 [n, M] and motif_patterns.txt; the periodic log gains a 'forbidden patterns' line")
+    pp.add_argument("--ppde_forbid_file", metavar="FILE", type=str, default=None,
+                    help="more patterns for --ppde_forbid, one per line ('#' comments)")
+    pp.add_argument("--ppde_forbid_strict", action="store_true",
+                    help="with --ppde_forbid: check the sites at which the wild type matches too (a wild type that matches cannot "
+                         "start a run)")
     pp.add_argument("--ppde_stats", action="store_true",
                     help="count, on the device, how the chains move: stats_iters, _accepts, _moved, _jump_sum, _dist_sum and "
                          "_wt_returns.npy int64 [n, R] per (chain, rung), stats_len_attempts and _len_accepts.npy [R, 2 pas - 1] per "
