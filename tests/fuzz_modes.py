@@ -2,7 +2,9 @@
 """Random configurations of the chain modes (default, reversible, tempering, fixed and adaptive annealing, recombination; each with
 and without a design library; the four observers on half of them) at random geometries, on the device RNG, against the modes' CPU
 references fed the device's noise restated on the CPU (tests/helpers_fuzz_modes.py: draw, reference, compare). No chain is exempt:
-only draws whose reference run takes no decision near a tie are kept.
+only draws whose reference run takes no decision near a tie are kept. FZ_FORBID=1: every configuration also carries forbidden
+patterns built on its own unconstrained reference (the reversible dynamics only), and the veto counters, the active words and
+outcome 4 join the comparison.
 Run on the GPU box: python tests/fuzz_modes.py [seed]; FZ_TRIALS trials (default 12), FZ_DYNAMICS a comma list that restricts the
 dynamics. PPDE_GRAPH_LEN (read once per process by the library) lets the short runs replay graphs: the generator then draws runs
 that do, and the script demands that every dynamics it ran replayed some steps. Prints one line per trial and `failures: N`; exits non-zero on a mismatch. An
@@ -42,6 +44,8 @@ def build(cfg, m, trace):
                                   cfg["min_step"])
     elif dyn == "recombine":
         ch.set_recombination(cfg["every"], cfg["deme"])
+    if cfg.get("patterns") is not None:                                       # (between create and init, behind set_reversible)
+        ch.set_forbidden(cfg["patterns"], cfg["allow_native"])
     if ob is not None:
         ch.set_recorder(ob["every"], ob["burn_in"], ob["rung"], True)
         ch.set_pair_counts(ob["sites"])
@@ -67,6 +71,8 @@ def device_run(cfg, m):
         run["anneal"] = ch.annealing_state()
     if dyn == "recombine":
         run["recomb"] = ch.recombination_state()
+    if cfg.get("patterns") is not None:
+        run["forbid"] = ch.forbidden_state()
     if cfg["observers"] is not None:
         run.update(rec=ch.recorded(), pairs=ch.pair_counts(), archive=ch.archive(), stats=ch.stats())
     ch.close()
@@ -78,9 +84,10 @@ def main():
     trials = int(os.environ.get("FZ_TRIALS", 12))
     pool = tuple(os.environ["FZ_DYNAMICS"].split(",")) if os.environ.get("FZ_DYNAMICS") else None
     graph_len = int(os.environ.get("PPDE_GRAPH_LEN", 0) or 0)
+    forbid = os.environ.get("FZ_FORBID", "0") not in ("", "0")
     t0 = time.time()
-    configs, discarded = fz.kept(seed, trials, pool, graph_len)
-    print(f"{trials} configurations kept, {discarded} discarded near a tie ({time.time() - t0:.1f} s of CPU reference)", flush=True)
+    configs, discarded = fz.kept(seed, trials, pool, graph_len, forbid)
+    print(f"{trials} configurations kept, {discarded} discarded near a tie{' or without a veto' if forbid else ''} ({time.time() - t0:.1f} s of CPU reference)", flush=True)
     bad, replayed = 0, {}
     for trial, (cfg, ref) in enumerate(configs):
         print(f"trial {trial}: {fz.describe(cfg)}", flush=True)
@@ -110,7 +117,8 @@ def main():
                 why.append("the run without trace buffers differs from the traced run")
         bad += bool(why)
         de = np.abs(run["res"]["energy_history"] - ref["run"]["res"]["energy_history"]).max()
-        print(f"   -> {'ok' if not why else 'FAIL: ' + '; '.join(why[:8])} (max |dE| {de:.1e}, accepted {run['tr']['accepted'].mean():.2f}, "
+        vetoed = f"vetoes {int(run['forbid']['vetoes'].sum())}, " if forbid else ""
+        print(f"   -> {'ok' if not why else 'FAIL: ' + '; '.join(why[:8])} (max |dE| {de:.1e}, {vetoed}accepted {run['tr']['accepted'].mean():.2f}, "
               f"replayed {gs['replayed_steps']} of {cfg['T']}, device {time.time() - t1:.2f} s)", flush=True)
         m.close()
     print("replayed steps per dynamics:", replayed)

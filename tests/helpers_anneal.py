@@ -84,13 +84,16 @@ def plan(e, dbeta, u, fault=None):
 
 
 def annealed_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_length, nmut_threshold, betas, every, deme,
-                 seed=0, chain_offset=0, allowed=None, trace=False, select_u=None, fault=None, keep_probs=False):
+                 seed=0, chain_offset=0, allowed=None, trace=False, select_u=None, fault=None, keep_probs=False, forbidden=None,
+                 motif_fault=None):
     """The whole mode on explicit noise: what hr.reversible_run returns (histories and best states on the UNTEMPERED energy;
     history row it + 1 and states[it + 1] describe the population AFTER selection), plus parent int32 [events, n] (local
     indices), pre_energy fp32 [events, n], log_mean_w / ess fp64 [events, n / D], beta fp32 [n] at the end, accepted
     [T, n] (the slots' own Metropolis results), post_accept (states, energies) per iteration, and select_margin, the smallest
     |tau_j - C_i| / W over all offspring. `select_u`: callable it -> u [n / D] replacing Philox. `keep_probs`: the traces keep the
-    forward proposal rows (helpers_reversible.replay_margins reads them)."""
+    forward proposal rows (helpers_reversible.replay_margins reads them).
+    `forbidden` = (patterns, allow_native): the iteration runs through helpers_motifs' constrained iteration on the
+    same beta-scaled energy object, and the result gains vetoes int64 [n, M] (`motif_fault`: one of helpers_motifs' faults)."""
     betas = np.asarray(betas, dtype=np.float32)
     S, D = int(betas.size) - 1, int(deme)
     thr = hr._threshold(nmut_threshold)
@@ -108,10 +111,12 @@ def annealed_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_l
     parents, pres, lmws, esss, post = [], [], [], [], []
     cur = idx0.clone()
     margin = np.inf
+    import helpers_motifs as hmot
+    iteration, con = hmot.iteration_of(forbidden, n, motif_fault)
     for it in range(num_steps):
         U, q, u = noise(it)
         sc = ht.ScaledEnergy(energy, beta)
-        out = hr.reversible_iteration(sc, cur, cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
+        out = iteration(sc, cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
         (ex, fx), (ey, fy) = sc.raw
         a = out["accepted"]
         cur = out["idx"].clone()
@@ -159,6 +164,8 @@ def annealed_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_l
                beta=beta.copy(), post_accept=post, select_margin=margin)
     if trace:
         res["traces"] = traces
+    if con is not None:
+        res.update(vetoes=con.vetoes, veto_log=con.log)
     return res
 
 

@@ -93,13 +93,14 @@ def ulp32(b):
 
 
 def adaptive_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_length, nmut_threshold, beta_start, beta_end, rho,
-                 min_step, every, deme, max_stages=4096, seed=0, chain_offset=0, allowed=None, fault=None, trace=False, keep_probs=False):
+                 min_step, every, deme, max_stages=4096, seed=0, chain_offset=0, allowed=None, fault=None, trace=False, keep_probs=False, forbidden=None,
+                 motif_fault=None):
     """The adaptive run of ONE deme (idx0 [D, L]; `noise` as helpers_anneal.annealed_run takes it) by the rule itself: the schedule
     is grown one event at a time -- annealed_run on the path so far (padded with an equal beta, whose event is the identity)
     shows the energies event s sees, `step` turns them into beta_after[s] -- and the run on the finished path is returned with
     beta_path fp32 [events + 1]. `fault`: one of FAULTS ('delta_w' resamples event s by helpers_anneal.plan's weights at d
     instead of at the rounded pair; the others change beta_next). `trace`, `keep_probs`: as annealed_run takes them, for the
-    returned run."""
+    returned run. `forbidden`, `motif_fault`: handed to every annealed_run (the prefixes run under the constraint too)."""
     D = int(deme)
     assert idx0.shape[0] == D
     cap = min(int(max_stages), num_steps // every)
@@ -107,6 +108,8 @@ def adaptive_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_l
     db_over = {}
 
     def run(sched, T, **kw):
+        if forbidden is not None:
+            kw.update(forbidden=forbidden, motif_fault=motif_fault)
         if fault != "delta_w":
             return ha.annealed_run(energy, idx0, wt_idx, noise, T, min_pos, max_pos, pas_length, nmut_threshold, sched, every, D, seed=seed,
                                    chain_offset=chain_offset, allowed=allowed, **kw)

@@ -4,12 +4,14 @@
 annealing (fixed and adaptive) and recombination, each with and without a design library, with the observers on half the draws,
 over the axes the hand-picked mode tests leave alone (two and three logit groups per thread, padded state rows of any length, a
 proposal range that is not the Potts window, demes astride 64 lanes, pas 1 and 5, several streams, a run cut into several calls).
+With `forbid` the configuration also carries forbidden patterns (ppde_chains_set_forbidden_patterns) under one of the five
+reversible dynamics, built around proposals its own unconstrained reference accepted (`_patterns`).
 `check_abi(cfg)` restates the refusal rules of include/ppde_hip.h for such a dict; `draw` returns only what passes them.
 
 `reference(cfg)` is the CPU run of the configuration: orc.device_noise restates the device RNG, the mode's own helper runs the
 iterations, the observers' rules (helpers_archive, helpers_stats, helpers_pairs, the recorder's row rule of ppde_amd.sampler) turn
 its states into what the device must hold. It is returned in the layout a device run is read in, with the reference's own
-near-tie margins. No rule is stated here a second time.
+near-tie margins. No rule is stated here a second time: the veto is helpers_motifs' constrained iteration inside each mode's helper.
 
 `compare(cfg, run, ref)` is the ONE comparison both modules call: the GPU script hands it a device run, the CPU module a reference
 run with a planted fault. No chain is exempt: `kept(...)` keeps a draw only if every decision of its reference run is clear of a
@@ -25,6 +27,7 @@ import helpers_anneal_adaptive as haa
 import helpers_archive as har
 import helpers_library as hl
 import helpers_modes as hm
+import helpers_motifs as hmot
 import helpers_pairs as hp
 import helpers_recombine as hrc
 import helpers_reversible as hr
@@ -33,6 +36,7 @@ import helpers_tempering as ht
 import ppde_oracle as orc
 from helpers import oracle_energy
 from ppde_amd import library as dl
+from ppde_amd import motifs
 from ppde_amd import synthetic
 from ppde_amd.sampler import recorder_row_of, recorder_rows
 
@@ -40,6 +44,10 @@ A = 20
 BLOCK = 512                                    # threads of a chain workgroup (PPDE_BLOCK): groups per thread = ceil(L * 20 / 4 / 512)
 DYNAMICS = ("default", "reversible", "tempering", "anneal", "adaptive", "recombine")
 GROUPED = ("tempering", "anneal", "adaptive", "recombine")
+REVERSIBLE = DYNAMICS[1:]                       # the dynamics forbidden patterns compose with
+# the seeds of the two pattern lists, searched on the CPU reference alone for lists that show every item
+# tests/test_fuzz_modes_cpu.py asserts of them
+PATTERN_SEEDS = (8, 3)
 # the thresholds of the modes' own replay tests: swap |d - log u| (tests/test_tempering_cpu.py), selection |tau - C| / W
 # (tests/test_anneal_gpu.py), recombination |exp(d) - u| (tests/test_recombine_gpu.py); race gap and accept margin are helpers_modes'
 NEAR = dict(gap=hm.GAP_TOL, accept=hm.ACC_TOL, swap=2e-3, select=1e-4, cross=1e-4)
@@ -50,6 +58,9 @@ GPU_CASES = {
     "default_env": dict(seed=43, trials=24, env={}, dynamics=None),
     "graph_len_4": dict(seed=53, trials=24, env={"PPDE_GRAPH_LEN": "4"}, dynamics=None, graph_len=4),
     "general_kernels": dict(seed=33, trials=8, env={"PPDE_CHAIN_SPEC": "0"}, dynamics=("default",)),
+    "patterns": dict(seed=PATTERN_SEEDS[0], trials=20, env={"FZ_FORBID": "1"}, dynamics=REVERSIBLE, forbid=True),
+    "patterns_graph_len_4": dict(seed=PATTERN_SEEDS[1], trials=20, env={"FZ_FORBID": "1", "PPDE_GRAPH_LEN": "4"}, dynamics=REVERSIBLE,
+                                 graph_len=4, forbid=True),
 }
 
 
@@ -73,10 +84,16 @@ def _library(rng, wt, L, lo, hi):
     raise AssertionError("no library for this range")
 
 
-def draw(rng, dynamics=None, library=None, graph_len=0):
+def draw(rng, dynamics=None, library=None, graph_len=0, forbid=False, allow_native=True):
     """One configuration. `dynamics` / `library` pin those two axes (kept() cycles through them); everything else is drawn.
     `graph_len`: the run is to replay graph segments of that length (PPDE_GRAPH_LEN): graphs are on, a recombination `every` divides
-    it, and the cuts are drawn again until some call replays a segment."""
+    it, and the cuts are drawn again until some call replays a segment.
+    `forbid`: a configuration with forbidden patterns (`patterns`, `allow_native`): one of the REVERSIBLE dynamics, with several
+    streams a population some stream's share of which is no multiple of the veto kernel's four chains per workgroup, and patterns
+    built on the configuration's own unconstrained reference (`_patterns`); None where none could be built. Without it nothing new
+    is drawn and no variate consumed."""
+    if forbid and dynamics is None:
+        dynamics = REVERSIBLE[int(rng.integers(len(REVERSIBLE)))]
     dyn = DYNAMICS[int(rng.integers(len(DYNAMICS)))] if dynamics is None else dynamics
     with_lib = bool(rng.integers(2)) if library is None else bool(library)
     with_cnn = bool(rng.integers(0, 5) == 0)                               # (the CPU CNN is slow: a minority, at L <= 100)
@@ -138,6 +155,8 @@ def draw(rng, dynamics=None, library=None, graph_len=0):
         cfg["observers"] = dict(every=every, burn_in=int(rng.integers(0, T - every + 1)), rung=rung, K=int(rng.choice([1, 3, 32])),
                                 sites=hp.scattered_sites(L, int(rng.choice([s for s in hp.SITE_COUNTS if s <= L])), int(rng.integers(1 << 20))))
     cfg["n_streams"] = int(rng.choice([1, 2, 3])) if dyn in ("default", "reversible") and cfg["observers"] is None else 1
+    if forbid and cfg["n_streams"] > 1 and not ragged_share(n, cfg["n_streams"]):
+        n = cfg["n"] = n + 1
     # the run, cut into 1..4 calls; with recombination on half the draws at multiples of `every` only
     if graph_len:
         cfg["use_graph"] = True
@@ -159,8 +178,108 @@ def draw(rng, dynamics=None, library=None, graph_len=0):
         for l in rng.choice(span, size=k, replace=False):
             start[b, l] = rng.choice(np.flatnonzero((int(words[l]) >> np.arange(A)) & 1))
     cfg["start"] = start
+    if forbid:
+        assert dyn in REVERSIBLE
+        cfg["allow_native"] = bool(allow_native)
+        cfg["patterns"] = _patterns(rng, cfg, reference(cfg))
+        if cfg["patterns"] is None:
+            return None
     assert not check_abi(cfg), check_abi(cfg)
     return cfg
+
+
+def stream_shares(n, n_streams):
+    """The chains of every stream's sub-population (ppde_chains_create: at most 8 streams, the remainder to the first ones)."""
+    K = min(n_streams, 8, n) if n_streams > 1 else 1
+    return [n // K + (k < n % K) for k in range(K)]
+
+
+def ragged_share(n, n_streams):
+    return any(s % 4 for s in stream_shares(n, n_streams))
+
+
+def _extras(rng, density, without=()):
+    w = int(sum(1 << k for k in range(A) if rng.random() < density))
+    for k in without:
+        w &= ~(1 << int(k))
+    return w
+
+
+def _patterns(rng, cfg, ref0):
+    """Patterns for `cfg` from its unconstrained reference run `ref0`: M of {1, 3, 32}, each built around the mutated residue of a
+    proposal that run ACCEPTED (pattern 0 around one of the four earliest: up to its first veto the constrained run is the unconstrained one,
+    so that proposal is made again and only the veto can reject it) -- the element at that residue holds the proposal's letter and neither
+    the current nor the wild-type one, the others the proposal's letters in a window of the drawn length, each with random extra
+    letters; on a third of the draws each the window sits at the last start (around a move among the last eight residues, where
+    the run has one) or across lane 64 of the veto kernel, where it can. Under
+    recombination every other pattern is built on an accepted child instead, over a residue it took from its partner and one it
+    kept. Every pattern is drawn again until the starts (without allow_native: and the wild type) are free of it."""
+    L, wt, n, T = cfg["L"], cfg["wt"].astype(np.int64), cfg["n"], cfg["T"]
+    native = cfg["allow_native"]
+    M = int(rng.choice([1, 3, 32]))
+    states, props = ref0["states"], ref0["proposals"]
+    acc = ref0["run"]["tr"]["accepted"].astype(bool)
+    moves = [(int(t), int(b)) for t, b in zip(*np.nonzero(acc)) if (props[t, b] != states[t, b]).any()]          # in time order
+    kids = []
+    if cfg["dynamics"] == "recombine":
+        rc = ref0["run"]["recomb"]
+        for e, b in zip(*np.nonzero((rc["outcome"] == 1) & (rc["differ"] > 0))):
+            own, other = ref0["pre_event"][e][b], ref0["pre_event"][e][rc["partner"][e, b]]
+            child = states[(e + 1) * cfg["every"], b]
+            s1, s2 = np.flatnonzero(child != own), np.flatnonzero(child != other)
+            near = [(int(a), int(c)) for a in s1 for c in s2 if abs(int(a) - int(c)) <= 7]
+            if near:
+                kids.append((child, own, other, near))
+    if not moves:
+        return None
+    tail = [(t, b) for t, b in moves if (props[t, b] != states[t, b])[max(0, L - 8):].any()]
+    el, ln = np.zeros((M, 8), np.uint32), np.zeros(M, np.int32)
+    twin = None
+    for m in range(M):
+        for attempt in range(60):
+            words = np.zeros(8, np.uint32)
+            if kids and m % 2 == 1:
+                child, own, other, near = kids[int(rng.integers(len(kids)))]
+                a, c = near[int(rng.integers(len(near)))]
+                lo_s, hi_s = min(a, c), max(a, c)
+                k = int(rng.integers(hi_s - lo_s + 1, min(8, L) + 1))
+                p = int(rng.integers(max(0, hi_s - k + 1), min(lo_s, L - k) + 1))
+                for j in range(k):
+                    words[j] = (1 << int(child[p + j])) | _extras(rng, 0.3)
+                words[a - p] = (1 << int(child[a])) | _extras(rng, 0.2, (own[a],))
+                words[c - p] = (1 << int(child[c])) | _extras(rng, 0.2, (other[c],))
+            else:
+                where = int(rng.integers(3))
+                if m == 1 and twin is not None and attempt == 0:
+                    t, b = twin                                                 # a second pattern on the first one's proposal
+                elif m > 0 and where == 0 and tail:
+                    t, b = tail[int(rng.integers(len(tail)))]                   # a move among the last eight residues
+                else:
+                    t, b = moves[int(rng.integers(min(len(moves), 4 if m == 0 and attempt < 20 else len(moves))))]
+                if m == 0:
+                    twin = (t, b)
+                x, y = states[t, b], props[t, b]
+                l = int(np.flatnonzero(x != y)[-1]) if where == 0 else int(rng.choice(np.flatnonzero(x != y)))
+                k = int(rng.integers(L - l if where == 0 and L - l <= min(8, L) else 1, min(8, L) + 1))
+                lo_p, hi_p = max(0, l - k + 1), min(l, L - k)
+                p = int(rng.integers(lo_p, hi_p + 1))
+                if where == 0 and hi_p == L - k:
+                    p = L - k
+                seam = [s for s in range(lo_p, hi_p + 1) if s < 64 <= s + k - 1]
+                if where == 1 and seam:
+                    p = int(rng.choice(seam))
+                wide = float(rng.choice([0.15, 0.5, 1.0]))
+                for j in range(k):
+                    words[j] = (1 << int(y[p + j])) | _extras(rng, wide)
+                words[l - p] = (1 << int(y[l])) | _extras(rng, 0.2, (x[l], wt[l]))
+            one = motifs.Patterns(words[None], [k])
+            if motifs.is_free(cfg["start"], one, wt, native).all() and (native or motifs.is_free(wt[None], one, None, False).all()):
+                el[m], ln[m] = words, k
+                break
+        else:
+            return None
+    pt = motifs.Patterns(el, ln)
+    return pt if motifs.active_mask(pt, L, wt, native).any() else None
 
 
 def check_abi(cfg):
@@ -214,6 +333,16 @@ def check_abi(cfg):
         s = np.asarray(ob["sites"])
         need(1 <= s.size <= L and s[0] >= 0 and s[-1] < L and (np.diff(s) > 0).all(), "pair sites")
         need(1 <= ob["K"] <= 32, "archive k")
+    pt = cfg.get("patterns")
+    if pt is not None:                                                      # ppde_chains_set_forbidden_patterns, and init's free starts
+        need(dyn != "default", "forbidden patterns need reversible mode")
+        need(1 <= len(pt) <= motifs.MAX_PATTERNS, "forbidden patterns: n_patterns outside 1..32")
+        need(all(1 <= int(k) <= min(motifs.MAX_LEN, L) for k in pt.lengths), "forbidden patterns: a length outside 1..8 or above L")
+        need(all(0 < int(pt.elements[m, j]) < (1 << A) for m in range(len(pt)) for j in range(min(int(pt.lengths[m]), motifs.MAX_LEN))),
+             "forbidden patterns: an element that is 0 or has a bit >= 20")
+        if not bad:
+            need(motifs.active_mask(pt, L, cfg["wt"], cfg["allow_native"]).any(), "forbidden patterns: no active (m, p)")
+            need(motifs.is_free(cfg["start"], pt, cfg["wt"], cfg["allow_native"]).all(), "forbidden patterns: a start that is not free")
     if dyn != "default" and lib is not None:                                # reversible mode: a start inside the library
         try:
             dl.check_population(lib, cfg["start"])
@@ -228,6 +357,8 @@ def describe(cfg):
              "anneal": lambda: f" D={cfg['deme']} every={cfg['every']} schedule={cfg['schedule']}",
              "adaptive": lambda: f" D={cfg['deme']} every={cfg['every']} ess={cfg['ess_target']} min_step={cfg['min_step']} stages={cfg['max_stages']}",
              "recombine": lambda: f" D={cfg['deme']} every={cfg['every']}"}.get(cfg["dynamics"], lambda: "")()
+    if cfg.get("patterns") is not None:
+        extra += f" patterns={len(cfg['patterns'])} (lengths {sorted(set(cfg['patterns'].lengths.tolist()))}) native={cfg['allow_native']}"
     return (f"{cfg['dynamics']}{'+lib' if cfg['library'] is not None else ''}{extra} L={cfg['L']} Lp={cfg['Lp']} i0={cfg['i0']} "
             f"pos=[{cfg['min_pos']},{cfg['max_pos']}] which={cfg['which']} lam={cfg['lamda']} n={cfg['n']} off={cfg['chain_offset']} T={cfg['T']} "
             f"cuts={cfg['cuts']} pas={cfg['pas']} nmut={cfg['nmut']} reuse={cfg['reuse_grad']} graph={cfg['use_graph']} "
@@ -297,6 +428,7 @@ def library_ignored_on_the_reverse_path():
         hr.proposal_row = real
 
 
+MOTIF_FAULTS = hmot.FAULTS + hmot.RUN_FAULTS      # planted in a configuration with patterns, under any of the REVERSIBLE dynamics
 FAULTS = {"reversible": ("reverse_library",),
           "tempering": ("swap_u_shifted", "beta_on_rows_only"),
           "anneal": ha.FAULTS + ("observers_before_selection",),
@@ -310,12 +442,18 @@ def _runner(cfg, energy, x0, noise, fault):
     fn = lambda t: noise[t]
     common = (fn, cfg["T"], cfg["min_pos"], cfg["max_pos"], cfg["pas"], cfg["nmut"])
     seed, off = cfg["seed"], cfg["chain_offset"]
+    forb = {}
+    if cfg.get("patterns") is not None:                                     # the mode's helper runs its iteration under the constraint
+        forb = dict(forbidden=(cfg["patterns"], cfg["allow_native"]), motif_fault=fault if fault in MOTIF_FAULTS else None)
     if dyn == "default":
         if lib is None:
             return [orc.run(energy, x0, wt, *common, False, trace=True, keep_probs=True)]
         return [hl.masked_run(lib, energy, x0, wt, *common, False, trace=True, keep_probs=True)]
     if dyn == "reversible":
         with library_ignored_on_the_reverse_path() if fault == "reverse_library" else contextlib.nullcontext():
+            if forb:
+                return [hmot.constrained_run(energy, x0, wt, *common, lib, cfg["patterns"], cfg["allow_native"], forb["motif_fault"],
+                                             keep_probs=True)]
             return [hr.reversible_run(energy, x0, wt, *common, trace=True, keep_probs=True, allowed=lib)]
     if dyn == "tempering":
         R = len(cfg["betas"])
@@ -323,10 +461,10 @@ def _runner(cfg, energy, x0, noise, fault):
         swap_u = (lambda it: ht.swap_uniforms(seed, first, it + 1, R)) if fault == "swap_u_shifted" else None
         with hm.beta_on_rows_only() if fault == "beta_on_rows_only" else contextlib.nullcontext():
             return [ht.tempered_run(energy, x0, wt, *common, cfg["betas"], cfg["swap_every"], seed=seed, chain_offset=off, allowed=lib,
-                                    trace=True, keep_probs=True, swap_u=swap_u)]
+                                    trace=True, keep_probs=True, swap_u=swap_u, **forb)]
     if dyn == "anneal":
         return [ha.annealed_run(energy, x0, wt, *common, cfg["schedule"], cfg["every"], cfg["deme"], seed=seed, chain_offset=off,
-                                allowed=lib, trace=True, keep_probs=True, fault=fault if fault in ha.FAULTS else None)]
+                                allowed=lib, trace=True, keep_probs=True, fault=fault if fault in ha.FAULTS else None, **forb)]
     if dyn == "adaptive":
         D, out = cfg["deme"], []
         for d in range(cfg["n"] // D):
@@ -334,12 +472,12 @@ def _runner(cfg, energy, x0, noise, fault):
             sub = lambda t, sl=sl: (noise[t][0][sl], noise[t][1][:, sl], noise[t][2][sl])
             out.append(haa.adaptive_run(energy, x0[sl], wt, sub, cfg["T"], cfg["min_pos"], cfg["max_pos"], cfg["pas"], cfg["nmut"],
                                         cfg["beta_start"], cfg["beta_end"], cfg["ess_target"], cfg["min_step"], cfg["every"], D,
-                                        max_stages=cfg["max_stages"], seed=seed, chain_offset=off + d * D, allowed=lib, fault=fault,
-                                        trace=True, keep_probs=True))
+                                        max_stages=cfg["max_stages"], seed=seed, chain_offset=off + d * D, allowed=lib,
+                                        fault=fault if fault in haa.FAULTS else None, trace=True, keep_probs=True, **forb))
         return out
     words = dl.full_library(cfg["L"]) if lib is None else lib
     return [hrc.recombined_run(energy, x0, wt, *common, cfg["every"], cfg["deme"], seed, words, chain_offset=off,
-                               fault="round0" if fault == "round0" else None, trace=True, keep_probs=True)]
+                               fault="round0" if fault == "round0" else None, trace=True, keep_probs=True, **forb)]
 
 
 def _observers(cfg, peeks, accepted, U, rung_hist):
@@ -405,6 +543,10 @@ def reference(cfg, fault=None, energy=None):
                         random_traj=states[:, 0].astype(np.uint8)),
                peeks=[peeks[t] for t in np.cumsum(cfg["cuts"])], temp=None, anneal=None, recomb=None)
     margins, events = {}, dict(cap_reached=bool(cfg["nmut"] and (dist >= cfg["nmut"] - 1).any()))
+    pt = cfg.get("patterns")
+    if pt is not None:                 # a vetoed proposal's |log_acc - log u| decides nothing: it counts as refused in the margin
+        for p in parts:
+            p["traces"] = [dict(o, refused=o["refused"] | o["veto"]) for o in p["traces"]]
     acc_m, gap = zip(*[hm.margins([(nz[0][sl], nz[1][:, sl], nz[2][sl]) for nz in noise], p)
                        for p, sl in zip(parts, _slices(parts))])
     margins.update(accept=min(acc_m), gap=min(gap))
@@ -439,7 +581,13 @@ def reference(cfg, fault=None, energy=None):
         for e in range(p["partner"].shape[0]):
             a = np.minimum(np.arange(n), p["partner"][e])
             u = hrc.cut(cfg["seed"], cfg["chain_offset"] + a, (e + 1) * cfg["every"] - 1, len(sites))[2]
-            out, _ = hrc.outcomes(p["log_ratio"][e], u, p["child_dist"][e], p["partner"][e], p["child_energy"][e], cfg["nmut"])
+            free = None
+            if pt is not None:
+                ev = hrc.event(p["post_accept"][(e + 1) * cfg["every"] - 1][0], wt, sites, e, (e + 1) * cfg["every"] - 1, cfg["deme"],
+                               cfg["seed"], cfg["chain_offset"], "round0" if fault == "round0" else None)
+                free = motifs.is_free(ev["children"], pt, wt, cfg["allow_native"])
+                free = free & free[p["partner"][e]]
+            out, _ = hrc.outcomes(p["log_ratio"][e], u, p["child_dist"][e], p["partner"][e], p["child_energy"][e], cfg["nmut"], free)
             assert np.array_equal(out, p["outcome"][e]) or fault
             with np.errstate(over="ignore"):
                 m = min(m, float(np.abs(np.exp(p["log_ratio"][e].astype(np.float64)) - u)[out < 2].min(initial=np.inf)))
@@ -451,7 +599,26 @@ def reference(cfg, fault=None, energy=None):
             seen = har.peeks_of(np.stack([post[0]] + [_np(s) for s, _ in parts[0]["post_accept"]]),
                                 np.stack([e_hist[0]] + [_np(e) for _, e in parts[0]["post_accept"]]), f_hist, wt)
         run.update(_observers(cfg, seen, accepted, U, rung_hist))
-    return dict(run=run, noise=noise, margins=margins, events=events)
+    out = dict(run=run, noise=noise, margins=margins, events=events, states=states,
+               proposals=np.stack([np.concatenate([_np(p["traces"][t]["proposal"]) for p in parts], 0) for t in range(T)]))
+    if dyn == "recombine":
+        out["pre_event"] = [parts[0]["post_accept"][(e + 1) * cfg["every"] - 1][0] for e in range(run["recomb"]["events"])]
+    if pt is not None:
+        log = [p["veto_log"] for p in parts]
+        veto, first, decided = (np.stack([np.concatenate([lg[t][k] for lg in log]) for t in range(T)]) for k in range(3))
+        run["forbid"] = dict(n_patterns=len(pt), allow_native=cfg["allow_native"], vetoes=cat("vetoes", 0),
+                             active=motifs.active_words(pt, L, wt, cfg["allow_native"]))
+        out.update(veto=veto, first_pattern=first, decided=decided)
+        events.update(vetoed=bool(veto.any()), accepted_move=bool((accepted.astype(bool) & (out["proposals"] != states[:-1]).any(2)).any()))
+        if fault is None:              # every state the run can show is free: what the observers hold is among them
+            assert motifs.is_free(states.reshape(-1, L), pt, wt, cfg["allow_native"]).all() and run["forbid"]["vetoes"].sum() == first[first >= 0].size
+            assert motifs.is_free(best_idx, pt, wt, cfg["allow_native"]).all()
+            if cfg["observers"] is not None:
+                assert motifs.is_free(run["rec"]["idx"].reshape(-1, L), pt, wt, cfg["allow_native"]).all()
+                ar = run["archive"]
+                assert all(motifs.is_free(ar["idx"][b, :ar["count"][b]], pt, wt, cfg["allow_native"]).all() for b in range(n) if ar["count"][b])
+                assert all(motifs.is_free(pk["idx"], pt, wt, cfg["allow_native"]).all() for pk in run["peeks"])
+    return out
 
 
 def _slices(parts):
@@ -463,27 +630,34 @@ def _slices(parts):
 
 
 def near_ties(ref):
-    """The kinds of decision of a reference run that sit inside their threshold (empty: the draw is kept)."""
-    return [k for k, v in ref["margins"].items() if not v > NEAR[k]]
+    """The kinds of decision of a reference run that sit inside their threshold (empty: the draw is kept). A run under forbidden
+    patterns that vetoed nothing or accepted no move is discarded with them."""
+    idle = [k for k in ("vetoed", "accepted_move") if ref["events"].get(k) is False]
+    return [k for k, v in ref["margins"].items() if not v > NEAR[k]] + idle
 
 
 _KEPT = {}
 
 
-def kept(seed, trials, dynamics=None, graph_len=0):
+def kept(seed, trials, dynamics=None, graph_len=0, forbid=False):
     """The first `trials` kept configurations of seed `seed` with their references: [(cfg, ref)], and the number of draws discarded.
     Slot i pins dynamics and library by turns, so that every combination comes up; a discarded draw is replaced by the next draw of
-    the same stream for the same slot. A pure function of its arguments (cached per process)."""
-    key = (seed, trials, dynamics, graph_len)
+    the same stream for the same slot. `forbid`: configurations with forbidden patterns, allow_native by turns behind the library
+    (dynamics x library x allow_native come round every 4 len(pool) slots); a draw for which no patterns could be built is
+    discarded too. A pure function of its arguments (cached per process)."""
+    key = (seed, trials, dynamics, graph_len) + ((True,) if forbid else ())
     if key not in _KEPT:
         rng = np.random.default_rng(seed)
-        pool = DYNAMICS if dynamics is None else tuple(dynamics)
+        pool = (REVERSIBLE if forbid else DYNAMICS) if dynamics is None else tuple(dynamics)
         out, discarded = [], 0
         while len(out) < trials:
             i = len(out)
-            cfg = draw(rng, pool[i % len(pool)], (i // len(pool)) % 2, graph_len)
-            ref = reference(cfg)
-            if near_ties(ref):
+            if forbid:
+                cfg = draw(rng, pool[i % len(pool)], (i // len(pool)) % 2, graph_len, True, (i // (2 * len(pool))) % 2 == 0)
+            else:
+                cfg = draw(rng, pool[i % len(pool)], (i // len(pool)) % 2, graph_len)
+            ref = reference(cfg) if cfg is not None else None
+            if ref is None or near_ties(ref):
                 discarded += 1
                 assert discarded <= 4 * trials, "the generator discards almost everything"
                 continue
@@ -604,6 +778,12 @@ def compare(cfg, run, ref):
             with np.errstate(invalid="ignore"):
                 d32 = (ce[rows, a] - pe[rows, a]) + (ce[rows, b] - pe[rows, b])
             same("recombination: log_ratio is not the fp32 sum of its own records", rc["log_ratio"], d32.astype(np.float32))
+    if cfg.get("patterns") is not None:
+        fb, eb = run["forbid"], exp["forbid"]
+        same("forbidden patterns: vetoes", fb["vetoes"], eb["vetoes"])
+        same("forbidden patterns: n_patterns", fb["n_patterns"], len(cfg["patterns"]))
+        same("forbidden patterns: allow_native", bool(fb["allow_native"]), cfg["allow_native"])
+        same("forbidden patterns: active", fb["active"], motifs.active_words(cfg["patterns"], cfg["L"], cfg["wt"], cfg["allow_native"]))
     if cfg["observers"] is not None:
         rec, erec = run["rec"], exp["rec"]
         for k in ("rows", "chain", "idx", "site_counts"):
@@ -619,3 +799,43 @@ def compare(cfg, run, ref):
         for k in hs.KEYS:
             same(f"statistics: {k}", run["stats"][k], exp["stats"][k])
     return why
+
+
+# ------------------------------------------------------------------------------------------------ what a pattern run showed
+def veto_facts(cfg, ref):
+    """What the vetoes of a kept configuration's reference run fell on: {item of tests/test_fuzz_modes_cpu.py's list: bool}. Every
+    position and match count is motifs.find / motifs.matches on the run's own proposals."""
+    pt, wt, L, T, n = cfg["patterns"], cfg["wt"], cfg["L"], cfg["T"], cfg["n"]
+    native, lib = cfg["allow_native"], cfg["library"]
+    veto, acc, props = ref["veto"], ref["run"]["tr"]["accepted"].astype(bool), ref["proposals"]
+    act = motifs.active_mask(pt, L, wt, native)
+    wt_hits = motifs.matches(np.asarray(wt)[None], pt)[0]                  # [M, L]
+    frozen = np.ones(L, bool)
+    frozen[cfg["min_pos"]:cfg["max_pos"] + 1] = False
+    if lib is not None:
+        frozen |= np.asarray(lib) == 0
+    f = dict.fromkeys(("start >= 64", "window across lanes 63 | 64", "last start", "context", "two patterns", "native elsewhere"), False)
+    for t, b in zip(*np.nonzero(veto)):
+        m, p = (int(v[0]) for v in motifs.find(props[t, b][None], pt, wt, native))
+        k = int(pt.lengths[m])
+        assert m >= 0 and m == ref["first_pattern"][t, b]
+        f["start >= 64"] |= p >= 64
+        f["window across lanes 63 | 64"] |= p < 64 <= p + k - 1
+        f["last start"] |= p == L - k
+        f["context"] |= bool(frozen[p:p + k].any())
+        f["two patterns"] |= int((motifs.matches(props[t, b][None], pt)[0] & act).any(1).sum()) >= 2
+        f["native elsewhere"] |= bool(native and wt_hits[m].any())
+    f["decided by the veto alone"] = bool(ref["decided"].any())
+    f["veto behind an accepted proposal"] = bool((veto[1:] & acc[:-1]).any())
+    f["accepted behind a veto"] = bool((acc[1:] & veto[:-1]).any())
+    f["outcome 4"] = cfg["dynamics"] == "recombine" and bool((ref["run"]["recomb"]["outcome"] == 4).any())
+    f["veto behind a replaced slot"] = False
+    if cfg["dynamics"] in ("anneal", "adaptive"):
+        par = ref["run"]["anneal"]["parent"]
+        f["veto behind a replaced slot"] = any(bool((veto[(e + 1) * cfg["every"]] & (par[e] != np.arange(n))).any())
+                                               for e in range(par.shape[0]) if (e + 1) * cfg["every"] < T)
+    f["veto behind a swap"] = False
+    if cfg["dynamics"] == "tempering":
+        h = ref["run"]["temp"]["hist"]
+        f["veto behind a swap"] = bool((veto[1:] & (h[1:T] != h[:T - 1])).any())
+    return f

@@ -55,23 +55,92 @@ def find_with(idx, pt, act):
 
 
 def constrained_iteration(energy, idx_cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, pt, allow_native=True, fault=None,
-                          keep_probs=False):
+                          keep_probs=False, stale=None):
     """One iteration of the mode for all chains: hr.reversible_iteration's proposal, ratio and refusals, and the decision
     acc = exp(log_acc) >= u and not refused and y free. A vetoed proposal records what a cap rejection records: accept bit 0,
-    the current state, energy and fitness; log_acc stays the computed value. Extra keys: veto bool [n], first_pattern int32 [n]."""
+    the current state, energy and fitness; log_acc stays the computed value. Extra keys: veto bool [n], first_pattern int32 [n]
+    (the pattern the counter counts), decided bool [n] (the vetoed proposals that u and the refusals would have let through).
+    `fault`: one of FAULTS or RUN_FAULTS; `stale`: the veto of the iteration before ('veto_stale' decides by it)."""
     out = hr.reversible_iteration(energy, idx_cur, idx_cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
     n = idx_cur.shape[0]
-    fp, _ = motifs.find(out["proposal"].numpy(), pt, np.asarray(wt_idx), allow_native)
+    y = out["proposal"].numpy()
+    if fault in ("last_start_skipped", "frozen_not_context", "native_per_pattern"):
+        act = faulty_active(pt, y.shape[1], np.asarray(wt_idx), allow_native, fault, _words(allowed, y.shape[1]))
+        fp, _ = find_with(y, pt, act)
+    else:
+        act = motifs.active_mask(pt, y.shape[1], np.asarray(wt_idx), allow_native)
+        fp, _ = motifs.find(y, pt, np.asarray(wt_idx), allow_native)
     veto = torch.as_tensor(fp >= 0)
+    passed = (torch.exp(out["log_acc"]) >= u) & ~out["refused"]
     if fault == "veto_through_u":                            # -inf in the ratio instead of an explicit rejection: u = 0 accepts
         acc = (torch.exp(torch.where(veto, torch.tensor(-np.inf), out["log_acc"])) >= u) & ~out["refused"]
+    elif fault == "veto_ignored":
+        acc = passed
+    elif fault == "veto_stale":                              # the byte the accept reads is the one the iteration before wrote
+        acc = passed & ~(torch.zeros(n, dtype=torch.bool) if stale is None else stale)
     else:
-        acc = (torch.exp(out["log_acc"]) >= u) & ~out["refused"] & ~veto
-    _, fit_x, _ = energy.energy_grad(idx_cur)
-    _, fit_y, _ = energy.energy_grad(out["proposal"])
+        acc = passed & ~veto
+    if fault == "highest_pattern_counted":
+        any_m = (motifs.matches(y, pt) & act[None]).any(axis=2)
+        fp = np.where(fp >= 0, any_m.shape[1] - 1 - any_m[:, ::-1].argmax(axis=1), -1).astype(np.int32)
+    if fault == "counted_only_when_it_decided":
+        fp = np.where(passed.numpy(), fp, -1).astype(np.int32)
     out.update(idx=torch.where(acc.reshape(n, 1), out["proposal"], idx_cur), energy=torch.where(acc, out["e_y"], out["e_x"]),
-               fitness=torch.where(acc, fit_y, fit_x), accepted=acc, veto=veto, first_pattern=fp)
+               fitness=torch.where(acc, out["fit_y"], out["fit_x"]), accepted=acc, veto=veto, first_pattern=fp, decided=veto & passed)
     return out
+
+
+def _words(allowed, L):
+    from ppde_amd import library as dl
+    return dl.as_words(dl.full_library(L) if allowed is None else allowed, L)
+
+
+# faults of a whole run, next to FAULTS: the accept phase deaf to the byte, or reading the byte of the iteration before (the veto
+# enqueued behind the accept), recombination's children in the counters, a counter that counts only the vetoes that changed the
+# outcome, the highest matching pattern in the counter cell
+RUN_FAULTS = ("veto_ignored", "veto_stale", "children_counted", "counted_only_when_it_decided", "highest_pattern_counted")
+
+
+class Constraint:
+    """The mode as every reversible dynamics runs it, stated once: `iteration` is constrained_iteration on the energy object the
+    mode's helper built (the beta-scaled one under tempering and annealing) and counts the counters as the header says -- the lowest
+    matching active pattern, whether or not the proposal would otherwise have been accepted --; `children_free` is the check of a
+    recombination event, whose children are not counted. forbidden = (patterns, allow_native)."""
+
+    def __init__(self, forbidden, n, fault=None):
+        self.pt, self.allow_native, self.fault = motifs.parse(forbidden[0]), bool(forbidden[1]), fault
+        self.vetoes = np.zeros((n, len(self.pt)), np.int64)
+        self.stale = None
+        self.log = []                                        # per iteration (veto, first_pattern, decided)
+
+    def iteration(self, energy, idx_cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=False):
+        out = constrained_iteration(energy, idx_cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, self.pt, self.allow_native,
+                                    self.fault, keep_probs, self.stale)
+        hit = np.flatnonzero(out["first_pattern"] >= 0)
+        np.add.at(self.vetoes, (hit, out["first_pattern"][hit]), 1)
+        self.stale = out["veto"]
+        self.log.append((out["veto"].numpy().copy(), out["first_pattern"].copy(), out["decided"].numpy().copy()))
+        return out
+
+    def children_free(self, children, wt_idx, partner):
+        """bool [n]: BOTH children of the slot's pair are free (an event's outcome 4 where not)."""
+        fp, _ = motifs.find(np.asarray(children), self.pt, np.asarray(wt_idx), self.allow_native)
+        if self.fault == "children_counted":
+            hit = np.flatnonzero(fp >= 0)
+            np.add.at(self.vetoes, (hit, fp[hit]), 1)
+        free = fp < 0
+        if self.fault == "one_child_only":                   # the lower slot's child alone
+            return free[np.minimum(np.arange(free.size), np.asarray(partner))]
+        return free & free[np.asarray(partner)]
+
+
+def iteration_of(forbidden, n, fault=None):
+    """(iteration, constraint) a mode helper runs: hr.reversible_iteration and None without patterns."""
+    if forbidden is None:
+        return (lambda energy, cur, wt, U, q, u, lo, hi, thr, allowed, keep_probs=False:
+                hr.reversible_iteration(energy, cur, cur, wt, U, q, u, lo, hi, thr, allowed, keep_probs=keep_probs)), None
+    c = Constraint(forbidden, n, fault)
+    return c.iteration, c
 
 
 def constrained_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_length, nmut_threshold, allowed, pt,
@@ -86,13 +155,11 @@ def constrained_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pa
         allowed = dl.full_library(L)
     e0, f0 = energy.energy(idx0)
     e_hist, f_hist, states, accs, traces = [e0], [f0], [idx0.clone()], [], []
-    vetoes = np.zeros((n, len(pt)), np.int64)
+    con = Constraint((pt, allow_native), n, fault)
     cur = idx0.clone()
     for it in range(num_steps):
         U, q, u = noise(it)
-        out = constrained_iteration(energy, cur, wt, U, q, u, min_pos, max_pos, thr, allowed, pt, allow_native, fault, keep_probs)
-        hit = np.flatnonzero(out["first_pattern"] >= 0)
-        np.add.at(vetoes, (hit, out["first_pattern"][hit]), 1)
+        out = con.iteration(energy, cur, wt, U, q, u, min_pos, max_pos, thr, allowed, keep_probs)
         cur = out["idx"].clone()
         e_hist.append(out["energy"]); f_hist.append(out["fitness"]); accs.append(out["accepted"]); traces.append(out)
         states.append(cur.clone())
@@ -100,7 +167,7 @@ def constrained_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pa
     best_e, best_t = torch.max(e_hist, 0)
     ar = torch.arange(n)
     return dict(best_idx=states[best_t, ar], best_energy=best_e, best_fitness=f_hist[best_t, ar], energy_history=e_hist,
-                fitness_history=f_hist, states=states, accepted=torch.stack(accs, 0), final_idx=cur, traces=traces, vetoes=vetoes)
+                fitness_history=f_hist, states=states, accepted=torch.stack(accs, 0), final_idx=cur, traces=traces, vetoes=con.vetoes, veto_log=con.log)
 
 
 def constrain_kernel(K, inside, free):

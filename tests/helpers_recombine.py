@@ -81,14 +81,18 @@ def event(X, wt, sites, s, it, D, seed, chain_offset=0, fault=None):
 
 
 def recombined_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_length, nmut_threshold, every, D, seed, allowed,
-                   chain_offset=0, fault=None, trace=False, keep_probs=False):
+                   chain_offset=0, fault=None, trace=False, keep_probs=False, forbidden=None, motif_fault=None):
     """The CPU iteration of reversible mode (helpers_reversible.reversible_iteration) on explicit noise with the events of the
     rule: dict of states [T + 1, n, L], energy_history / fitness_history [T + 1, n] (row it + 1 after the event), accepted
     [T, n] (the slots' own Metropolis results) and the event records partner, lo, hi, differ, child_dist, outcome, log_ratio,
     pre_energy, child_energy [events, n]. `trace`: also traces (the iterations' dicts; `keep_probs`: with their forward rows),
     post_accept (states, energies per iteration, in front of the event) and the running best by the accept phase's strict rule
-    (best_idx, best_energy, best_fitness, best_step), as helpers_anneal.annealed_run keeps them."""
+    (best_idx, best_energy, best_fitness, best_step), as helpers_anneal.annealed_run keeps them.
+    `forbidden` = (patterns, allow_native): the iteration runs through helpers_motifs' constrained iteration, a pair with a child
+    that is not free takes outcome 4 (`outcome_of`), and the result gains vetoes int64 [n, M], which the children never enter
+    (`motif_fault`: one of helpers_motifs' faults)."""
     import torch
+    import helpers_motifs as hmot
     import helpers_reversible as hr
     from ppde_amd import library as dl
     thr = hr._threshold(nmut_threshold)
@@ -107,9 +111,10 @@ def recombined_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas
         better = e_row > best_e                                              # strict: the accept phase's rule
         best_e[better], best_f[better], best_t[better], best_x[better] = e_row[better], f_row[better], t, x_rows[better]
 
+    iteration, con = hmot.iteration_of(forbidden, n, motif_fault)
     for it in range(num_steps):
         U, q, u = noise(it)
-        out = hr.reversible_iteration(energy, cur, cur, wt, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
+        out = iteration(energy, cur, wt, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
         cur = out["idx"].clone()
         e, f = out["energy"].numpy().copy(), out["fitness"].numpy().copy()
         accs.append(out["accepted"].numpy())
@@ -127,7 +132,8 @@ def recombined_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas
                 hit = np.exp(d) >= ev["u"]
             finite = np.isfinite(ce) & np.isfinite(ce[pa])
             capped = (ev["child_dist"] >= thr) | (ev["child_dist"][pa] >= thr)
-            outcome = np.where(~finite, 3, np.where(capped, 2, np.where(hit, 1, 0))).astype(np.uint8)
+            free = None if con is None else con.children_free(ev["children"], wt.numpy(), pa)
+            outcome = outcome_of(finite, capped, free, hit).astype(np.uint8)
             for k, v in (("partner", pa), ("lo", ev["lo"]), ("hi", ev["hi"]), ("differ", ev["differ"]), ("child_dist", ev["child_dist"]),
                          ("outcome", outcome), ("log_ratio", d), ("pre_energy", e.copy()), ("child_energy", ce)):
                 rec[k].append(np.asarray(v))
@@ -144,17 +150,29 @@ def recombined_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas
     res.update({k: np.stack(v) if v else np.zeros((0, n)) for k, v in rec.items()})
     if trace:
         res.update(traces=traces, post_accept=post, best_idx=best_x, best_energy=best_e, best_fitness=best_f, best_step=best_t)
+    if con is not None:
+        res.update(vetoes=con.vetoes, veto_log=con.log)
     return res
 
 
-def outcomes(log_ratio, u, child_dist, partner, child_energy, nmut):
-    """The decision in fp64 on recorded values: (outcome [n], margin [n] = |exp(d) - u| / max(exp(d), u) where u decided)."""
+def outcome_of(finite, capped, pair_free, hit):
+    """The outcome of every slot's pair: 3 a non-finite child energy, 2 a child at or over the cap, 4 a child that is not free
+    (`pair_free` bool [n], None without forbidden patterns) -- checked behind 3 and 2 and in front of u --, then 1 / 0 by u."""
+    out = np.where(hit, 1, 0)
+    if pair_free is not None:
+        out = np.where(pair_free, out, 4)
+    return np.where(~finite, 3, np.where(capped, 2, out))
+
+
+def outcomes(log_ratio, u, child_dist, partner, child_energy, nmut, pair_free=None):
+    """The decision in fp64 on recorded values: (outcome [n], margin [n] = |exp(d) - u| / max(exp(d), u) where u decided).
+    `pair_free` bool [n]: forbidden patterns are set and both children of the slot's pair are free (outcome 4 where not)."""
     d = np.asarray(log_ratio, dtype=np.float64)
     with np.errstate(over="ignore", invalid="ignore"):
         ed = np.exp(d)
     finite = np.isfinite(child_energy) & np.isfinite(np.asarray(child_energy)[partner])
     capped = (nmut > 0) & ((child_dist >= nmut) | (np.asarray(child_dist)[partner] >= nmut)) if nmut > 0 else np.zeros(d.size, bool)
-    out = np.where(~finite, 3, np.where(capped, 2, np.where(ed >= u, 1, 0)))
+    out = outcome_of(finite, capped, pair_free, ed >= u)
     with np.errstate(invalid="ignore", divide="ignore"):
         margin = np.where(finite & ~capped, np.abs(ed - u) / np.maximum(ed, u), np.inf)
     return out, margin

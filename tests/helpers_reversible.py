@@ -84,7 +84,7 @@ def reversible_iteration(energy, idx_cur, idx_reject, wt_idx, U, q, u, min_pos, 
     out = dict(idx=torch.where(acc.reshape(n, 1), cur, idx_reject), energy=torch.where(acc, e_y, e_x),
                fitness=torch.where(acc, fit_y, fit_x), accepted=acc, log_acc=log_acc, flat=torch.stack(flats, 0), proposal=cur,
                logp_fwd=torch.stack(logp_fwd, 0), logp_rev=torch.stack(logp_rev, 0), undo=torch.stack(undo, 0), refused=refused,
-               e_x=e_x, e_y=e_y, grad_x=g_x, grad_y=g_y)
+               e_x=e_x, e_y=e_y, fit_x=fit_x, fit_y=fit_y, grad_x=g_x, grad_y=g_y)
     if keep_probs:
         out["p_fwd"] = torch.stack(p_fwd, 0)
     return out

@@ -69,10 +69,12 @@ def swap_decision(beta_lo, beta_hi, e_a, e_b, u):
 
 
 def tempered_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_length, nmut_threshold, betas, swap_every,
-                 seed=0, chain_offset=0, allowed=None, trace=False, keep_probs=False, swap_u=None):
+                 seed=0, chain_offset=0, allowed=None, trace=False, keep_probs=False, swap_u=None, forbidden=None, motif_fault=None):
     """The whole algorithm on explicit noise: what hr.reversible_run returns (histories and best states on the UNTEMPERED
     energy), plus rung_history uint8 [T+1, n], rung / beta [n] at the end, swap_attempts / swap_accepts int64 [n/R, R-1] and
-    swap_margin, the smallest |d - log u| over the swap decisions. `swap_u`: callable it -> u [n/R, R] replacing Philox."""
+    swap_margin, the smallest |d - log u| over the swap decisions. `swap_u`: callable it -> u [n/R, R] replacing Philox.
+    `forbidden` = (patterns, allow_native): the iteration runs through helpers_motifs' constrained iteration on the
+    same beta-scaled energy object, and the result gains vetoes int64 [n, M] (`motif_fault`: one of helpers_motifs' faults)."""
     betas = np.asarray(betas, dtype=np.float32)
     R = int(betas.size)
     thr = hr._threshold(nmut_threshold)
@@ -92,10 +94,12 @@ def tempered_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_l
     e_hist, f_hist, states, accs, traces, rung_hist = [e0], [f0], [idx0.clone()], [], [], [rung.astype(np.uint8)]
     cur = idx0.clone()
     margin = np.inf
+    import helpers_motifs as hmot
+    iteration, con = hmot.iteration_of(forbidden, n, motif_fault)
     for it in range(num_steps):
         U, q, u = noise(it)
         sc = ScaledEnergy(energy, beta)
-        out = hr.reversible_iteration(sc, cur, cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
+        out = iteration(sc, cur, wt_idx, U, q, u, min_pos, max_pos, thr, allowed, keep_probs=keep_probs)
         (ex, fx), (ey, fy) = sc.raw
         a = out["accepted"]
         cur = out["idx"].clone()
@@ -130,6 +134,8 @@ def tempered_run(energy, idx0, wt_idx, noise, num_steps, min_pos, max_pos, pas_l
                swap_margin=margin)
     if trace:
         res["traces"] = traces
+    if con is not None:
+        res.update(vetoes=con.vetoes, veto_log=con.log)
     return res
 
 

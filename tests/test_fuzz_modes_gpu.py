@@ -3,7 +3,10 @@ child process (PPDE_GRAPH_LEN and PPDE_CHAIN_SPEC are read once per process), on
   default_env      the default environment: runs of 6..14 iterations fit no graph segment and are issued eagerly;
   graph_len_4      PPDE_GRAPH_LEN=4: the short runs replay graphs under every dynamics (with recombination where 4 is a multiple of
                    `every`); the script demands that every dynamics replayed some steps;
-  general_kernels  PPDE_CHAIN_SPEC=0 on the default and library trials: the general chain kernels in place of the pinned ones.
+  general_kernels  PPDE_CHAIN_SPEC=0 on the default and library trials: the general chain kernels in place of the pinned ones;
+  patterns         FZ_FORBID=1: the five reversible dynamics x library x allow_native with forbidden patterns built on each
+                   configuration's unconstrained reference; veto counters, active words and outcome 4 compared exactly;
+  patterns_graph_len_4  the same axes under PPDE_GRAPH_LEN=4: the veto launch inside replayed segments.
 tests/test_fuzz_modes_cpu.py shows what these lists cover and that the comparison sees every planted fault."""
 import os
 import subprocess

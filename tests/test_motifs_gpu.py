@@ -402,9 +402,8 @@ def test_invariants_under_recombination_and_outcome_4(toy):
         plain, margin = hrc.outcomes(st["log_ratio"][s], ev["u"], st["child_dist"][s], pa, st["child_energy"][s], nmut)
         rejected = st["outcome"][s] != 1
         assert np.array_equal(st["child_dist"][s][rejected], ev["child_dist"][rejected])
-        bad_child = ~motifs.is_free(ev["children"], pt, c["wt"])
-        bad_pair = bad_child | bad_child[pa]
-        want = np.where((plain < 2) & bad_pair, 4, plain)
+        free_child = motifs.is_free(ev["children"], pt, c["wt"])
+        want, _ = hrc.outcomes(st["log_ratio"][s], ev["u"], st["child_dist"][s], pa, st["child_energy"][s], nmut, pair_free=free_child & free_child[pa])
         sure = rejected & ((margin > 1e-5) | (want >= 2))
         assert np.array_equal(st["outcome"][s][sure], want[sure]), s
         taken = ~rejected
